@@ -1,15 +1,20 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/sec at 640x640 for the VGGHeads forward path (BASELINE.json).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus N ...          (no torchrun environment: spawns the N ranks itself through torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps of the headline workload and prints the JSON line (its `roofline` from the HIP events
+of the timed steps, without traffic).  --dump-outputs DIR then writes the detections of the last timed forward (rank 0) as DIR/*.npy
+(dump_detections).  Everything else below -- the secondary workloads, the FLAME decode sweep, the overlap check, power / throttle
+sampling, live PMC traffic, cpu_baseline and the deviation reports -- runs with --full only.
 
 One step = one pass of the whole hot path over one batch that is already resident in HBM:
     network (stem + ~125 fused convs) -> box/score decode -> per-image top-k(1000) -> candidate gather + FLAME
     fix-up -> NMS (every image) -> compaction -> FLAME decode of every surviving head -> (N>1) RCCL gather to rank 0.
 Workload at N=1 = BASELINE.json configs[2]: VGGHeads_L, bf16, batch 64 @ 640x640 with FLAME decode per detection (per GPU; weak
-scaling: configs[3] = 8 x this).  Measured in the same run and reported inside `config` (and on stderr):
+scaling: configs[3] = 8 x this).  With --full, measured in the same run and reported inside `config` (and on stderr):
     configs[1]  VGGHeads_M, batch 32 @ 640                              -> config.secondary_vgg_heads_m_b32
     configs[4]  VGGHeads_L @ 1280x1280 crowd (>= 32 heads / image)      -> config.secondary_vgg_heads_l_b16_1280_crowd (one GPU's shard of the 8-GPU config) and
                                                                            config.secondary_vgg_heads_l_b256_1280_crowd (the stated batch on ONE GPU, chunked arena)
@@ -20,7 +25,7 @@ Weights / FLAME constants are seeded synthetic tensors of the exact architecture
 The random-weight network's scores are arbitrary, so the NMS confidence threshold is calibrated ONCE (untimed) so that
 about 3 heads per image survive; nothing is skipped inside the timed region.
 
-The JSON line also carries
+The JSON line also carries (`traffic` and cpu_baseline with --full)
   roofline     : the conv kernel family against the dense bf16 MFMA peak, measured live with HIP events on the engine's stream around
                  the network part of every timed step; `traffic` = HBM bytes per forward from PMC passes (FETCH_SIZE / WRITE_SIZE,
                  separate rocprofv3 runs of tools/traffic_run.py launched by this script when rocprofv3 is on the box, else the
@@ -30,6 +35,7 @@ The JSON line also carries
 The run refuses to start with any VGH_* environment variable set (experiment knobs must not leak into a measurement).
 """
 import argparse
+import contextlib
 import json
 import os
 import shutil
@@ -234,6 +240,34 @@ def deviation_from_oracle(variant: str, precision: str, ref: dict, dev) -> dict:
                 "top100_log_scale_max_abs_err": float((torch.log(flame[0, :100, 412].cpu()) - torch.log(of_at[:, 412])).abs().max())}
     finally:
         eng.close()
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_detections(det, out_dir: str, budget: int = DUMP_BUDGET_BYTES) -> None:
+    """--dump-outputs: what a caller of the timed path receives from one forward (engine.Detections), valid rows only, image-major:
+    counts [B]; boxes [n, 4], scores [n], flame_params [n, 413] (the first counts[b] rows of image b); head_image [n], head_pose [n, 3],
+    vertices_3d [n, V, 3].  float32 as computed, the integer arrays as float64.  When the vertices would take the total past `budget`, a
+    seeded sample of their rows is written (sorted, indices in vertices_3d_rows.npy)."""
+    import numpy as np
+    import torch
+
+    counts = det.counts.cpu().long()
+    valid = torch.arange(det.boxes.shape[1])[None, :] < counts[:, None]
+    arrays = {"counts": counts.double(), "boxes": det.boxes.cpu()[valid], "scores": det.scores.cpu()[valid], "flame_params": det.flame_params.cpu()[valid]}
+    if det.vertices_cap is not None:
+        arrays.update(head_image=det.head_image.cpu().double(), head_pose=det.head_pose.cpu(), vertices_3d=det.vertices_3d.cpu())
+    arrays = {k: v.numpy() for k, v in arrays.items()}
+    vert = arrays.get("vertices_3d")
+    if vert is not None and sum(a.nbytes for a in arrays.values()) > budget:
+        room = budget - sum(a.nbytes for k, a in arrays.items() if k != "vertices_3d") - 8 * vert.shape[0]  # 8 bytes per row: the row indices
+        rows = np.sort(np.random.default_rng(0).choice(vert.shape[0], max(0, room // vert[0].nbytes), replace=False))
+        arrays.update(vertices_3d=vert[rows], vertices_3d_rows=rows.astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a))
+    print(f"[bench] --dump-outputs: {', '.join(f'{k}{list(a.shape)}' for k, a in arrays.items())} -> {out_dir}", file=sys.stderr)
 
 
 def make_step(eng, flame, images, unpad, conf, B, slots, gat, overlap, use_graph, n_heads_all, ev0=None, ev1=None, ready=None):
@@ -522,6 +556,9 @@ def main():
     ap.add_argument("--batch", type=int, default=64, help="images per GPU per step")
     ap.add_argument("--image-size", type=int, default=640)
     ap.add_argument("--heads-per-image", type=float, default=3.0)
+    ap.add_argument("--full", action="store_true", help="also run everything beyond the headline: secondary workloads, FLAME decode sweep, overlap check, power / throttle "
+                    "sampling, live PMC traffic, cpu_baseline and the deviation reports (the --no-* switches below then drop parts of it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps write the detections of the last timed forward as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-accuracy", action="store_true", help="skip the (untimed) deviation reports of the bf16 / parity modes")
     ap.add_argument("--no-overlap-check", action="store_true", help="skip the untimed overlapped-vs-serial post-stage check before the timed steps (N = 1 only)")
@@ -534,7 +571,8 @@ def main():
     ap.add_argument("--exchange", action="store_true", help="run the N>1 step (output slots + RCCL gather to rank 0 on the communication stream) even with one rank")
     ap.add_argument("--tuning", default=None, help="tile table to load instead of head_detector_amd/tuning/conv_cfg.json")
     ap.add_argument("--precision", default="bf16", help="activation format of the main workload (bf16 = the headline; fp16x3 / fp32 are the parity modes)")
-    ap.add_argument("--traffic", default="auto", choices=["auto", "live", "file", "off"], help="roofline.traffic: PMC passes run by this script (live), the committed profile (file)")
+    ap.add_argument("--traffic", default=None, choices=["auto", "live", "file", "off"], help="roofline.traffic: PMC passes run by this script (live), the committed profile (file); "
+                    "default auto with --full, off without")
     ap.add_argument("--inner", type=int, default=8, help="forwards (engine calls over one resident batch each) per timed step: the driver's 20-step run then times "
                     "> 2 s instead of 0.27 s, i.e. one clock / power state covers the region; ms_per_step is per step, config.ms_per_forward per forward")
     ap.add_argument("--dry-run-cpu", action="store_true", help="N>1 first-contact kit without GPUs: this script's step closure + DetectionGatherer on gloo ranks with a stand-in "
@@ -542,6 +580,8 @@ def main():
     ap.add_argument("--compact-gather", action="store_true", help="N>1: send packed survivor rows (DetectionGatherer(compact_rows=...)) instead of the [B, keep, 418] capacity slab")
     ap.add_argument("--ramp-steps", type=int, default=30, help="untimed steps before the W warm-up steps (clock ramp of a cold box; 0 = off)")
     args = ap.parse_args()
+    if args.traffic is None:
+        args.traffic = "auto" if args.full else "off"
     if args.dry_run_cpu:  # control flow of the N>1 step on CPU ranks (no GPU, no kernels, no measurement): tools/dryrun_dist.py
         sys.path.insert(0, os.path.join(ROOT, "tools"))  # spawn'ed ranks inherit sys.path and import the module by name
         import dryrun_dist as mod
@@ -576,7 +616,7 @@ def main():
     steered = [False]
 
     def run_workload(variant: str, B: int, steps: int, warmup: int, per_layer_path=None, image_size: int = S, heads_per_image: float = args.heads_per_image,
-                     precision: str = "bf16", inner: int = 1) -> dict:
+                     precision: str = "bf16", inner: int = 1, dump_dir=None) -> dict:
         """The timed region of the contract for one (variant, batch): W warm-up steps, barrier + synchronize, K steps, synchronize +
         barrier, max over ranks.  HIP events on the engine's stream bracket the network part of every timed step."""
         # post stages of batch s under the network of batch s+1: pays from batch 8 up (measured r02: 2.89 vs 2.95 ms at B=8, 13.25 vs 13.42 at B=64), costs
@@ -640,7 +680,7 @@ def main():
         # lane (csrc/streams.hip::blocked_behind, profiles/r06_starved_side_stream_classes.txt) -- and the library now acquires the side stream clear of those pipes, so the
         # workaround is gone: the overlap stays on; both timings and the pipe test are only REPORTED (config.*.overlap_check), so that a regression would be seen, not hidden
         overlap_check = None
-        if overlap and world == 1 and not args.no_overlap_check:
+        if args.full and overlap and world == 1 and not args.no_overlap_check:
             def probe(n=4 * max(inner, 2)):
                 eng.join()
                 torch.cuda.synchronize()
@@ -666,10 +706,10 @@ def main():
         if dist.is_initialized():
             dist.barrier()
         torch.cuda.synchronize()
-        with ThrottleProbe(local) as throttle, PowerSampler(local) as power:
+        with ThrottleProbe(local) if args.full else contextlib.nullcontext() as throttle, PowerSampler(local) if args.full else contextlib.nullcontext() as power:
             t0 = time.perf_counter()
             for i in range(nfw):  # K steps of `inner` forwards each
-                step(i)
+                det = step(i)
             step.flush()  # the exchanges of the last two batches
             eng.join()
             last_exchanges = []
@@ -699,6 +739,8 @@ def main():
             print(f"[bench] WARNING: the compact exchange cut {dropped} survivor rows at its cap in the last two steps", file=sys.stderr)
         net_ms = sum(a.elapsed_time(b) for a, b in zip(ev0, ev1)) / max(nfw, 1)  # per forward
         heads = int(n_heads_all.sum().item())
+        if dump_dir and rank == 0:
+            dump_detections(det, dump_dir)
         if per_layer_path and rank == 0:
             eng.join()
             eng.set_split(1)  # per-op events make sense on one stream only: the table is the single-stream view of every op
@@ -707,8 +749,9 @@ def main():
         fp8_flops = 2.0 * sum(op["macs"] for op in eng.program.ops if arch.op_touches_fp8(eng.program, op) and eng.program.bufs[op["in_buf"]]["is_f32"] in arch.Q8_FMTS)
         out = dict(variant=variant, B=B, steps=steps, warmup=warmup, dt=dt, net_ms=net_ms, fp8_flops_per_image=fp8_flops, fp8_links=sum(bf["is_f32"] in arch.Q8_FMTS for bf in eng.program.bufs), heads_per_img=heads / max(nfw * B, 1), overlap=overlap, inner=inner,
                    value=B * world * nfw / dt, flops_per_image=eng.flops_per_image, conv_tflops=eng.flops_per_image * B / (net_ms * 1e-3) / 1e12,
-                   alg_bytes=alg["read"] + alg["write"], arena_batch=eng.arena_batch, power=power.summary(), exchange_dropped_rows=dropped, per_rank=per_rank, overlap_check=overlap_check)
-        thr = throttle.summary()
+                   alg_bytes=alg["read"] + alg["write"], arena_batch=eng.arena_batch, power=power.summary() if power else None, exchange_dropped_rows=dropped, per_rank=per_rank,
+                   overlap_check=overlap_check)
+        thr = throttle.summary() if throttle else None
         if thr and out["power"] is not None:
             out["power"]["throttle"] = thr
         elif thr:
@@ -751,7 +794,7 @@ def main():
                 "conv_tflops": round(m["conv_tflops"], 2), "roofline_frac": round(m["conv_tflops"] / MFMA_BF16_DENSE_PEAK_TFLOPS, 4), "steps": m["steps"],
                 "heads_per_image_decoded": round(m["heads_per_img"], 2), **({"overlap_check": m["overlap_check"]} if m.get("overlap_check") else {})}
 
-    main_run = run_workload(args.variant, args.batch, args.steps, args.warmup, args.per_layer, precision=args.precision, inner=max(1, args.inner))
+    main_run = run_workload(args.variant, args.batch, args.steps, args.warmup, args.per_layer, precision=args.precision, inner=max(1, args.inner), dump_dir=args.dump_outputs)
     B = args.batch
 
     # FLAME decode alone (second headline metric): us per head at n = 96 (all 400 coefficients), straight through the C ABI with preallocated outputs -- the
@@ -775,8 +818,7 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) * 1e3 / iters
 
-    decode_sweep = {f"n{k}": round(decode_us(k), 2) for k in (1, 8, 32, 96, 512, 1024)}
-    decode_us_per_head = decode_sweep["n96"] / 96
+    decode_sweep = {f"n{k}": round(decode_us(k), 2) for k in (1, 8, 32, 96, 512, 1024)} if args.full else None
 
     if rank == 0:
         inner = main_run["inner"]
@@ -785,7 +827,9 @@ def main():
                   "global_batch": B * world, "forwards_per_step": inner, "images_per_step": inner * B * world,
                   "ms_per_forward": round(main_run["dt"] / (args.steps * inner) * 1e3, 3), "net_ms_per_forward": round(main_run["net_ms"], 3), "image_size": S, "parallelism": f"dp{world}", "gflop_per_image": round(main_run["flops_per_image"] / 1e9, 2),
                   "graph": bool(args.graph), "exchange_to_rank0": bool(world > 1 or args.exchange), "overlap_post": main_run["overlap"], "batch_split": nsplit,
-                  "flame_decode_us_per_head_n96": round(decode_us_per_head, 3), "flame_decode_us_per_call_all400": decode_sweep, "net_ms_per_step": round(main_run["net_ms"] * inner, 3), "ramp_steps": args.ramp_steps}
+                  "net_ms_per_step": round(main_run["net_ms"] * inner, 3), "ramp_steps": args.ramp_steps}
+        if decode_sweep:
+            config.update(flame_decode_us_per_head_n96=round(decode_sweep["n96"] / 96, 3), flame_decode_us_per_call_all400=decode_sweep)
         if main_run["overlap_check"]:
             config["overlap_check"] = main_run["overlap_check"]  # untimed report: overlapped vs serial post stages on this engine + the pipe test of its side stream (the overlap stays on)
         if main_run["power"]:
@@ -795,7 +839,7 @@ def main():
         if main_run["exchange_dropped_rows"]:
             config["exchange_dropped_rows"] = main_run["exchange_dropped_rows"]
         sec_steps = max(50, args.steps // 2)
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             if (args.variant, B) != ("vgg_heads_m", 32):
                 m = run_workload("vgg_heads_m", 32, sec_steps, args.warmup)
                 config["secondary_vgg_heads_m_b32"] = brief(m)
@@ -884,7 +928,7 @@ def main():
             "ms_per_step": round(main_run["dt"] / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": args.precision, "data": "synthetic", "config": config, "roofline": roof,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"], ref = cpu_baseline(args.variant, S, flame_model)
             if not args.no_accuracy and S == 640:
                 # checker role of the oracle: every precision mode on the oracle's image (parity_mode.vs_oracle is what north_star's bar reads)

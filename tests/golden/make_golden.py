@@ -86,6 +86,24 @@ def _load(name):
     return mod
 
 
+def write_raster_live(ref):
+    """raster_live.npz: the reference's rasterize_kernel.cpp (oracle/_ref, `ref_rasterize`) on the meshes of
+    tests/test_oracle_golden.py::test_raster_oracle_matches_live_reference_build, clipped and unclipped, both row orders."""
+    from oracle import raster_oracle as ro
+
+    cases = {}
+    for seed in (31, 32, 33):
+        ver, tri, col = ro.random_mesh(seed, n_side=9 + seed % 5, size=100 + 20 * (seed % 3), centre=(20 + 30 * (seed % 4), 70), depth_scale=25)
+        bg = np.random.default_rng(seed).integers(0, 256, (96, 128, 3), dtype=np.uint8)
+        cases.update({f"s{seed}_ver": ver, f"s{seed}_tri": tri, f"s{seed}_col": col, f"s{seed}_bg": bg})
+        for rev in (False, True):
+            img = bg.copy()
+            zb = np.zeros((96, 128), dtype=np.float32) - 1e8
+            ref.ref_rasterize(img.ctypes.data, ver.ctypes.data, tri.ctypes.data, col.ctypes.data, zb.ctypes.data, tri.shape[0], 96, 128, 3, 1.0, int(rev))
+            cases[f"s{seed}_rev{int(rev)}_out"] = img
+    np.savez_compressed(os.path.join(OUT, "raster_live.npz"), **cases)
+
+
 def main():
     _stub_modules()
     head_info = _load("head_info")
@@ -229,6 +247,7 @@ def main():
         pncc_triangles=proc.triangles, pncc_colors=proc.colors, heads=np.stack(heads_v), heads_after=np.stack([h.vertices_3d for h in heads]),
         image_shape=np.array(image.shape), pncc=pncc_img, head_indices=hidx, bboxes=np.array([[b.x, b.y, b.w, b.h] for b in bb]), **cases,
     )
+    write_raster_live(ref)
     # ---- (g) PredictionResult.save_meshes / MeshSaver (detection_result.py:22-35,73-78): the OBJ text the reference writes ------
     _load("draw_utils")  # cv2 is only touched inside the draw functions
     det = _load("detection_result")

@@ -2,6 +2,7 @@
 """Generate tests/golden/head_decode.npz by RUNNING THE REFERENCE's own head / decoding / post-prediction code.
 
     python tests/golden/make_golden_heads.py          (build container only: needs /root/reference)
+    MKL_CBWR=COMPATIBLE python tests/golden/make_golden_heads.py --tail      (head_tail_compatible.npz, see write_tail_compatible)
 
 Real reference code that runs here, imported unmodified from /root/reference/yolo_head_training/yolo_head/:
   * yolo_head_dfl_head.py   YoloHeadsDFLHead.__init__ / forward   (rows a5: stems, towers, six FLAME branches, tanh*3, exp/0.05,
@@ -187,6 +188,45 @@ def _head_conf(variant: str, level: int) -> dict:
         flame_transformation_inter_channels=h["tr_inter"], shared_stem=False, width_mult=h["width_mult"], first_conv_group_size=0, stride=arch.STRIDES[level], reg_max=16)}
 
 
+def _ref_heads(ndfl, variant: str, seed: int):
+    """The reference's YoloHeadsNDFLHeads of `variant` on the shared seeded weights, eval mode; also its input channels."""
+    v = arch.VARIANTS[variant]
+    in_ch = (v["neck"][1][0], v["neck"][2][0], v["neck"][3][0])
+    heads = ndfl.YoloHeadsNDFLHeads(num_classes=1, in_channels=in_ch, heads_list=[_head_conf(variant, i) for i in range(3)], reg_max=16)
+    sd = {k[len("heads."):]: torch.from_numpy(a) for k, a in arch.random_state_dict(variant, seed).items() if k.startswith("heads.")}
+    missing, unexpected = heads.load_state_dict(sd, strict=False)
+    assert not unexpected and all(k.endswith("num_batches_tracked") for k in missing), (missing[:5], unexpected[:5])
+    return heads.eval(), in_ch
+
+
+def write_tail_compatible():
+    """head_tail_compatible.npz: YoloHeadsDFLHead.forward's activation tail (tanh * 3, exp / 0.05, zero padding, concat) on the raw branch
+    outputs stored in head_decode.npz (forward hooks hand them to the tail in place of the branch convs), evaluated with MKL in its
+    COMPATIBLE branch.  torch's CPU tanh / exp call MKL's vector math, whose default branch rounds differently (1 - 2 ulp) from one CPU
+    vendor or instruction set to the next; the COMPATIBLE branch gives the same bits on every x86-64 host."""
+    assert os.environ.get("MKL_CBWR") == "COMPATIBLE", "MKL reads MKL_CBWR at start-up: MKL_CBWR=COMPATIBLE python tests/golden/make_golden_heads.py --tail"
+    _install_shells()
+    import yolo_head.yolo_head_dfl_head as dfl
+    import yolo_head.yolo_head_ndfl_heads as ndfl
+
+    _Factory.registry["YoloHeadsDFLHead"] = dfl.YoloHeadsDFLHead
+    g = np.load(os.path.join(OUT, "head_decode.npz"))
+    out = {}
+    for variant, seed in (("vgg_heads_l", 31), ("vgg_heads_m", 32)):
+        tag = variant[-1]
+        heads, _ = _ref_heads(ndfl, variant, seed)
+        for lv in range(3):
+            hd = getattr(heads, f"head{lv + 1}")
+            hooks = [getattr(hd, f"flame_{br}_pred").register_forward_hook(lambda m, i, o, key=f"{tag}_raw{lv}_{br}": torch.from_numpy(g[key]))
+                     for br in ("shape", "expression", "rotation", "jaw", "translation", "scale")]
+            with torch.no_grad():
+                out[f"{tag}_flame{lv}"] = hd(torch.from_numpy(g[f"{tag}_feat{lv}"]))[2].numpy()
+            for h_ in hooks:
+                h_.remove()
+    np.savez_compressed(os.path.join(OUT, "head_tail_compatible.npz"), **out)
+    print("wrote", os.path.join(OUT, "head_tail_compatible.npz"), os.path.getsize(os.path.join(OUT, "head_tail_compatible.npz")), "bytes")
+
+
 def main():
     _install_shells()
     import yolo_head.flame as rflame
@@ -208,13 +248,7 @@ def main():
     out = {}
     for variant, seed in (("vgg_heads_l", 31), ("vgg_heads_m", 32)):
         tag = variant[-1]
-        v = arch.VARIANTS[variant]
-        in_ch = (v["neck"][1][0], v["neck"][2][0], v["neck"][3][0])
-        heads = ndfl.YoloHeadsNDFLHeads(num_classes=1, in_channels=in_ch, heads_list=[_head_conf(variant, i) for i in range(3)], reg_max=16)
-        sd = {k[len("heads."):]: torch.from_numpy(a) for k, a in arch.random_state_dict(variant, seed).items() if k.startswith("heads.")}
-        missing, unexpected = heads.load_state_dict(sd, strict=False)
-        assert not unexpected and all(k.endswith("num_batches_tracked") for k in missing), (missing[:5], unexpected[:5])
-        heads.eval()
+        heads, in_ch = _ref_heads(ndfl, variant, seed)
         B, sizes = 2, ((8, 8), (4, 4), (2, 2))
         g = torch.Generator().manual_seed(seed)
         feats = [torch.randn(B, c, h, w, generator=g).relu() for c, (h, w) in zip(in_ch, sizes)]
@@ -252,4 +286,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    write_tail_compatible() if "--tail" in sys.argv else main()

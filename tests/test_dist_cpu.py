@@ -272,3 +272,36 @@ def test_bench_refuses_a_rank_count_that_differs_from_gpus(tmp_path):
     r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"), "--gpus", "2", "--steps", "1"], env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout) and "n_gpus" not in r.stdout
+
+
+def test_bench_dump_outputs_writes_the_valid_rows_within_the_budget(tmp_path):
+    """`--dump-outputs` (bench.dump_detections): the first counts[b] rows of every image, image-major, and the per-head arrays of the live
+    heads, as float32 / float64 .npy; past the byte budget a seeded, sorted sample of vertex rows together with their indices."""
+    import numpy as np
+
+    import bench
+    from head_detector_amd.engine import Detections
+
+    B, keep, V, cap = 3, 5, 7, 9
+    g = torch.Generator().manual_seed(0)
+    counts = torch.tensor([2, 0, 3], dtype=torch.int32)
+    det = Detections(torch.rand(B, keep, 4, generator=g), torch.rand(B, keep, generator=g), torch.rand(B, keep, 413, generator=g), counts,
+                     n_heads=torch.tensor([5], dtype=torch.int32), head_image_cap=torch.tensor([0, 0, 2, 2, 2, 7, 7, 7, 7], dtype=torch.int32),
+                     vertices_cap=torch.rand(cap, V, 3, generator=g), rpy_cap=torch.rand(cap, 3, generator=g))
+    bench.dump_detections(det, str(tmp_path / "all"))
+    out = {p.stem: np.load(p) for p in (tmp_path / "all").glob("*.npy")}
+    assert set(out) == {"counts", "boxes", "scores", "flame_params", "head_image", "head_pose", "vertices_3d"}
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    rows = [(0, 0), (0, 1), (2, 0), (2, 1), (2, 2)]
+    for name, t in (("boxes", det.boxes), ("scores", det.scores), ("flame_params", det.flame_params)):
+        assert np.array_equal(out[name], np.stack([t[b, k].numpy() for b, k in rows])), name
+    assert np.array_equal(out["counts"], [2, 0, 3]) and np.array_equal(out["head_image"], [0, 0, 2, 2, 2])
+    assert np.array_equal(out["vertices_3d"], det.vertices_cap[:5].numpy()) and np.array_equal(out["head_pose"], det.rpy_cap[:5].numpy())
+
+    budget = sum(a.nbytes for k, a in out.items() if k != "vertices_3d") + 8 * 5 + 2 * V * 3 * 4  # room for two vertex rows
+    bench.dump_detections(det, str(tmp_path / "cut"), budget=budget)
+    cut = {p.stem: np.load(p) for p in (tmp_path / "cut").glob("*.npy")}
+    idx = cut["vertices_3d_rows"].astype(np.int64)
+    assert len(idx) == 2 and np.all(np.diff(idx) > 0) and idx.max() < 5
+    assert np.array_equal(cut["vertices_3d"], det.vertices_cap[idx].numpy()) and sum(a.nbytes for a in cut.values()) <= budget
+    assert all(np.array_equal(cut[k], out[k]) for k in out if k != "vertices_3d")

@@ -9,7 +9,7 @@ for m in ${2:-1 2 1 2}; do
   python - $m > $O/b_$m.json 2> $O/b_$m.err <<'PY'
 import runpy, sys
 mode = int(sys.argv[1])
-sys.argv = ["bench.py", "--no-cpu-baseline", "--no-accuracy", "--no-secondary", "--traffic", "off"]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-accuracy", "--no-secondary", "--traffic", "off"]
 from head_detector_amd import _lib
 _lib.check(_lib.load().vgh_flame_set_matrix_path(mode))
 runpy.run_path("bench.py", run_name="__main__")

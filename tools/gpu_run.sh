@@ -2,7 +2,7 @@
 # One parametrised GPU-box script (replaces the per-experiment gpu_*.sh pile):
 #     tools/gpu_run.sh <out-subdir> <step> [<step> ...]        e.g.  gpurun -- 'tools/gpu_run.sh r3a tests bench prof pmc'
 # steps:  tests      pytest -m gpu (PYTEST_K='expr' to narrow)             smoke      __graft_entry__.smoke()
-#         bench      default bench line + per-layer table             prof       rocprofv3 --kernel-trace --stats of the bench command
+#         bench      bench.py --full line + per-layer table             prof       rocprofv3 --kernel-trace --stats of the bench command
 #         pmc        HBM traffic + MFMA-busy PMC passes around tools/traffic_run.py, one and two lanes (separate --pmc passes, kernel-trace only)
 #         tune       retune the L b64 / M b32 tile tables             tune1280   retune the L b16 @1280 bucket
 #         tunesplit  tile table of the fp16x3 parity mode (L b32)
@@ -29,7 +29,7 @@ for step in "$@"; do
     smoke)
       timeout 300 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; echo "smoke rc=$?" >> $O/smoke.log; tail -2 $O/smoke.log ;;
     bench)
-      timeout 1200 python bench.py --per-layer $O/per_layer_l64.json ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -5 $O/bench.err; cut -c1-900 $O/bench.json ;;
+      timeout 1200 python bench.py --full --per-layer $O/per_layer_l64.json ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; tail -5 $O/bench.err; cut -c1-900 $O/bench.json ;;
     prof)
       (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o $TAG -- python $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-accuracy --no-secondary --traffic off ${PROF_ARGS:-} > $O/prof.log 2>&1)
       f=$(find $O/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $O/${TAG}_bench_${PROF_NAME:-l64}_kernel_stats.csv && head -14 "$f" | cut -c1-220
@@ -107,7 +107,7 @@ for step in "$@"; do
       grep -v amdgpu $O/tune16.log | tail -4; cp head_detector_amd/tuning/conv_cfg.json $O/conv_cfg.json ;;
     benchm)
       # BASELINE configs[1] (VGGHeads_M b32) as the MAIN workload of bench.py: its own line, per-layer table and (PROF_ARGS / PMC_VARIANT) kernel stats / PMC passes
-      timeout 900 python bench.py --variant vgg_heads_m --batch 32 --no-secondary --no-cpu-baseline --no-accuracy --per-layer $O/${TAG}_per_layer_m32.json ${BENCH_ARGS:-} > $O/bench_m32.json 2> $O/bench_m32.err; echo "benchm rc=$?"; tail -3 $O/bench_m32.err; cut -c1-700 $O/bench_m32.json ;;
+      timeout 900 python bench.py --full --variant vgg_heads_m --batch 32 --no-secondary --no-cpu-baseline --no-accuracy --per-layer $O/${TAG}_per_layer_m32.json ${BENCH_ARGS:-} > $O/bench_m32.json 2> $O/bench_m32.err; echo "benchm rc=$?"; tail -3 $O/bench_m32.err; cut -c1-700 $O/bench_m32.json ;;
     probe)
       python tools/net_probe.py vgg_heads_l 64 2>&1 | grep -v amdgpu; python tools/net_probe.py vgg_heads_m 32 2>&1 | grep -v amdgpu ;;
     *) echo "unknown step $step" ;;
