@@ -9,11 +9,11 @@ from typing import Optional
 HERE = os.path.dirname(os.path.abspath(__file__))
 # VGH_LIB_PATH: load another build of the library (tools/ use it for the -DVGH_EXPERIMENTS build, which is never shipped)
 LIB_PATH = os.environ.get("VGH_LIB_PATH") or os.path.join(HERE, "libvgh.so")
-ABI_VERSION = 7  # = VGH_ABI_VERSION of include/vgh.h
+ABI_VERSION = 8  # = VGH_ABI_VERSION of include/vgh.h
 
 VGH_OP_STEM, VGH_OP_CONV, VGH_OP_SPP_POOL, VGH_OP_FORK = 0, 1, 2, 3
 VGH_ACT_NONE, VGH_ACT_RELU, VGH_ACT_SILU = 0, 1, 2
-VGH_IMG_F32_NCHW, VGH_IMG_U8_NHWC = 0, 1
+VGH_IMG_F32_NCHW, VGH_IMG_U8_NHWC, VGH_IMG_U8_RAW = 0, 1, 2
 VGH_FMT_BF16, VGH_FMT_F32, VGH_FMT_BF16X2, VGH_FMT_F16X2, VGH_FMT_FP8, VGH_FMT_F16, VGH_FMT_I8 = 0, 1, 2, 3, 4, 5, 6
 NUM_FLAME_PARAMS = 413
 
@@ -59,6 +59,11 @@ class ConvCall(C.Structure):
     ]
 
 
+class RawImage(C.Structure):
+    """vgh_raw_image: one source image of a VGH_IMG_U8_RAW batch (u8 [h, w, channels] on the device, rows pitch_bytes apart)."""
+    _fields_ = [("data_dev", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("channels", C.c_int32), ("pitch_bytes", C.c_int64)]
+
+
 class HeadLevel(C.Structure):
     _fields_ = [("pred_dev", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("pitch", C.c_int32), ("stride", C.c_int32)]
 
@@ -89,7 +94,7 @@ class CtxInfo(C.Structure):
                 ("precision", C.c_int32), ("flops_per_image", C.c_double)]
 
 
-SCRATCH_BOXES_ALL, SCRATCH_SCORES_ALL, SCRATCH_TOPK_IDX, SCRATCH_KEEP_IDX, SCRATCH_HEAD_ROW = range(5)
+SCRATCH_BOXES_ALL, SCRATCH_SCORES_ALL, SCRATCH_TOPK_IDX, SCRATCH_KEEP_IDX, SCRATCH_HEAD_ROW, SCRATCH_UNPAD, SCRATCH_CANVAS = range(7)
 
 # every symbol include/vgh.h declares: (restype, argtypes)
 _P, _I, _I64, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float

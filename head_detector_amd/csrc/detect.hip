@@ -37,6 +37,8 @@ struct vgh_detector {
     bool side_low = true;   // priority class of `side` (vgh_detector_set_side_priority)
     bool side_own = false;  // `side` was created for this detector alone (vgh_detector_renew_side): destroyed, not parked, on release
     hipEvent_t ev_net = nullptr, ev_cand = nullptr, ev_side = nullptr;
+    vgh_lb_batch* lb = nullptr;        // VGH_IMG_U8_RAW: canvas + letterbox staging, created by the first such call
+    const float* raw_unpad = nullptr;  // un-pad table of the last vgh_detector_candidates call if it was VGH_IMG_U8_RAW
 };
 
 namespace {
@@ -174,6 +176,7 @@ void vgh_detector_destroy(vgh_detector* d) {
     hipFree(d->head_row);
     hipFree(d->head_image);
     hipFree(d->ticket);
+    vgh_lb_destroy(d->lb);
     release_side(d);
     if (d->net) vgh_net_set_pred_guard(d->net, nullptr);
     if (d->ev_net) hipEventDestroy(d->ev_net);
@@ -185,18 +188,32 @@ void vgh_detector_destroy(vgh_detector* d) {
 int vgh_detector_candidates(vgh_detector* d, const void* images_dev, int image_fmt, int B, void* stream) {
     VGH_REQUIRE(d && images_dev, "detector_candidates: null argument");
     VGH_REQUIRE(B >= 1 && B <= d->cfg.max_batch, "detector_candidates: batch %d outside 1..%d", B, d->cfg.max_batch);
-    VGH_REQUIRE(image_fmt == VGH_IMG_F32_NCHW || image_fmt == VGH_IMG_U8_NHWC, "detector_candidates: unknown image format %d", image_fmt);
-    const size_t img_bytes = (size_t)d->S * d->S * 3 * (image_fmt == VGH_IMG_F32_NCHW ? 4 : 1);
+    VGH_REQUIRE(image_fmt == VGH_IMG_F32_NCHW || image_fmt == VGH_IMG_U8_NHWC || image_fmt == VGH_IMG_U8_RAW, "detector_candidates: unknown image format %d", image_fmt);
+    const bool raw = image_fmt == VGH_IMG_U8_RAW;  // images_dev: HOST array of B vgh_raw_image
+    if (raw)
+        if (int rc = vgh_lb_prepare(&d->lb, d->S, d->cfg.max_batch, d->arena_batch, (const vgh_raw_image*)images_dev, B)) return rc;
+    const int fmt = raw ? VGH_IMG_U8_NHWC : image_fmt;  // RAW: the network reads the letterboxed canvas
+    const size_t img_bytes = (size_t)d->S * d->S * 3 * (fmt == VGH_IMG_F32_NCHW ? 4 : 1);
     // arena-sized chunks (the conv kernels address < 2 GiB per tensor; the arena is planned for arena_batch images)
     const bool lazy = d->lazy_flame;
     if (B > d->arena_batch) d->lazy_flame = false;  // chunks: the next chunk's forward overwrites the prediction buffers a lazy select would read
     int rc = VGH_OK;
     for (int at = 0; at < B && !rc; at += d->arena_batch) {
         const int n = (B - at < d->arena_batch) ? B - at : d->arena_batch;
-        rc = vgh_net_forward(d->net, (const char*)images_dev + (size_t)at * img_bytes, image_fmt, n, stream);
+        const void* img = (const char*)images_dev + (size_t)at * img_bytes;
+        if (raw) {
+            // batched letterbox of the chunk into the detector's canvas.  The canvas is read only by this chunk's network, which is queued on
+            // `stream` right behind it (a batch split forks its lanes from `stream` and joins them back into it), and the next writer of the canvas
+            // -- the next chunk's or the next call's letterbox -- is queued on that same stream: stream order keeps the reuse race-free, in
+            // overlap mode too (the side stream's decode / select never read the canvas).
+            rc = vgh_lb_chunk(d->lb, at / d->arena_batch, n, (hipStream_t)stream);
+            img = vgh_lb_canvas(d->lb);
+        }
+        if (!rc) rc = vgh_net_forward(d->net, img, fmt, n, stream);
         if (!rc) rc = vgh_detector_decode_candidates(d, n, at, stream);
     }
     d->lazy_flame = lazy;
+    d->raw_unpad = raw ? vgh_lb_unpad(d->lb) : nullptr;
     return rc;
 }
 
@@ -254,6 +271,8 @@ void* vgh_detector_scratch(vgh_detector* d, int which) {
         case VGH_SCRATCH_TOPK_IDX: return d->idx;
         case VGH_SCRATCH_KEEP_IDX: return d->keep_idx;
         case VGH_SCRATCH_HEAD_ROW: return d->head_row;
+        case VGH_SCRATCH_UNPAD: return vgh_lb_unpad(d->lb);
+        case VGH_SCRATCH_CANVAS: return vgh_lb_canvas(d->lb);
         default: return nullptr;
     }
 }
@@ -304,8 +323,12 @@ static int select_on(vgh_detector* d, int B, float conf_thr, float iou_thr, vgh_
     }
     if (!(o->proj_dev || o->verts_dev || o->rot_dev || o->rpy_dev)) return VGH_OK;
     VGH_REQUIRE(d->flame, "detector_select: per-head FLAME outputs requested but the detector was created without a FLAME handle");
-    return vgh_flame_decode_indirect(d->flame, o->flame_dev, d->head_row, himg, o->n_heads_dev, capacity, c.shape_live, c.expr_live, o->unpad_dev, o->verts_dev,
-                                     o->rot_dev, o->rpy_dev, o->proj_dev, stream);
+    // VGH_IMG_U8_RAW: un-padded with the detector's table of that call unless the caller passes one
+    const float* unpad = o->unpad_dev ? o->unpad_dev : d->raw_unpad;
+    if ((rc = vgh_flame_decode_indirect(d->flame, o->flame_dev, d->head_row, himg, o->n_heads_dev, capacity, c.shape_live, c.expr_live, unpad, o->verts_dev,
+                                        o->rot_dev, o->rpy_dev, o->proj_dev, stream)))
+        return rc;
+    return unpad && unpad == d->raw_unpad ? vgh_lb_unpad_read(d->lb, (hipStream_t)stream) : VGH_OK;  // its staging slot is read until here
 }
 
 int vgh_detector_select(vgh_detector* d, int B, float conf_thr, float iou_thr, vgh_detect_out* o, void* stream) {

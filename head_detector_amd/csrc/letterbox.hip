@@ -8,64 +8,96 @@
 // PARITY UNPINNED against cv2 itself (absent from this image); bit-exact against oracle/letterbox_oracle.py.
 #include <hip/hip_runtime.h>
 
+#include <map>
+#include <new>
+#include <vector>
+
+#include "letterbox_tables.h"
 #include "vgh_internal.h"
 
 namespace {
 
-struct LbArgs {
-    const uint8_t* src;  // [src_h, src_w, 3+] u8, pixel stride src_cn, row stride src_pitch bytes
-    int src_h, src_w, src_cn;
-    int64_t src_pitch;
+// One source image and where its resized copy goes on the S x S canvas: kernel argument of vgh_letterbox, device-side descriptor of the
+// batched kernel (VGH_IMG_U8_RAW).
+struct LbImage {
+    const uint8_t* src;    // [src_h, src_w, src_cn >= 3] u8, row stride src_pitch bytes
     const int32_t* xofs;   // [new_w]
     const int16_t* alpha;  // [new_w][8]
     const int32_t* yofs;   // [new_h]
     const int16_t* beta;   // [new_h][8]
-    int new_w, new_h, pad_x, pad_y, S;
-    uint8_t pad[3];
-    uint8_t* dst;  // [S,S,3]
+    int64_t src_pitch;
+    int32_t src_h, src_w, src_cn, new_w, new_h, pad_x, pad_y;
+    uint32_t pad;  // border colour r | g << 8 | b << 16
 };
 
-__global__ __launch_bounds__(256) void letterbox_kernel(LbArgs a) {
-    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
-    if (x >= a.S || y >= a.S) return;
-    uint8_t* o = a.dst + ((size_t)y * a.S + x) * 3;
+// global-address-space views: pointers read from a descriptor in memory would otherwise be accessed with flat instructions
+template <typename T>
+__device__ __forceinline__ const __attribute__((address_space(1))) T* gmem(const T* p) {
+    return (const __attribute__((address_space(1))) T*)p;
+}
+
+// Canvas pixel (x, y) as r | g << 8 | b << 16: the per-pixel arithmetic of BOTH letterbox kernels (they cannot drift apart).
+__device__ __forceinline__ uint32_t letterbox_pixel(const LbImage& a, int x, int y) {
     const int dx = x - a.pad_x, dy = y - a.pad_y;
-    if ((unsigned)dx >= (unsigned)a.new_w || (unsigned)dy >= (unsigned)a.new_h) {
-        o[0] = a.pad[0];
-        o[1] = a.pad[1];
-        o[2] = a.pad[2];
-        return;
-    }
-    const int sx = a.xofs[dx] - 3, sy = a.yofs[dy] - 3;
+    if ((unsigned)dx >= (unsigned)a.new_w || (unsigned)dy >= (unsigned)a.new_h) return a.pad;
+    const int sx = gmem(a.xofs)[dx] - 3, sy = gmem(a.yofs)[dy] - 3;
     int al[8], cx[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        al[k] = a.alpha[dx * 8 + k];
+        al[k] = gmem(a.alpha)[dx * 8 + k];
         cx[k] = min(max(sx + k, 0), a.src_w - 1) * a.src_cn;
     }
     unsigned acc[3] = {0u, 0u, 0u};  // unsigned: C's int accumulation with defined wrap-around
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int ry = min(max(sy + j, 0), a.src_h - 1);
-        const uint8_t* row = a.src + (size_t)ry * a.src_pitch;
+        const auto row = gmem(a.src) + (size_t)ry * a.src_pitch;
         unsigned h0 = 0u, h1 = 0u, h2 = 0u;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const uint8_t* p = row + cx[k];
+            const auto p = row + cx[k];
             h0 += (unsigned)((int)p[0] * al[k]);
             h1 += (unsigned)((int)p[1] * al[k]);
             h2 += (unsigned)((int)p[2] * al[k]);
         }
-        const int b = a.beta[dy * 8 + j];
+        const int b = gmem(a.beta)[dy * 8 + j];
         acc[0] += (unsigned)((int)h0 * b);
         acc[1] += (unsigned)((int)h1 * b);
         acc[2] += (unsigned)((int)h2 * b);
     }
+    // each channel clamped into a byte of its own, then packed: written as one shift / clamp / or chain, hipcc (ROCm 7.0) lowers two channels
+    // to v_ashr_pk_u8_i32 on gfx950, and the device then returned wrong red / blue bytes (measured against oracle/letterbox_oracle.py)
+    uint8_t o[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const int v = ((int)acc[c] + (1 << 21)) >> 22;  // FixedPtCast<int, uchar, 22>
         o[c] = (uint8_t)min(max(v, 0), 255);
     }
+    return (uint32_t)o[0] | (uint32_t)o[1] << 8 | (uint32_t)o[2] << 16;
+}
+
+__global__ __launch_bounds__(256) void letterbox_kernel(LbImage a, uint8_t* dst, int S) {
+    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    if (x >= S || y >= S) return;
+    uint8_t* o = dst + ((size_t)y * S + x) * 3;
+    const uint32_t rgb = letterbox_pixel(a, x, y);
+    o[0] = (uint8_t)rgb;
+    o[1] = (uint8_t)(rgb >> 8);
+    o[2] = (uint8_t)(rgb >> 16);
+}
+
+// VGH_IMG_U8_RAW: every image of an arena chunk in one launch, canvas [n, S, S, 3].  blockIdx.z = image (its descriptor is wave-uniform:
+// scalar loads); one pixel per lane as in letterbox_kernel.  The kernel is bound by the 128 byte gathers per pixel, not by its stores: four
+// pixels per lane with one 3-dword store measured 1.70 ms per 64 mixed photographs against 1.16 ms for this form (profiles/raw_letterbox_l64.txt).
+__global__ __launch_bounds__(256) void letterbox_batch_kernel(const LbImage* __restrict__ imgs, uint8_t* __restrict__ canvas, int S) {
+    const LbImage& a = imgs[blockIdx.z];
+    const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
+    if (x >= S || y >= S) return;
+    uint8_t* o = canvas + (((size_t)blockIdx.z * S + y) * S + x) * 3;
+    const uint32_t rgb = letterbox_pixel(a, x, y);
+    o[0] = (uint8_t)rgb;
+    o[1] = (uint8_t)(rgb >> 8);
+    o[2] = (uint8_t)(rgb >> 16);
 }
 
 }  // namespace
@@ -76,7 +108,7 @@ extern "C" int vgh_letterbox(const uint8_t* src_dev, int src_h, int src_w, int s
     VGH_REQUIRE(src_dev && xofs_dev && alpha_dev && yofs_dev && beta_dev && dst_dev && pad_rgb, "letterbox: null argument");
     VGH_REQUIRE(src_h > 0 && src_w > 0 && src_channels >= 3 && src_pitch_bytes >= (int64_t)src_w * src_channels, "letterbox: bad source geometry");
     VGH_REQUIRE(new_w > 0 && new_h > 0 && pad_x >= 0 && pad_y >= 0 && pad_x + new_w <= S && pad_y + new_h <= S, "letterbox: the resized image does not fit the %dx%d canvas", S, S);
-    LbArgs a;
+    LbImage a;
     a.src = src_dev;
     a.src_h = src_h;
     a.src_w = src_w;
@@ -90,12 +122,168 @@ extern "C" int vgh_letterbox(const uint8_t* src_dev, int src_h, int src_w, int s
     a.new_h = new_h;
     a.pad_x = pad_x;
     a.pad_y = pad_y;
-    a.S = S;
-    a.pad[0] = pad_rgb[0];
-    a.pad[1] = pad_rgb[1];
-    a.pad[2] = pad_rgb[2];
-    a.dst = dst_dev;
-    hipLaunchKernelGGL(letterbox_kernel, dim3((S + 31) / 32, (S + 7) / 8), dim3(256), 0, (hipStream_t)stream, a);
+    a.pad = pad_rgb[0] | (uint32_t)pad_rgb[1] << 8 | (uint32_t)pad_rgb[2] << 16;
+    hipLaunchKernelGGL(letterbox_kernel, dim3((S + 31) / 32, (S + 7) / 8), dim3(256), 0, (hipStream_t)stream, a, dst_dev, S);
     VGH_HIP(hipGetLastError());
     return VGH_OK;
+}
+
+// ---- VGH_IMG_U8_RAW: the detector's batched letterbox (include/vgh.h, vgh_detect) ----------------------------------------------------------
+// The host validates the B descriptors, builds (or finds in its cache) the per-axis tables and packs, for every arena chunk, the chunk's
+// LbImage descriptors and tables into a pinned staging slot: ONE async copy and ONE letterbox_batch_kernel launch per chunk.  The first slot
+// region also holds the un-pad table [max_batch, 3] of the whole call, so it travels with the first chunk's copy.
+//
+// Two slots, alternating per call.  A slot is free again once its last device reader has run: the letterbox launches of its call (on the
+// detector's stream) and, when the select un-pads the FLAME outputs with its table, that select (on the overlap-mode side stream, possibly
+// later).  ev[k] is recorded behind each of them (the latest record wins) and the host waits for it before it rewrites slot k -- two calls
+// later, so a pipelined caller is normally not held up.  The canvas needs no such guard: see vgh_detector_candidates.
+struct vgh_lb_batch {
+    int S = 0, max_batch = 0, arena_batch = 0;
+    uint8_t* canvas = nullptr;  // [arena_batch, S, S, 3]
+    size_t slot_bytes = 0;
+    uint8_t* host[2] = {nullptr, nullptr};  // pinned
+    uint8_t* dev[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool recorded[2] = {false, false};
+    int slot = 1;                  // slot of the last prepared call
+    std::vector<size_t> chunk_at;  // [chunks + 1] byte offsets of the chunk regions in the slot
+    std::map<std::pair<int, int>, vgh_lb::AxisTables> cache;  // (src, dst) length -> tables, like letterbox.py's lru_cache
+};
+
+namespace {
+
+size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+const vgh_lb::AxisTables& cached_tables(vgh_lb_batch* lb, int src, int dst) {
+    auto it = lb->cache.find({src, dst});
+    if (it != lb->cache.end()) return it->second;
+    if (lb->cache.size() >= 256) lb->cache.clear();  // bounded: a stream of ever-new sizes does not grow it without limit
+    return lb->cache.emplace(std::make_pair(src, dst), vgh_lb::axis_tables(src, dst)).first->second;
+}
+
+void lb_free(vgh_lb_batch* lb) {
+    hipFree(lb->canvas);
+    for (int k = 0; k < 2; ++k) {
+        hipHostFree(lb->host[k]);
+        hipFree(lb->dev[k]);
+        if (lb->ev[k]) hipEventDestroy(lb->ev[k]);
+    }
+    delete lb;
+}
+
+int lb_create(int S, int max_batch, int arena_batch, vgh_lb_batch** out) {
+    vgh_lb_batch* lb = new (std::nothrow) vgh_lb_batch();
+    VGH_REQUIRE(lb, "detector_candidates: out of host memory");
+    lb->S = S;
+    lb->max_batch = max_batch;
+    lb->arena_batch = arena_batch;
+    // per image at most sizeof(LbImage) + 16 bytes of descriptor region and two axes of <= S entries (4 + 16 bytes, 16-byte aligned)
+    lb->slot_bytes = align16((size_t)max_batch * 12) + (size_t)max_batch * (sizeof(LbImage) + 16 + 2 * (align16((size_t)4 * S) + (size_t)16 * S));
+    const size_t canvas_bytes = (size_t)arena_batch * S * S * 3;
+    bool ok = hipMalloc((void**)&lb->canvas, canvas_bytes) == hipSuccess;
+    for (int k = 0; k < 2 && ok; ++k)
+        ok = hipHostMalloc((void**)&lb->host[k], lb->slot_bytes, hipHostMallocDefault) == hipSuccess && hipMalloc((void**)&lb->dev[k], lb->slot_bytes) == hipSuccess &&
+             hipEventCreateWithFlags(&lb->ev[k], hipEventDisableTiming) == hipSuccess;
+    if (!ok) {
+        lb_free(lb);
+        vgh_set_error("detector_candidates: allocating the letterbox canvas (%zu bytes) and staging (2 x %zu bytes) failed", canvas_bytes, lb->slot_bytes);
+        return VGH_ERR_NOMEM;
+    }
+    *out = lb;
+    return VGH_OK;
+}
+
+}  // namespace
+
+int vgh_lb_prepare(vgh_lb_batch** plb, int S, int max_batch, int arena_batch, const vgh_raw_image* imgs, int B) {
+    std::vector<vgh_lb::Geometry> geo(B);
+    for (int i = 0; i < B; ++i) {  // everything is checked before anything is allocated, written or queued
+        const vgh_raw_image& im = imgs[i];
+        VGH_REQUIRE(im.data_dev, "detector_candidates: image %d: null data_dev", i);
+        VGH_REQUIRE(im.h >= 1 && im.w >= 1, "detector_candidates: image %d: empty (%d x %d)", i, im.h, im.w);
+        VGH_REQUIRE(im.channels >= 3, "detector_candidates: image %d: %d channels (needs >= 3, the first three RGB)", i, im.channels);
+        VGH_REQUIRE(im.pitch_bytes >= (int64_t)im.w * im.channels, "detector_candidates: image %d: pitch_bytes %lld < w * channels = %lld", i, (long long)im.pitch_bytes,
+                    (long long)im.w * im.channels);
+        geo[i] = vgh_lb::geometry(im.h, im.w, S);
+        VGH_REQUIRE(geo[i].new_w >= 1 && geo[i].new_h >= 1, "detector_candidates: image %d (%d x %d) is too elongated for a %dx%d letterbox", i, im.h, im.w, S, S);
+    }
+    if (!*plb)
+        if (int rc = lb_create(S, max_batch, arena_batch, plb)) return rc;
+    vgh_lb_batch* lb = *plb;
+    const int k = lb->slot ^ 1;
+    if (lb->recorded[k]) VGH_HIP(hipEventSynchronize(lb->ev[k]));  // its last call's copies / letterbox / select have run
+    uint8_t* h = lb->host[k];
+    float* unpad = (float*)h;
+    for (int i = 0; i < B; ++i) {
+        unpad[3 * i] = (float)geo[i].pad_x;
+        unpad[3 * i + 1] = (float)geo[i].pad_y;
+        unpad[3 * i + 2] = (float)geo[i].scale;
+    }
+    size_t at = align16((size_t)lb->max_batch * 12);
+    lb->chunk_at.clear();
+    for (int c0 = 0; c0 < B; c0 += arena_batch) {
+        const int n = B - c0 < arena_batch ? B - c0 : arena_batch;
+        lb->chunk_at.push_back(at);
+        LbImage* desc = (LbImage*)(h + at);
+        at = align16(at + (size_t)n * sizeof(LbImage));
+        for (int i = 0; i < n; ++i) {
+            const vgh_raw_image& im = imgs[c0 + i];
+            const vgh_lb::Geometry& g = geo[c0 + i];
+            LbImage& a = desc[i];
+            a.src = im.data_dev;
+            a.src_pitch = im.pitch_bytes;
+            a.src_h = im.h;
+            a.src_w = im.w;
+            a.src_cn = im.channels;
+            a.new_w = g.new_w;
+            a.new_h = g.new_h;
+            a.pad_x = g.pad_x;
+            a.pad_y = g.pad_y;
+            a.pad = 127u;  // letterbox.py PAD_VALUE = (127, 0, 0): cv2.copyMakeBorder(..., value=127) on an RGB image
+            const int32_t** ofs[2] = {&a.xofs, &a.yofs};
+            const int16_t** coef[2] = {&a.alpha, &a.beta};
+            const int src_len[2] = {im.w, im.h}, dst_len[2] = {g.new_w, g.new_h};
+            for (int ax = 0; ax < 2; ++ax) {
+                const vgh_lb::AxisTables& t = cached_tables(lb, src_len[ax], dst_len[ax]);
+                const size_t ob = (size_t)dst_len[ax] * 4, cb = (size_t)dst_len[ax] * 16;
+                VGH_REQUIRE(align16(at + ob) + cb <= lb->slot_bytes, "detector_candidates: letterbox staging overflow (internal)");
+                memcpy(h + at, t.ofs.data(), ob);
+                *ofs[ax] = (const int32_t*)(lb->dev[k] + at);
+                at = align16(at + ob);
+                memcpy(h + at, t.coef.data(), cb);
+                *coef[ax] = (const int16_t*)(lb->dev[k] + at);
+                at = align16(at + cb);
+            }
+        }
+    }
+    lb->chunk_at.push_back(at);
+    lb->slot = k;
+    return VGH_OK;
+}
+
+int vgh_lb_chunk(vgh_lb_batch* lb, int chunk, int n, hipStream_t stream) {
+    VGH_REQUIRE(lb && chunk >= 0 && chunk + 1 < (int)lb->chunk_at.size() && n >= 1 && n <= lb->arena_batch, "letterbox: chunk %d outside the prepared batch", chunk);
+    const int k = lb->slot;
+    const size_t from = chunk == 0 ? 0 : lb->chunk_at[chunk], to = lb->chunk_at[chunk + 1];  // chunk 0 carries the un-pad table in front
+    VGH_HIP(hipMemcpyAsync(lb->dev[k] + from, lb->host[k] + from, to - from, hipMemcpyHostToDevice, stream));
+    const int S = lb->S;
+    hipLaunchKernelGGL(letterbox_batch_kernel, dim3((S + 31) / 32, (S + 7) / 8, n), dim3(256), 0, stream,
+                       (const LbImage*)(lb->dev[k] + lb->chunk_at[chunk]), lb->canvas, S);
+    VGH_HIP(hipGetLastError());
+    VGH_HIP(hipEventRecord(lb->ev[k], stream));
+    lb->recorded[k] = true;
+    return VGH_OK;
+}
+
+int vgh_lb_unpad_read(vgh_lb_batch* lb, hipStream_t stream) {
+    VGH_HIP(hipEventRecord(lb->ev[lb->slot], stream));
+    lb->recorded[lb->slot] = true;
+    return VGH_OK;
+}
+
+uint8_t* vgh_lb_canvas(const vgh_lb_batch* lb) { return lb ? lb->canvas : nullptr; }
+float* vgh_lb_unpad(const vgh_lb_batch* lb) { return lb ? (float*)lb->dev[lb->slot] : nullptr; }
+
+void vgh_lb_destroy(vgh_lb_batch* lb) {
+    if (lb) lb_free(lb);
 }

@@ -221,3 +221,14 @@ int vgh_net_lane_streams(vgh_net* n, hipStream_t main, hipStream_t* out);
 extern "C" __attribute__((visibility("hidden"))) int vgh_net_device(vgh_net* n);  // library-internal
 // net.hip, library-internal since r06 (was exported): the first op of the next forwards that writes a prediction buffer waits for `event` (or nullptr) on its stream
 extern "C" __attribute__((visibility("hidden"))) int vgh_net_set_pred_guard(vgh_net* n, void* event);
+
+// letterbox.hip: the batched letterbox of VGH_IMG_U8_RAW, owned by a detector (canvas [arena_batch, S, S, 3] + two pinned / device staging slots)
+struct vgh_lb_batch;
+// Validates the B descriptors (VGH_ERR_INVALID naming the image; nothing allocated or queued) and packs their tables + the un-pad table into the
+// next staging slot; *lb (NULL before the first RAW call) is created here.
+int vgh_lb_prepare(vgh_lb_batch** lb, int S, int max_batch, int arena_batch, const vgh_raw_image* imgs, int B);
+int vgh_lb_chunk(vgh_lb_batch* lb, int chunk, int n, hipStream_t stream);  // chunk's upload + ONE launch -> canvas rows [0, n)
+int vgh_lb_unpad_read(vgh_lb_batch* lb, hipStream_t stream);            // a select on `stream` read the un-pad table of the last call
+uint8_t* vgh_lb_canvas(const vgh_lb_batch* lb);
+float* vgh_lb_unpad(const vgh_lb_batch* lb);  // [max_batch, 3] of the last prepared call
+void vgh_lb_destroy(vgh_lb_batch* lb);

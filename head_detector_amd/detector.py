@@ -258,18 +258,23 @@ class HeadDetector:
         return self._parse_predictions(boxes, scores, flame_params, cache)
 
     def detect_batch(self, images: Sequence[Union[str, "np.ndarray", Any]], confidence_threshold: float = 0.5) -> List[PredictionResult]:
-        """Batched twin of ``__call__`` (what yolo_heads_post_prediction_callback.py:41-99 does for a batch): every image goes
-        through ONE fused device call (vgh_detect: net -> top-k -> NMS per image -> FLAME decode + un-pad + head pose of every
-        survivor); only the final per-head Python objects are built on the host.  Needs ``max_batch >= len(images)``."""
+        """Batched twin of ``__call__`` (what yolo_heads_post_prediction_callback.py:41-99 does for a batch): the images, of any sizes, go through
+        ONE fused device call (vgh_detect with VGH_IMG_U8_RAW: batched letterbox -> net -> top-k -> NMS per image -> FLAME decode + un-pad + head
+        pose of every survivor); only the final per-head Python objects are built on the host.  Needs ``max_batch >= len(images)``."""
         if len(images) > self._max_batch:
             raise ValueError(f"detect_batch: {len(images)} images exceed max_batch={self._max_batch} (pass max_batch= to HeadDetector)")
+        from .letterbox import geometry
+
         originals = [self._convert_image(im) for im in images]
         if not originals:
             return []
-        tensors, caches = zip(*[self._preprocess(im) for im in originals])
-        batch = torch.cat(tensors, 0).contiguous()
-        unpad = torch.tensor([[c["padding"][0], c["padding"][1], c["scale"]] for c in caches], dtype=torch.float32, device=self._device)
-        det = self.model.detect(batch, confidence_threshold=confidence_threshold, flame=self._flame, unpad=unpad)
+        raw = []
+        for im in originals:
+            src = torch.from_numpy(np.ascontiguousarray(im))
+            if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] < 3:
+                raise ValueError(f"detect_batch expects uint8 images [H,W,3]; got {src.dtype} {tuple(src.shape)}")
+            raw.append(src.to(self._device, non_blocking=True))
+        det = self.model.detect(raw, confidence_threshold=confidence_threshold, flame=self._flame)  # FLAME outputs un-padded on the device
         counts = det.counts.cpu().numpy()
         n = det.num_heads
         verts = det.vertices_3d.cpu().numpy()
@@ -277,15 +282,15 @@ class HeadDetector:
         boxes, scores, params = det.boxes.cpu().numpy(), det.scores.cpu().numpy(), det.flame_params.cpu()
         results, at = [], 0
         S = self._image_size
-        for b, (orig, cache) in enumerate(zip(originals, caches)):
-            padding, scale = cache["padding"], cache["scale"]
+        for b, orig in enumerate(originals):
+            _, _, pad_x, pad_y, scale = geometry(orig.shape[0], orig.shape[1], S)
             heads = []
             for i in range(int(counts[b])):
                 if at >= n:
                     break  # head capacity exhausted (never with the default capacities)
                 bb = boxes[b, i].clip(0, S)
-                bb[[0, 2]] -= padding[0]
-                bb[[1, 3]] -= padding[1]
+                bb[[0, 2]] -= pad_x
+                bb[[1, 3]] -= pad_y
                 bb = np.rint(bb / scale).astype(int)
                 fp = FlameParams.from_3dmm(params[b, i].unsqueeze(0))
                 fp.scale = fp.scale / scale

@@ -241,6 +241,38 @@ class VGHeadsEngine:
             raise ValueError(f"batch {B} exceeds max_batch {self.max_batch}")
         return B, fmt
 
+    def _images_arg(self, images) -> Tuple[int, int, int]:
+        """(B, image format, pointer for vgh_detector_candidates): a canvas batch (``_check_images``), or a list of GPU uint8 tensors [h, w, C >= 3] of any size
+        (VGH_IMG_U8_RAW, letterboxed on the device; rows may be padded: strides (pitch, C, 1)) -> a host array of vgh_raw_image kept alive on the engine."""
+        if isinstance(images, torch.Tensor):
+            B, fmt = self._check_images(images)
+            return B, fmt, images.data_ptr()
+        B = len(images)
+        if not 1 <= B <= self.max_batch:
+            raise ValueError(f"raw image batch of {B} outside 1..max_batch={self.max_batch}")
+        arr = (_lib.RawImage * B)()
+        for i, t in enumerate(images):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] < 3 or t.device != self.device:
+                raise ValueError(f"raw image {i}: expected a uint8 tensor [h, w, C >= 3] on {self.device}; got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+            if t.stride(2) != 1 or t.stride(1) != t.shape[2]:
+                raise ValueError(f"raw image {i}: the pixels of a row must be dense (strides (pitch, C, 1)); got {t.stride()}")
+            arr[i] = _lib.RawImage(t.data_ptr(), t.shape[0], t.shape[1], t.shape[2], t.stride(0))
+            t.record_stream(self.stream)  # read asynchronously by the letterbox on the engine stream
+        self._raw_arg = arr  # alive until the library has read it (during the vgh_detector_candidates call that follows)
+        return B, _lib.VGH_IMG_U8_RAW, C.addressof(arr)
+
+    def raw_unpad(self) -> Optional[torch.Tensor]:
+        """[max_batch, 3] (pad_x, pad_y, scale) per image of the last raw-image call (VGH_SCRATCH_UNPAD: what un-pads its boxes, (x - pad_x) / scale); None before the
+        first one.  A view of library memory that the raw-image calls after the next one overwrite."""
+        p = self.lib.vgh_detector_scratch(self._det, _lib.SCRATCH_UNPAD)
+        return None if not p else _alias(p, (self.max_batch, 3), "<f4", self.device)
+
+    def raw_canvas(self) -> Optional[torch.Tensor]:
+        """u8 [arena_batch, S, S, 3]: the letterboxed canvas of the last arena chunk of the last raw-image call (VGH_SCRATCH_CANVAS); None before the first one."""
+        p = self.lib.vgh_detector_scratch(self._det, _lib.SCRATCH_CANVAS)
+        S = self.image_size
+        return None if not p else _alias(p, (self.arena_batch, S, S, 3), "|u1", self.device)
+
     def forward_net(self, images: torch.Tensor, use_graph: bool = False) -> int:
         """Backbone + neck + heads for one arena-sized batch: leaves the fp32 prediction buffers inside the arena. Returns B."""
         B, fmt = self._check_images(images)
@@ -351,15 +383,15 @@ class VGHeadsEngine:
 
     def forward_candidates(self, images: torch.Tensor, use_graph: bool = False, lazy_flame: bool = False) -> int:
         """Network + candidate stages for a batch of any size <= max_batch (arena-sized chunks): one vgh_detector_candidates call.  ``lazy_flame``: see ``candidates``
-        (a batch that runs in several arena chunks gathers eagerly whatever the flag says)."""
-        B, fmt = self._check_images(images)
-        if use_graph and B <= self.arena_batch:
+        (a batch that runs in several arena chunks gathers eagerly whatever the flag says).  ``images`` may be a list of raw images (see ``detect``)."""
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        B, fmt, ptr = self._images_arg(images)
+        if use_graph and B <= self.arena_batch and fmt != _lib.VGH_IMG_U8_RAW:
             self.forward_net(images, True)
             self.candidates(B, lazy_flame=lazy_flame)
             return B
         self._set_lazy_flame(lazy_flame)
-        self.stream.wait_stream(torch.cuda.current_stream(self.device))
-        _lib.check(self.lib.vgh_detector_candidates(self._det, images.data_ptr(), fmt, B, self._sp()))
+        _lib.check(self.lib.vgh_detector_candidates(self._det, ptr, fmt, B, self._sp()))
         return B
 
     def _join_if_overlap(self):
@@ -425,19 +457,22 @@ class VGHeadsEngine:
             det.n_heads, det.head_image_cap, det.vertices_cap, det.rpy_cap = nh, himg, proj, rpy
         return o, det
 
-    def detect(self, images: torch.Tensor, confidence_threshold: float = 0.5, iou_threshold: float = 0.5, flame: Optional[FLAMELayer] = None,
+    def detect(self, images, confidence_threshold: float = 0.5, iou_threshold: float = 0.5, flame: Optional[FLAMELayer] = None,
                unpad: Optional[torch.Tensor] = None, use_graph: bool = False, reuse_outputs: bool = False) -> Detections:
         """net -> top-k -> NMS (every image) -> optional FLAME decode + head pose of every surviving head: ONE asynchronous
         library call (vgh_detect); the data-dependent head count stays on the device (see ``Detections``).
+        ``images``: a letterboxed canvas batch (f32 [B,3,S,S] / u8 [B,S,S,3]), or a LIST of GPU uint8 tensors [h, w, C >= 3] of any size (VGH_IMG_U8_RAW:
+        letterboxed on the device as detector.py:40-52 does; the boxes stay in the padded S-space, the FLAME outputs are un-padded with the letterbox
+        geometry -- ``raw_unpad()`` -- unless ``unpad`` is given).
         ``unpad`` [B,3] = (pad_x, pad_y, scale) per image fuses detector.py:67-69.  The result is written into fresh tensors the
         caller owns; ``reuse_outputs=True`` writes into the engine's own output buffers (no allocation, see ``Detections``)."""
-        B, fmt = self._check_images(images)
         cur = torch.cuda.current_stream(self.device)
         # The result tensors are allocated (and zero-filled) on the engine stream, whose pool the caching allocator returns them to when the
         # caller drops them.  Two orderings make that safe: the engine stream first waits for the caller's stream (a block freed by the caller
         # may still be read by kernels the caller queued earlier), and the tensors are recorded on the caller's stream before they are handed
         # out (the allocator then keeps a dropped block until the caller's reads of it have finished).
         self.stream.wait_stream(cur)
+        B, fmt, ptr = self._images_arg(images)
         # r06: the network goes to the GPU FIRST; the result tensors are allocated, zero-filled and marshalled while it runs (vgh_detect IS vgh_detector_candidates +
         # vgh_detector_select, csrc/detect.hip).  The other order left the GPU idle for the ~75 us of host work in front of a single-image call's first kernel
         # (profiles/r06_latency_trace_l1.txt: 76 us between the fill kernel and the stem).
@@ -449,11 +484,11 @@ class VGHeadsEngine:
             with torch.cuda.stream(self.stream):
                 slot = self.new_output_slot(flame, B)
         # (r06) lazy FLAME gather: detect() queues the select right behind the candidates, so the survivors' vectors come straight from the prediction buffers
-        if use_graph and B <= self.arena_batch:
+        if use_graph and B <= self.arena_batch and fmt != _lib.VGH_IMG_U8_RAW:
             self.forward_candidates(images, True, lazy_flame=True)
         else:
             self._set_lazy_flame(True)
-            _lib.check(self.lib.vgh_detector_candidates(self._det, images.data_ptr(), fmt, B, self._sp()))
+            _lib.check(self.lib.vgh_detector_candidates(self._det, ptr, fmt, B, self._sp()))
         if net_first and not reuse_outputs:
             with torch.cuda.stream(self.stream):
                 slot = self.new_output_slot(flame, B)

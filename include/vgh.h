@@ -30,6 +30,16 @@ extern "C" {
 
 #define VGH_IMG_F32_NCHW 0 /* what HeadDetector._transform_image hands the model (detector.py:51) */
 #define VGH_IMG_U8_NHWC 1  /* raw letterboxed image before .permute().float()/255 (detector.py:48-51) */
+#define VGH_IMG_U8_RAW 2   /* images of any size, letterboxed on the device (detector.py:40-52): `images_dev` is a HOST array of B vgh_raw_image */
+                           /*   (vgh_detector_candidates / vgh_detect / vgh_ctx_detect only: the net entry points take a canvas and reject it) */
+
+/* One source image of a VGH_IMG_U8_RAW batch.  The descriptor is read on the host during the call; the pixels are read on the device
+ * by work queued on the call's stream, so they must stay valid until that work has run. */
+typedef struct vgh_raw_image {
+    const uint8_t* data_dev; /* u8 [h, w, channels] on the device, channels >= 3 (the first three = RGB), rows pitch_bytes apart */
+    int32_t h, w, channels;
+    int64_t pitch_bytes;     /* >= w * channels */
+} vgh_raw_image;
 
 #define VGH_NUM_FLAME_PARAMS 413 /* FLAME_CONSTS, head_detector/head_info.py:12-21 */
 
@@ -39,9 +49,10 @@ const char* vgh_last_error(void);
 /* ABI revision of this header: bumped whenever a struct below grows or a function changes meaning (r03 -> 3: vgh_conv_call / vgh_op_desc gained
  * grp_cout, grp_in_stride, fmt, out_scale and vgh_flame_set_matrix_path became a 0..4 mode; r04 -> 4: this call; -> 5: modes 0..7 of
  * vgh_flame_set_matrix_path; r05 -> 6: VGH_FMT_FP8, vgh_buf_desc.scale, vgh_conv_call.out_fp8 / gscale_dev, vgh_pack_conv_weights_fp8;
- * -> 7: VGH_FMT_I8, vgh_conv_call.out_fp8 = 2 / diag_dev, vgh_pack_conv_weights_i8, vgh_net_set_i8_diag).  A client built against another
- * revision passes structs of another size: compare before the first call that takes one (head_detector_amd/_lib.py and tests/c_abi_smoke.c do). */
-#define VGH_ABI_VERSION 7
+ * -> 7: VGH_FMT_I8, vgh_conv_call.out_fp8 = 2 / diag_dev, vgh_pack_conv_weights_i8, vgh_net_set_i8_diag; -> 8: VGH_IMG_U8_RAW / vgh_raw_image, the
+ * detector's VGH_SCRATCH_UNPAD / VGH_SCRATCH_CANVAS).  A client built against another revision passes structs of another size: compare before the
+ * first call that takes one (head_detector_amd/_lib.py and tests/c_abi_smoke.c do). */
+#define VGH_ABI_VERSION 8
 int vgh_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -102,7 +113,8 @@ typedef struct vgh_net vgh_net;
 int vgh_net_create(int device, int image_size, int max_batch, const vgh_buf_desc* bufs, int n_bufs, const vgh_op_desc* ops, int n_ops,
                    const float* weights_host, int64_t n_weights, const float* biases_host, int64_t n_biases, vgh_net** out);
 void vgh_net_destroy(vgh_net* net);
-/* image_dev: [B,3,S,S] f32 (VGH_IMG_F32_NCHW) or [B,S,S,3] u8 (VGH_IMG_U8_NHWC). Runs every op. */
+/* image_dev: [B,3,S,S] f32 (VGH_IMG_F32_NCHW) or [B,S,S,3] u8 (VGH_IMG_U8_NHWC). Runs every op.  (VGH_IMG_U8_RAW is rejected here and by
+ * vgh_net_profile / vgh_net_capture: a network needs a canvas.) */
 int vgh_net_forward(vgh_net* net, const void* image_dev, int image_fmt, int B, void* stream);
 /* As vgh_net_forward but host-synchronous, bracketing every op with HIP events on `stream`;
  * op_ms[n_ops] receives each op's device time in milliseconds (tuning / roofline reporting). */
@@ -316,8 +328,15 @@ int vgh_flame_set_matrix_path(int mode);
  *       caller's fixed-capacity slabs + the image-major head list + reproject_spatial_vertices / un-pad / calculate_rpy of
  *       every survivor (detector.py:66-69,87)
  *   vgh_detect              = both.
- * Nothing is allocated after vgh_detector_create; all outputs are caller-owned device memory; every call is asynchronous
- * on `stream`; a detector (like the net and FLAME handles it borrows) serves one stream at a time.
+ * Nothing is allocated after vgh_detector_create -- except, once, by the first VGH_IMG_U8_RAW call: the u8 canvas [arena_batch,S,S,3] and two
+ * pinned + device staging slots of letterbox tables -- all outputs are caller-owned device memory; every call is asynchronous on `stream`; a
+ * detector (like the net and FLAME handles it borrows) serves one stream at a time.
+ * VGH_IMG_U8_RAW (images of any size): per arena chunk ONE async upload of the chunk's LANCZOS4 tables + descriptors, ONE batched letterbox
+ * launch into the detector's canvas (the vgh_letterbox arithmetic, bit-identical to it), then the network on the canvas as VGH_IMG_U8_NHWC.
+ * The detections stay in the padded S-space (boxes_dev); with out->unpad_dev == NULL the FLAME outputs are un-padded with the detector's
+ * table of this call (VGH_SCRATCH_UNPAD); a non-NULL unpad_dev wins.  Invalid descriptors (NULL data, channels < 3, pitch < w * channels, an
+ * image too elongated for the S x S letterbox) fail with VGH_ERR_INVALID naming the image, before anything is queued.  The host blocks only
+ * when it reuses a staging slot whose previous call (two RAW calls back) has not finished its letterbox / select yet.
  * ---------------------------------------------------------------------------------------------- */
 #define VGH_MAX_LEVELS 4
 typedef struct vgh_detect_cfg {
@@ -357,12 +376,16 @@ int vgh_detector_decode_candidates(vgh_detector* d, int n, int at, void* stream)
 int vgh_detector_candidate_buffers(vgh_detector* d, float** boxes_dev, float** scores_dev, float** flame_dev);
 int vgh_detector_set_flame(vgh_detector* d, vgh_flame* flame);
 /* detector-owned intermediates (parity tests / debugging): dense boxes [max_batch,A,4], dense scores [max_batch,A],
- * top-k anchor indices [max_batch,pre_k] i32, NMS keep positions [max_batch,keep_k] i32, head rows [max_batch*keep_k] i32 */
+ * top-k anchor indices [max_batch,pre_k] i32, NMS keep positions [max_batch,keep_k] i32, head rows [max_batch*keep_k] i32;
+ * of the last VGH_IMG_U8_RAW call (NULL before the first one): the un-pad table [max_batch,3] f32 (pad_x, pad_y, scale) per image
+ * (detector.py:67-69; what un-pads boxes_dev: (x - pad_x) / scale), and the u8 canvas [arena_batch,S,S,3] holding its last arena chunk */
 #define VGH_SCRATCH_BOXES_ALL 0
 #define VGH_SCRATCH_SCORES_ALL 1
 #define VGH_SCRATCH_TOPK_IDX 2
 #define VGH_SCRATCH_KEEP_IDX 3
 #define VGH_SCRATCH_HEAD_ROW 4
+#define VGH_SCRATCH_UNPAD 5
+#define VGH_SCRATCH_CANVAS 6
 void* vgh_detector_scratch(vgh_detector* d, int which);
 int vgh_detector_select(vgh_detector* d, int B, float conf_thr, float iou_thr, vgh_detect_out* out, void* stream);
 int vgh_detect(vgh_detector* d, const void* images_dev, int image_fmt, int B, float conf_thr, float iou_thr, vgh_detect_out* out, void* stream);
@@ -450,6 +473,8 @@ int vgh_refined_head_bbox(const float* verts_dev, int n_heads, int V, const int3
  * vgh_net_forward(VGH_IMG_U8_NHWC) consumes.  The caller supplies the per-axis tables exactly as resize.cpp builds them
  * (head_detector_amd/letterbox.py: xofs/yofs = floor source coordinate, alpha/beta = [n][8] fixed-point weights) and the
  * placement of the resized image; src is u8 [src_h, src_w, src_channels >= 3] with the given row pitch; pad_rgb is HOST memory.
+ * Without tables: vgh_detect(..., VGH_IMG_U8_RAW, ...) letterboxes a whole batch of any-size images in one launch per arena chunk,
+ * with the tables built in the library (a port of letterbox.py, bit-identical).
  * ---------------------------------------------------------------------------------------------- */
 int vgh_letterbox(const uint8_t* src_dev, int src_h, int src_w, int src_channels, int64_t src_pitch_bytes, const int32_t* xofs_dev,
                   const int16_t* alpha_dev, const int32_t* yofs_dev, const int16_t* beta_dev, int new_w, int new_h, int pad_x, int pad_y,
