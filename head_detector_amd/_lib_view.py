@@ -1,0 +1,59 @@
+"""ctypes binding of libvghview.so (include/vgh_view.h): the companion library of result-side image helpers.  libvgh.so knows nothing of it
+and ``_lib`` does not load it; like ``_lib`` there is NO fallback: a missing library raises ``VghError``."""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Optional
+
+from ._lib import VghError
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(HERE, "libvghview.so")
+MAX_SIDE = 32767  # = VGHV_MAX_SIDE
+
+
+class Crop(C.Structure):
+    """vghv_crop: one crop of an affinely warped u8 RGB image (tables and result addressed by offsets into the call's shared arrays)."""
+    _fields_ = [("src_dev", C.c_void_p), ("src_pitch_bytes", C.c_int64), ("src_h", C.c_int32), ("src_w", C.c_int32), ("src_channels", C.c_int32),
+                ("crop_w", C.c_int32), ("crop_h", C.c_int32), ("table_offset", C.c_int64), ("dst_offset", C.c_int64)]
+
+
+# every symbol include/vgh_view.h declares: (restype, argtypes)
+_P, _I, _I64 = C.c_void_p, C.c_int, C.c_int64
+SYMBOLS = {
+    "vghv_version": (C.c_char_p, []),
+    "vghv_last_error": (C.c_char_p, []),
+    "vghv_warp_crops": (_I, [C.POINTER(Crop), _I, _P, _I64, _P, _I64, _P]),
+}
+
+_lib: Optional[C.CDLL] = None
+
+
+def load() -> C.CDLL:
+    """Load libvghview.so and bind every declared symbol. Raises VghError if the library is absent."""
+    global _lib
+    if _lib is not None:
+        return _lib
+    if not os.path.exists(LIB_PATH):
+        raise VghError(f"{LIB_PATH} not found: the HIP extension is not built. Run `python -m head_detector_amd.build` (needs hipcc). "
+                       "There is no CPU fallback in this package.")
+    try:
+        lib = C.CDLL(LIB_PATH)
+    except OSError as e:
+        raise VghError(f"failed to load {LIB_PATH}: {e}") from e
+    for name, (res, args) in SYMBOLS.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise VghError(f"{LIB_PATH} does not export {name} (stale build?)") from e
+        fn.restype = res
+        fn.argtypes = args
+    _lib = lib
+    return lib
+
+
+def check(rc: int) -> None:
+    if rc != 0:
+        msg = load().vghv_last_error().decode("utf-8", "replace")
+        raise VghError(f"libvghview error {rc}: {msg}")

@@ -1,4 +1,4 @@
-"""In-tree build of libvgh.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
+"""In-tree build of libvgh.so and its companion libvghview.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
 from __future__ import annotations
 
 import os
@@ -11,6 +11,9 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvgh.so")
 SOURCES = ["conv_igemm.hip", "conv_patch.hip", "conv_rings.hip", "conv_pp.hip", "ds_b2b.hip", "conv_split.hip", "conv_f32.hip", "stem_pool.hip", "postproc.hip", "flame.hip", "net.hip", "detect.hip", "raster.hip", "letterbox.hip", "ctx.hip", "streams.hip"]
 EXPERIMENT_SOURCES = ["stem_ds.hip"]  # measured losers kept for tools/: part of libvgh_exp.so (-DVGH_EXPERIMENTS) only
+# libvghview.so (include/vgh_view.h): result-side image helpers, a library of its own -- never linked into libvgh.so, hidden visibility but for its vghv_* exports
+LIB_VIEW = os.path.join(HERE, "libvghview.so")
+VIEW_SOURCES = ["aligned.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -21,12 +24,24 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found")
 
 
-def needs_build() -> bool:
+def _core_needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(HERE, "..", "include", "vgh.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in VIEW_SOURCES] + [os.path.join(HERE, "..", "include", "vgh.h")]
     return any(os.path.getmtime(d) > t for d in deps)
+
+
+def _view_needs_build() -> bool:
+    if not os.path.exists(LIB_VIEW):
+        return True
+    t = os.path.getmtime(LIB_VIEW)
+    deps = [os.path.join(CSRC, f) for f in VIEW_SOURCES] + [os.path.join(HERE, "..", "include", "vgh_view.h")]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
+def needs_build() -> bool:
+    return _core_needs_build() or _view_needs_build()
 
 
 LIB_EXP = os.path.join(HERE, "libvgh_exp.so")  # -DVGH_EXPERIMENTS build (work-skipping switches, env-var knobs): tools/ only
@@ -37,17 +52,19 @@ def build_lib(force: bool = False, verbose: bool = True, experiments: bool = Fal
         return _build(os.path.join(HERE, "libvgh_var.so"), [f"-D{d}" for d in variant_defines], "build_var", verbose)
     if experiments:
         return _build(LIB_EXP, ["-DVGH_EXPERIMENTS"], "build_exp", verbose)
-    if not force and not needs_build():
-        return LIB
-    return _build(LIB, [], "build", verbose)
+    if force or _view_needs_build():
+        _build(LIB_VIEW, ["-fvisibility=hidden"], "build_view", verbose, VIEW_SOURCES)
+    if force or _core_needs_build():
+        _build(LIB, [], "build", verbose)
+    return LIB
 
 
-def _build(LIB: str, extra, objdir: str, verbose: bool) -> str:
+def _build(LIB: str, extra, objdir: str, verbose: bool, sources=None) -> str:
     hipcc = _hipcc()
     objs, procs = [], []
     t0 = time.time()
     os.makedirs(os.path.join(HERE, objdir), exist_ok=True)
-    for src in SOURCES + (EXPERIMENT_SOURCES if "-DVGH_EXPERIMENTS" in extra else []):
+    for src in sources or SOURCES + (EXPERIMENT_SOURCES if "-DVGH_EXPERIMENTS" in extra else []):
         obj = os.path.join(HERE, objdir, src.replace(".hip", ".o"))
         objs.append(obj)
         cmd = [hipcc, *FLAGS, *extra, "-c", os.path.join(CSRC, src), "-o", obj]
@@ -61,18 +78,18 @@ def _build(LIB: str, extra, objdir: str, verbose: bool) -> str:
         elif verbose and out.strip():
             sys.stderr.write(f"[vgh build] {src}:\n{out}\n")
     if failed:
-        raise RuntimeError("libvgh.so: compilation failed")
+        raise RuntimeError(f"{os.path.basename(LIB)}: compilation failed")
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB]
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
-        raise RuntimeError(f"libvgh.so: link failed\n{r.stdout}")
+        raise RuntimeError(f"{os.path.basename(LIB)}: link failed\n{r.stdout}")
     import ctypes
 
     try:  # catches undefined symbols (e.g. a kernel whose host stub was silently dropped) at build time, not on the GPU box
         ctypes.CDLL(LIB)
     except OSError as e:
         os.remove(LIB)
-        raise RuntimeError(f"libvgh.so: built but does not load: {e}")
+        raise RuntimeError(f"{os.path.basename(LIB)}: built but does not load: {e}")
     if verbose:
         sys.stderr.write(f"[vgh build] built {LIB} in {time.time() - t0:.1f}s\n")
     return LIB

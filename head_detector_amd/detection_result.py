@@ -1,8 +1,10 @@
 """PredictionResult with the reference's surface (head_detector/detection_result.py:38-81).  ``heads`` is the
 accelerated product.  ``get_pncc`` runs the HIP z-buffer rasteriser (csrc/raster.hip = the reference's Sim3DR kernel,
 SURVEY.md 8(f) N3) and needs the reference's mesh assets (user-supplied, see ``head_detector_amd.pncc.MeshAssets``);
-``save_meshes`` is pure file IO.  ``draw`` / ``get_aligned_heads`` are cv2 visualisation helpers outside the scope
-(SURVEY.md 2 rows 5-8): they raise a clear error instead of silently doing something else."""
+``save_meshes`` is pure file IO.  ``get_aligned_heads`` plans every head's crop on the host and warps all of them in one launch of
+csrc/aligned.hip (libvghview.so, ``head_detector_amd.aligned``); it needs ``head_indices`` (assets/flame_indices/head_indices.npy of the
+reference, user-supplied like the other mesh assets).  ``draw`` is a cv2 visualisation helper outside the scope: it
+raises a clear error instead of silently doing something else."""
 from __future__ import annotations
 
 import os
@@ -14,14 +16,16 @@ from .head_info import HeadMetadata
 
 
 class PredictionResult:
-    def __init__(self, original_image: np.ndarray, heads: List[HeadMetadata], faces: Optional[np.ndarray] = None, pncc_processor=None):
+    def __init__(self, original_image: np.ndarray, heads: List[HeadMetadata], faces: Optional[np.ndarray] = None, pncc_processor=None, *,
+                 head_indices: Optional[np.ndarray] = None):
         self.original_image = original_image
         self.heads = heads
         self._faces = faces  # [F,3] 0-based triangle indices of the FLAME mesh
         self.pncc_processor = pncc_processor  # head_detector_amd.pncc.PNCCProcessor or None (no mesh assets supplied)
+        self.head_indices = head_indices  # vertex subset of refined_head_bbox, or None (no mesh assets supplied)
 
     def _unsupported(self, what: str):
-        raise NotImplementedError(f"PredictionResult.{what} is a cv2/Sim3DR visualisation helper of the reference and is outside the accelerated forward path; "
+        raise NotImplementedError(f"PredictionResult.{what} is a cv2 visualisation helper of the reference and is outside the accelerated forward path; "
                                   "use `.heads` (bbox, score, flame_params, vertices_3d, head_pose).")
 
     def draw(self, method: str = "full"):
@@ -35,8 +39,16 @@ class PredictionResult:
                                     "construct HeadDetector(..., assets_dir=<reference>/head_detector/assets)")
         return self.pncc_processor(self.original_image, self.heads)
 
-    def get_aligned_heads(self):
-        self._unsupported("get_aligned_heads")
+    def get_aligned_heads(self, to_host: bool = True):
+        """detection_result.py:56-70: one upright, square crop per head (rotated by the head's roll about its skull centre when ``abs(yaw) < 60``),
+        uint8 [h, w, 3] with the reference's shapes and bytes -- a crop that its Python slice leaves empty is returned empty, so there is one
+        per head.  ``to_host=False`` returns GPU ``torch.uint8`` tensors (views into one packed buffer) for a next model on the device."""
+        if self.head_indices is None:
+            raise FileNotFoundError("get_aligned_heads needs the reference's mesh asset flame_indices/head_indices.npy: "
+                                    "construct HeadDetector(..., assets_dir=<reference>/head_detector/assets) or pass head_indices= to PredictionResult")
+        from .aligned import get_aligned_heads
+
+        return get_aligned_heads(self.original_image, self.heads, self.head_indices, to_host=to_host)
 
     def save_meshes(self, save_folder: str):
         """One Wavefront OBJ per head, 'v x y z' / 'f a b c' with 1-based faces (detection_result.py:22-35,73-78)."""

@@ -155,12 +155,15 @@ class HeadDetector:
         self._calibration_images = calibration_images
         self._flame = FLAMELayer(flame_path=flame_path, model=flame_model, device=self._device, max_heads=max(1024, 100 * max_batch))
         self.model = self._read_model(model, weights, seed)
-        # mesh assets of the reference (head_detector/assets) for PredictionResult.get_pncc(); user-supplied, optional
+        # mesh assets of the reference (head_detector/assets) for PredictionResult.get_pncc() / get_aligned_heads(); user-supplied, optional
         self._pncc = None
+        self._head_indices = None
         if mesh_assets is not None or assets_dir is not None:
-            from .pncc import PNCCProcessor
+            from .pncc import MeshAssets, PNCCProcessor
 
-            self._pncc = PNCCProcessor(mesh_assets if mesh_assets is not None else assets_dir)
+            assets = mesh_assets if mesh_assets is not None else MeshAssets.load(assets_dir)
+            self._pncc = PNCCProcessor(assets)
+            self._head_indices = assets.head_indices
 
     def _read_model(self, model: str, weights: Optional[str], seed: int) -> VGHeadsEngine:
         """detector.py:25-30 downloads ``okupyn/vgg_heads/<model>.trcd``; without a network the archive is a user-supplied file:
@@ -297,7 +300,7 @@ class HeadDetector:
                 heads.append(HeadMetadata(bbox=Bbox(x=bb[0], y=bb[1], w=bb[2] - bb[0], h=bb[3] - bb[1]), score=scores[b, i], flame_params=fp, vertices_3d=verts[at],
                                           head_pose=RPY(roll=float(rpy[at, 0]), pitch=float(rpy[at, 1]), yaw=float(rpy[at, 2]))))
                 at += 1
-            results.append(PredictionResult(original_image=orig, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc))
+            results.append(PredictionResult(original_image=orig, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc, head_indices=self._head_indices))
         return results
 
     def __call__(self, image: Union[str, "np.ndarray", Any], confidence_threshold: float = 0.5) -> PredictionResult:
@@ -305,4 +308,4 @@ class HeadDetector:
         image, cache = self._preprocess(original_image)
         predictions = self._process(image)
         heads = self._postprocess(predictions, cache, confidence_threshold)
-        return PredictionResult(original_image=original_image, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc)
+        return PredictionResult(original_image=original_image, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc, head_indices=self._head_indices)

@@ -1,0 +1,61 @@
+/* vgh_view.h -- libvghview.so: result-side image helpers for the MI355X head detector (gfx950 only).
+ *
+ * A companion of libvgh.so (include/vgh.h), not a part of it: libvgh.so never loads it, it links none of libvgh's objects, and a client of
+ * the detector's C ABI that wants no image helpers never pays for it.  Every export carries the prefix vghv_; everything else in the
+ * library has hidden visibility.
+ *
+ * Conventions as in vgh.h: functions return VGHV_OK (0) or a negative code, vghv_last_error() gives the message of the calling thread's
+ * last failure, `stream` is a hipStream_t (NULL = the default stream), work is queued on it and not waited for.
+ */
+#ifndef VGH_VIEW_H
+#define VGH_VIEW_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#if defined(__GNUC__)
+#define VGHV_API __attribute__((visibility("default")))
+#else
+#define VGHV_API
+#endif
+
+#define VGHV_OK 0
+#define VGHV_ERR_INVALID (-1)
+#define VGHV_ERR_HIP (-2)
+#define VGHV_ERR_NOMEM (-3)
+
+#define VGHV_MAX_SIDE 32767 /* source coordinates travel as int16 in the arithmetic this restates */
+
+/* One crop of an affinely warped u8 RGB image: OpenCV's 8-bit warpAffine(src, M, dsize, INTER_LINEAR), constant-0 border, evaluated only for
+ * the crop_w x crop_h pixels that are kept.  The caller supplies the fixed-point tables of those pixels (all int32, built in double on the
+ * host with round-half-to-even, A | b = the inverse of M, (cx, cy) = the crop's origin on the warped canvas):
+ *     adelta[i] = rint(A00 * (cx + i) * 1024)                  i < crop_w
+ *     bdelta[i] = rint(A10 * (cx + i) * 1024)                  i < crop_w
+ *     x0[j]     = rint((A01 * (cy + j) + b0) * 1024) + 16      j < crop_h
+ *     y0[j]     = rint((A11 * (cy + j) + b1) * 1024) + 16      j < crop_h
+ * laid out [adelta | bdelta | x0 | y0] from tables[table_offset].  The kernel itself is integer arithmetic only.  An identity matrix makes the
+ * crop a plain copy of src[cy : cy + crop_h, cx : cx + crop_w]. */
+typedef struct vghv_crop {
+    const uint8_t* src_dev;  /* u8 [src_h, src_w, 3] on the device */
+    int64_t src_pitch_bytes; /* >= src_w * 3: distance of two rows (strided views are fine) */
+    int32_t src_h, src_w;    /* 1 .. VGHV_MAX_SIDE */
+    int32_t src_channels;    /* 3 */
+    int32_t crop_w, crop_h;  /* >= 0; a crop with an empty side writes nothing */
+    int64_t table_offset;    /* first of this crop's 2 * crop_w + 2 * crop_h entries in `tables` */
+    int64_t dst_offset;      /* byte offset in dst_dev of the dense [crop_h, crop_w, 3] result */
+} vghv_crop;
+
+VGHV_API const char* vghv_version(void);
+VGHV_API const char* vghv_last_error(void);
+
+/* All n crops in ONE launch (descriptors, tile list and tables travel in one upload).  `tables` is host memory with n_tables entries; every
+ * crop's table range must lie inside it and every crop's result inside dst_bytes (checked before anything is queued; results must not overlap). */
+VGHV_API int vghv_warp_crops(const vghv_crop* crops, int n, const int32_t* tables, int64_t n_tables, uint8_t* dst_dev, int64_t dst_bytes, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -10,7 +10,8 @@ check prints PASS / FAIL / SKIPPED with the number behind it, and the exit code 
   2. --pkl           : FLAMELayer from the pickle; the reference's known-answer fixture (yolo_head_training/tests/1.json, committed as tests/golden/fixture_1json.npz):
                        its 413 parameters through vgh_flame_decode against its vertices_3d (the one full known answer the reference holds; 1e-4).
   3. --cv2           : the letterbox kernel (csrc/letterbox.hip, OpenCV's 8-bit LANCZOS4 restated) against cv2.resize + copyMakeBorder on seeded images and on --images,
-                       bit for bit (detector.py:40-52).
+                       bit for bit (detector.py:40-52); the warp of get_aligned_heads (csrc/aligned.hip, OpenCV's 8-bit bilinear warpAffine restated) against
+                       cv2.getRotationMatrix2D + cv2.warpAffine, bit for bit (utils.py:93-117).
   4. --images + weights (+ --pkl): bf16 / fp16 / int8 / fp8 against the fp16x3 parity mode on those photographs -- dense boxes IoU, scores, the kept detections'
                        parameters and vertices; int8 / fp8 calibrated on the same photographs.
 GPU needed for 2 - 4 (the library has no CPU path)."""
@@ -127,6 +128,23 @@ def main():
                 worst = max(worst, int(d.max()))
                 nbad += int((d > 0).sum())
             report("letterbox vs cv2 (bit for bit)", worst == 0, f"{len(imgs)} images, max |diff| {worst}, {nbad} differing bytes")
+            # the warp of get_aligned_heads (csrc/aligned.hip, OpenCV's 8-bit bilinear warpAffine restated) against cv2.getRotationMatrix2D + cv2.warpAffine
+            from head_detector_amd import aligned
+
+            worst, nbad, mworst, nwarp = 0, 0, 0.0, 0
+            for im in imgs:
+                h, w = im.shape[:2]
+                for angle in (0.0, 90.0, 17.3, -23.7, 181.0):
+                    centre = (int(rng.integers(0, w)), int(rng.integers(0, h)))
+                    mworst = max(mworst, float(np.abs(aligned.get_rotation_matrix_2d(centre, angle) - cv2.getRotationMatrix2D(centre, angle, 1.0)).max()))
+                    m, bounds = aligned.get_rotation_mat(im, centre, angle)
+                    got = aligned.warp_crops(im, [(m, (0, 0, bounds[0], bounds[1]))])[0]
+                    d = np.abs(got.astype(np.int32) - cv2.warpAffine(im, m, bounds, flags=cv2.INTER_LINEAR).astype(np.int32))
+                    worst = max(worst, int(d.max()))
+                    nbad += int((d > 0).sum())
+                    nwarp += 1
+            report("aligned-head warp vs cv2.warpAffine (bit for bit)", worst == 0 and mworst <= 1e-12,
+                   f"{nwarp} warps, max |diff| {worst}, {nbad} differing bytes, rotation matrix max |diff| {mworst:.1e}")
     else:
         skipped("letterbox vs cv2", "needs --cv2 and a GPU")
     # ---- 4. throughput modes against the parity mode on real photographs ----
