@@ -11,6 +11,9 @@ from ._lib import VghError
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libvghview.so")
 MAX_SIDE = 32767  # = VGHV_MAX_SIDE
+MAX_COORD = 1 << 24  # = VGHV_MAX_COORD
+MAX_RADIUS = 32  # = VGHV_MAX_RADIUS
+MAX_DRAW_HEADS = 65536  # = VGHV_MAX_DRAW_HEADS
 
 
 class Crop(C.Structure):
@@ -19,12 +22,20 @@ class Crop(C.Structure):
                 ("crop_w", C.c_int32), ("crop_h", C.c_int32), ("table_offset", C.c_int64), ("dst_offset", C.c_int64)]
 
 
+class DrawJob(C.Structure):
+    """vghv_draw_job: one image and everything that is painted over it (points, boxes and topology are host arrays, uploaded by the call)."""
+    _fields_ = [("src_dev", C.c_void_p), ("src_pitch_bytes", C.c_int64), ("dst_dev", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("n_heads", C.c_int32), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32), ("n_indices", C.c_int32), ("radius", C.c_int32), ("points", C.c_void_p),
+                ("boxes", C.c_void_p), ("triangles", C.c_void_p), ("indices", C.c_void_p), ("half_widths", C.c_void_p)]
+
+
 # every symbol include/vgh_view.h declares: (restype, argtypes)
 _P, _I, _I64 = C.c_void_p, C.c_int, C.c_int64
 SYMBOLS = {
     "vghv_version": (C.c_char_p, []),
     "vghv_last_error": (C.c_char_p, []),
     "vghv_warp_crops": (_I, [C.POINTER(Crop), _I, _P, _I64, _P, _I64, _P]),
+    "vghv_draw_heads": (_I, [C.POINTER(DrawJob), _P]),
 }
 
 _lib: Optional[C.CDLL] = None

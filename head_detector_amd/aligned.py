@@ -166,21 +166,21 @@ def warp_tables(matrix: np.ndarray, region: Tuple[int, int, int, int]) -> np.nda
     return np.clip(t, -2147483648, 2147483647).astype(np.int32)
 
 
-def _device_image(image) -> torch.Tensor:
+def _device_image(image, what: str = "aligned crops") -> torch.Tensor:
     """uint8 [H, W, 3] as a GPU tensor whose pixels are 3 bytes apart (rows may be further apart: strided views are used as they are)."""
     t = image if isinstance(image, torch.Tensor) else np.asarray(image)
     if str(t.dtype).replace("torch.", "") != "uint8" or len(t.shape) != 3 or t.shape[2] != 3:
-        raise ValueError(f"aligned crops need a uint8 image [H,W,3]; got {t.dtype} {tuple(t.shape)}")
+        raise ValueError(f"{what} need a uint8 image [H,W,3]; got {t.dtype} {tuple(t.shape)}")
     if not (1 <= t.shape[0] <= _lib_view.MAX_SIDE and 1 <= t.shape[1] <= _lib_view.MAX_SIDE):
-        raise ValueError(f"aligned crops need an image of 1 .. {_lib_view.MAX_SIDE} pixels a side; got {tuple(t.shape[:2])}")
+        raise ValueError(f"{what} need an image of 1 .. {_lib_view.MAX_SIDE} pixels a side; got {tuple(t.shape[:2])}")
     if not torch.cuda.is_available():
-        raise VghError("head_detector_amd.aligned needs a GPU: the HIP warp kernel is the only implementation of the pixels")
+        raise VghError(f"{what} need a GPU: the HIP kernels of libvghview.so are the only implementation of the pixels")
     if not isinstance(t, torch.Tensor):
         t = torch.from_numpy(np.ascontiguousarray(t))
     if not t.is_cuda:
         return t.contiguous().to(torch.device("cuda", torch.cuda.current_device()))
     if t.stride(2) != 1 or t.stride(1) != 3 or (t.shape[0] > 1 and t.stride(0) < 3 * t.shape[1]):
-        raise ValueError(f"aligned crops need pixels 3 bytes apart and rows at least 3 * W bytes apart; got strides {tuple(t.stride())}")
+        raise ValueError(f"{what} need pixels 3 bytes apart and rows at least 3 * W bytes apart; got strides {tuple(t.stride())}")
     return t
 
 

@@ -13,7 +13,8 @@ SOURCES = ["conv_igemm.hip", "conv_patch.hip", "conv_rings.hip", "conv_pp.hip", 
 EXPERIMENT_SOURCES = ["stem_ds.hip"]  # measured losers kept for tools/: part of libvgh_exp.so (-DVGH_EXPERIMENTS) only
 # libvghview.so (include/vgh_view.h): result-side image helpers, a library of its own -- never linked into libvgh.so, hidden visibility but for its vghv_* exports
 LIB_VIEW = os.path.join(HERE, "libvghview.so")
-VIEW_SOURCES = ["aligned.hip"]
+VIEW_SOURCES = ["aligned.hip", "draw.hip"]
+VIEW_HEADERS = ["vghv_internal.h"]  # shared by the view library's sources only: a dependency of libvghview.so, not of libvgh.so
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -28,7 +29,7 @@ def _core_needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in VIEW_SOURCES] + [os.path.join(HERE, "..", "include", "vgh.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in VIEW_SOURCES + VIEW_HEADERS] + [os.path.join(HERE, "..", "include", "vgh.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -36,7 +37,7 @@ def _view_needs_build() -> bool:
     if not os.path.exists(LIB_VIEW):
         return True
     t = os.path.getmtime(LIB_VIEW)
-    deps = [os.path.join(CSRC, f) for f in VIEW_SOURCES] + [os.path.join(HERE, "..", "include", "vgh_view.h")]
+    deps = [os.path.join(CSRC, f) for f in VIEW_SOURCES + VIEW_HEADERS] + [os.path.join(HERE, "..", "include", "vgh_view.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

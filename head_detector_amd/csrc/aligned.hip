@@ -7,21 +7,18 @@
 //   X = (X0[y] + adelta[x]) >> 5, Y likewise; source pixel (X >> 5, Y >> 5), fractions X & 31, Y & 31; weights 32 * {(32-fx)(32-fy), fx(32-fy),
 //   (32-fx)fy, fx fy} (sum 2^15); taps outside the source read 0; (sum + 2^14) >> 15.
 // PARITY UNPINNED against cv2 itself (absent from this image); bit-exact against tests/warp_affine_ref.py.
-// Self-contained on purpose: no csrc/vgh_internal.h, no object of libvgh.so; built with -fvisibility=hidden, only the vghv_* functions are exported.
-#include <hip/hip_runtime.h>
+// Self-contained on purpose: no csrc/vgh_internal.h, no object of libvgh.so (csrc/vghv_internal.h is what the view library's sources share); built with -fvisibility=hidden, only the vghv_* functions are exported.
 #include <stdarg.h>
-#include <stdint.h>
 #include <stdio.h>
 #include <string.h>
 
 #include <map>
 #include <mutex>
 
-#include "../../include/vgh_view.h"
+#include "vghv_internal.h"
 
-namespace {
+namespace vghv {
 
-// ---- error plumbing: never throw across the C ABI ----------------------------------------------------------------------------------
 thread_local char g_error[512] = "";
 
 void set_error(const char* fmt, ...) {
@@ -31,22 +28,33 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-#define VGHV_HIP(expr)                                                                         \
-    do {                                                                                       \
-        hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess) {                                                                \
-            set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e));    \
-            return VGHV_ERR_HIP;                                                               \
-        }                                                                                      \
-    } while (0)
+const char* last_error() { return g_error; }
 
-#define VGHV_REQUIRE(cond, ...)      \
-    do {                             \
-        if (!(cond)) {               \
-            set_error(__VA_ARGS__);  \
-            return VGHV_ERR_INVALID; \
-        }                            \
-    } while (0)
+int staging_reserve(Staging& s, size_t need, const char* who) {
+    if (s.recorded) VGHV_HIP(hipEventSynchronize(s.ev));
+    s.recorded = false;
+    if (!s.ev) VGHV_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    if (need <= s.bytes) return VGHV_OK;
+    hipHostFree(s.host);
+    hipFree(s.dev);
+    s.host = s.dev = nullptr;
+    s.bytes = 0;
+    const size_t cap = align16(need + need / 2);
+    if (hipHostMalloc((void**)&s.host, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&s.dev, cap) != hipSuccess) {
+        hipHostFree(s.host);
+        s.host = nullptr;
+        set_error("%s: allocating %zu bytes of staging failed", who, cap);
+        return VGHV_ERR_NOMEM;
+    }
+    s.bytes = cap;
+    return VGHV_OK;
+}
+
+}  // namespace vghv
+
+namespace {
+
+using namespace vghv;
 
 // device-side descriptor of one crop
 struct Crop {
@@ -101,46 +109,15 @@ __global__ __launch_bounds__(256) void warp_crops_kernel(const Crop* __restrict_
     }
 }
 
-// ---- staging: descriptors + tile list + tables of one call, one pinned block and one device block per device, grown on demand ---------
-// A block is rewritten only after the previous call's copy and kernel have run (the event), whatever stream they were queued on.
-struct Staging {
-    uint8_t* host = nullptr;
-    uint8_t* dev = nullptr;
-    size_t bytes = 0;
-    hipEvent_t ev = nullptr;
-    bool recorded = false;
-};
-
+// ---- staging: descriptors + tile list + tables of one call (vghv_internal.h) -----------------------------------------------------------
 std::mutex g_mutex;
 std::map<int, Staging> g_staging;
 
-size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-int staging_reserve(Staging& s, size_t need) {
-    if (s.recorded) VGHV_HIP(hipEventSynchronize(s.ev));
-    s.recorded = false;
-    if (!s.ev) VGHV_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    if (need <= s.bytes) return VGHV_OK;
-    hipHostFree(s.host);
-    hipFree(s.dev);
-    s.host = s.dev = nullptr;
-    s.bytes = 0;
-    const size_t cap = align16(need + need / 2);
-    if (hipHostMalloc((void**)&s.host, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&s.dev, cap) != hipSuccess) {
-        hipHostFree(s.host);
-        s.host = nullptr;
-        set_error("warp_crops: allocating %zu bytes of staging failed", cap);
-        return VGHV_ERR_NOMEM;
-    }
-    s.bytes = cap;
-    return VGHV_OK;
-}
-
 }  // namespace
 
-extern "C" VGHV_API const char* vghv_version(void) { return "vghview 1 (gfx950)"; }
+extern "C" VGHV_API const char* vghv_version(void) { return "vghview 2 (gfx950)"; }
 
-extern "C" VGHV_API const char* vghv_last_error(void) { return g_error; }
+extern "C" VGHV_API const char* vghv_last_error(void) { return vghv::last_error(); }
 
 extern "C" VGHV_API int vghv_warp_crops(const vghv_crop* crops, int n, const int32_t* tables, int64_t n_tables, uint8_t* dst_dev, int64_t dst_bytes, void* stream) {
     VGHV_REQUIRE(n >= 0 && n_tables >= 0 && dst_bytes >= 0, "warp_crops: negative count");
@@ -174,7 +151,7 @@ extern "C" VGHV_API int vghv_warp_crops(const vghv_crop* crops, int n, const int
     Staging& s = g_staging[device];
     const size_t at_tiles = align16((size_t)n * sizeof(Crop)), at_tab = align16(at_tiles + (size_t)n_tiles * sizeof(Tile));
     const size_t total = at_tab + (size_t)n_tables * sizeof(int32_t);
-    if (int rc = staging_reserve(s, total)) return rc;
+    if (int rc = staging_reserve(s, total, "warp_crops")) return rc;
     Crop* hc = (Crop*)s.host;
     Tile* ht = (Tile*)(s.host + at_tiles);
     for (int i = 0; i < n; ++i) {

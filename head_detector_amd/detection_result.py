@@ -3,8 +3,11 @@ accelerated product.  ``get_pncc`` runs the HIP z-buffer rasteriser (csrc/raster
 SURVEY.md 8(f) N3) and needs the reference's mesh assets (user-supplied, see ``head_detector_amd.pncc.MeshAssets``);
 ``save_meshes`` is pure file IO.  ``get_aligned_heads`` plans every head's crop on the host and warps all of them in one launch of
 csrc/aligned.hip (libvghview.so, ``head_detector_amd.aligned``); it needs ``head_indices`` (assets/flame_indices/head_indices.npy of the
-reference, user-supplied like the other mesh assets).  ``draw`` is a cv2 visualisation helper outside the scope: it
-raises a clear error instead of silently doing something else."""
+reference, user-supplied like the other mesh assets).  ``draw`` paints boxes, the mesh wireframe and landmark dots over a copy of the image
+with the kernels of csrc/draw.hip (libvghview.so, ``head_detector_amd.draw``) for the methods "full", "bbox", "landmarks" and "points"; it needs
+``triangles`` (assets/triangles.txt), ``head_indices`` and ``face_indices`` (assets/flame_indices/face.npy) as the method requires.  Its pixel
+rules are OpenCV's as restated in tests/draw_ref.py (parity with cv2 itself is unpinned, like the warp of the aligned crops); "pose" raises
+NotImplementedError instead of drawing something approximately right."""
 from __future__ import annotations
 
 import os
@@ -17,19 +20,23 @@ from .head_info import HeadMetadata
 
 class PredictionResult:
     def __init__(self, original_image: np.ndarray, heads: List[HeadMetadata], faces: Optional[np.ndarray] = None, pncc_processor=None, *,
-                 head_indices: Optional[np.ndarray] = None):
+                 head_indices: Optional[np.ndarray] = None, triangles: Optional[np.ndarray] = None, face_indices: Optional[np.ndarray] = None):
         self.original_image = original_image
         self.heads = heads
         self._faces = faces  # [F,3] 0-based triangle indices of the FLAME mesh
         self.pncc_processor = pncc_processor  # head_detector_amd.pncc.PNCCProcessor or None (no mesh assets supplied)
-        self.head_indices = head_indices  # vertex subset of refined_head_bbox, or None (no mesh assets supplied)
+        self.head_indices = head_indices  # vertex subset of refined_head_bbox and of the landmark dots, or None (no mesh assets supplied)
+        self.triangles = triangles  # [T, 3] vertex indices of the wireframe drawn by draw(), or None
+        self.face_indices = face_indices  # vertex subset drawn by draw("points"), or None
 
-    def _unsupported(self, what: str):
-        raise NotImplementedError(f"PredictionResult.{what} is a cv2 visualisation helper of the reference and is outside the accelerated forward path; "
-                                  "use `.heads` (bbox, score, flame_params, vertices_3d, head_pose).")
+    def draw(self, method: str = "full", to_host: bool = True):
+        """detection_result.py:45-51: a NEW uint8 [H, W, 3] image with every head drawn over a copy of the original, in the order of ``heads``:
+        "bbox" the box; "landmarks" the mesh wireframe and the ``head_indices`` dots; "points" the ``face_indices`` dots; "full" box, wireframe and
+        dots.  ``to_host=False`` returns a GPU ``torch.uint8`` tensor.  Any other method raises KeyError like the reference's lookup, "pose"
+        NotImplementedError, a method whose mesh asset is missing ``draw.DrawAssetsMissing`` (a FileNotFoundError and a NotImplementedError)."""
+        from .draw import draw_heads
 
-    def draw(self, method: str = "full"):
-        self._unsupported("draw")
+        return draw_heads(self.original_image, self.heads, method, triangles=self.triangles, head_indices=self.head_indices, face_indices=self.face_indices, to_host=to_host)
 
     def get_pncc(self):
         """detection_result.py:58-59: PNCC image of all heads (uint8 [H,W,3]); like the reference it negates z of every

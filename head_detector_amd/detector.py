@@ -157,13 +157,14 @@ class HeadDetector:
         self.model = self._read_model(model, weights, seed)
         # mesh assets of the reference (head_detector/assets) for PredictionResult.get_pncc() / get_aligned_heads(); user-supplied, optional
         self._pncc = None
-        self._head_indices = None
+        self._head_indices = self._triangles = self._face_indices = None
         if mesh_assets is not None or assets_dir is not None:
             from .pncc import MeshAssets, PNCCProcessor
 
             assets = mesh_assets if mesh_assets is not None else MeshAssets.load(assets_dir)
             self._pncc = PNCCProcessor(assets)
             self._head_indices = assets.head_indices
+            self._triangles, self._face_indices = getattr(assets, "triangles", None), getattr(assets, "face_indices", None)  # PredictionResult.draw()
 
     def _read_model(self, model: str, weights: Optional[str], seed: int) -> VGHeadsEngine:
         """detector.py:25-30 downloads ``okupyn/vgg_heads/<model>.trcd``; without a network the archive is a user-supplied file:
@@ -300,7 +301,7 @@ class HeadDetector:
                 heads.append(HeadMetadata(bbox=Bbox(x=bb[0], y=bb[1], w=bb[2] - bb[0], h=bb[3] - bb[1]), score=scores[b, i], flame_params=fp, vertices_3d=verts[at],
                                           head_pose=RPY(roll=float(rpy[at, 0]), pitch=float(rpy[at, 1]), yaw=float(rpy[at, 2]))))
                 at += 1
-            results.append(PredictionResult(original_image=orig, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc, head_indices=self._head_indices))
+            results.append(PredictionResult(original_image=orig, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc, head_indices=self._head_indices, triangles=self._triangles, face_indices=self._face_indices))
         return results
 
     def __call__(self, image: Union[str, "np.ndarray", Any], confidence_threshold: float = 0.5) -> PredictionResult:
@@ -308,4 +309,4 @@ class HeadDetector:
         image, cache = self._preprocess(original_image)
         predictions = self._process(image)
         heads = self._postprocess(predictions, cache, confidence_threshold)
-        return PredictionResult(original_image=original_image, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc, head_indices=self._head_indices)
+        return PredictionResult(original_image=original_image, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc, head_indices=self._head_indices, triangles=self._triangles, face_indices=self._face_indices)

@@ -74,13 +74,17 @@ def compute_ncc_color_codes(template_face: np.ndarray, subset_indexes: Optional[
 
 
 class MeshAssets:
-    """The reference's mesh assets (head_detector/assets).  ``MeshAssets.load(dir)`` reads the four .npy files."""
+    """The reference's mesh assets (head_detector/assets).  ``MeshAssets.load(dir)`` reads the three .npy files of the PNCC renderer and, where they
+    exist, flame_indices/head_indices.npy (aligned crops, draw), triangles.txt and flame_indices/face.npy (draw)."""
 
-    def __init__(self, full_faces: np.ndarray, v_template: np.ndarray, head_w_ears: np.ndarray, head_indices: Optional[np.ndarray] = None):
+    def __init__(self, full_faces: np.ndarray, v_template: np.ndarray, head_w_ears: np.ndarray, head_indices: Optional[np.ndarray] = None,
+                 triangles: Optional[np.ndarray] = None, face_indices: Optional[np.ndarray] = None):
         self.full_faces = np.asarray(full_faces)
         self.v_template = np.asarray(v_template)
         self.head_w_ears = np.asarray(head_w_ears)
         self.head_indices = None if head_indices is None else np.asarray(head_indices)
+        self.triangles = None if triangles is None else np.asarray(triangles).astype(np.int32)
+        self.face_indices = None if face_indices is None else np.asarray(face_indices)
 
     @classmethod
     def load(cls, assets_dir: str) -> "MeshAssets":
@@ -91,8 +95,12 @@ class MeshAssets:
             return p
 
         hi = os.path.join(assets_dir, "flame_indices", "head_indices.npy")
+        tri = os.path.join(assets_dir, "triangles.txt")
+        face = os.path.join(assets_dir, "flame_indices", "face.npy")
         return cls(np.load(need("full_faces.npy")), np.load(need("v_template.npy")), np.load(need(os.path.join("flame_indices", "head_w_ears.npy"))),
-                   np.load(hi, allow_pickle=True)[()] if os.path.exists(hi) else None)
+                   np.load(hi, allow_pickle=True)[()] if os.path.exists(hi) else None,
+                   np.loadtxt(tri, delimiter=",").astype(np.int32) if os.path.exists(tri) else None,
+                   np.load(face, allow_pickle=True)[()] if os.path.exists(face) else None)
 
 
 class PNCCProcessor:

@@ -55,6 +55,40 @@ VGHV_API const char* vghv_last_error(void);
  * crop's table range must lie inside it and every crop's result inside dst_bytes (checked before anything is queued; results must not overlap). */
 VGHV_API int vghv_warp_crops(const vghv_crop* crops, int n, const int32_t* tables, int64_t n_tables, uint8_t* dst_dev, int64_t dst_bytes, void* stream);
 
+/* ---- drawing: PredictionResult.draw ---------------------------------------------------------------------------------------------------------
+ * A copy of a u8 image with, for every head in order, up to three classes of primitives painted over it in this order (a later class paints
+ * over an earlier one, a later head over an earlier head), with the pixel sets of OpenCV's
+ *   class 0 box    cv2.rectangle(img, (x, y), (x + w, y + h), (255, 0, 0), 2)                          when boxes != NULL
+ *   class 1 wire   cv2.polylines(img, [triangle], isClosed=True, color=(0, 0, 255), thickness=1)       for every row of triangles, n_triangles > 0
+ *   class 2 dots   cv2.circle(img, point[indices[k]], radius, (255, 255, 255), -1)                    for every index, n_indices > 0
+ * (colours go to channels 0, 1, 2 as written).  All primitives are expanded on the device from what this struct points to; the number of
+ * launches does not depend on n_heads.  Painter's order is kept by an order key per pixel (1 + 3 * head + class, atomic max over a u32 plane of
+ * library scratch) and a resolve pass that writes colour or source pixel to dst.  Exact rules: tests/draw_ref.py. */
+#define VGHV_MAX_COORD 16777216 /* |point|, |box x, y| < 2^24; 0 <= box w, h < 2^24 */
+#define VGHV_MAX_RADIUS 32
+#define VGHV_MAX_DRAW_HEADS 65536
+
+typedef struct vghv_draw_job {
+    const uint8_t* src_dev;     /* u8 [height, width, 3] on the device */
+    int64_t src_pitch_bytes;    /* >= width * 3 */
+    uint8_t* dst_dev;           /* u8 [height, width, 3] on the device, dense, 4-byte aligned, not overlapping src */
+    int32_t height, width;      /* 1 .. VGHV_MAX_SIDE */
+    int32_t channels;           /* 3 */
+    int32_t n_heads;            /* 0 .. VGHV_MAX_DRAW_HEADS; 0 makes dst a copy of src */
+    int32_t n_vertices;         /* V: points per head */
+    int32_t n_triangles;        /* T, 0 = no wire */
+    int32_t n_indices;          /* K, 0 = no dots */
+    int32_t radius;             /* 1 .. VGHV_MAX_RADIUS when n_indices > 0 */
+    const int32_t* points;      /* host, [n_heads, V, 2]: x, y in pixels */
+    const int32_t* boxes;       /* host, [n_heads, 4]: x, y, w, h; NULL = no boxes */
+    const int32_t* triangles;   /* host, [T, 3]: indices < V, shared by all heads */
+    const int32_t* indices;     /* host, [K]: indices < V, shared by all heads */
+    const int32_t* half_widths; /* host, [radius + 1]: half the width of the filled circle's row at distance j from its centre row, 0 .. radius */
+} vghv_draw_job;
+
+/* Everything is checked (every index against V, every coordinate against VGHV_MAX_COORD) before anything is queued. */
+VGHV_API int vghv_draw_heads(const vghv_draw_job* job, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,9 @@ check prints PASS / FAIL / SKIPPED with the number behind it, and the exit code 
                        its 413 parameters through vgh_flame_decode against its vertices_3d (the one full known answer the reference holds; 1e-4).
   3. --cv2           : the letterbox kernel (csrc/letterbox.hip, OpenCV's 8-bit LANCZOS4 restated) against cv2.resize + copyMakeBorder on seeded images and on --images,
                        bit for bit (detector.py:40-52); the warp of get_aligned_heads (csrc/aligned.hip, OpenCV's 8-bit bilinear warpAffine restated) against
-                       cv2.getRotationMatrix2D + cv2.warpAffine, bit for bit (utils.py:93-117).
+                       cv2.getRotationMatrix2D + cv2.warpAffine, bit for bit (utils.py:93-117); PredictionResult.draw (csrc/draw.hip, OpenCV's rectangle / polylines /
+                       circle restated) for "full", "bbox", "landmarks" and "points" against the reference's own loop of cv2 calls (draw_utils.py), bit for bit, with
+                       the time that loop takes for the same heads.
   4. --images + weights (+ --pkl): bf16 / fp16 / int8 / fp8 against the fp16x3 parity mode on those photographs -- dense boxes IoU, scores, the kept detections'
                        parameters and vertices; int8 / fp8 calibrated on the same photographs.
 GPU needed for 2 - 4 (the library has no CPU path)."""
@@ -145,8 +147,54 @@ def main():
                     nwarp += 1
             report("aligned-head warp vs cv2.warpAffine (bit for bit)", worst == 0 and mworst <= 1e-12,
                    f"{nwarp} warps, max |diff| {worst}, {nbad} differing bytes, rotation matrix max |diff| {mworst:.1e}")
+            # PredictionResult.draw (csrc/draw.hip) against the reference's loop of cv2 calls for the same heads (draw_utils.py:15-42,87-90, detection_result.py:12-18,45-51)
+            import time
+            import types
+
+            from head_detector_amd import draw
+            from head_detector_amd.head_info import Bbox
+
+            V, cols = 5023, 71
+            k = np.arange(V)
+            row, col = k // cols, np.where((k // cols) % 2 == 1, cols - 1 - k % cols, k % cols)
+            start = rng.integers(0, V - cols - 1, 4816)
+            tri = np.stack([start, start + 1, start + cols + rng.integers(-1, 2, 4816)], axis=1).astype(np.int32)
+            tri[-40:] = rng.integers(0, V, (40, 3))  # a few edges as long as the head
+            hidx, fidx = np.sort(rng.choice(V, 2470, replace=False)), np.sort(rng.choice(V, 2094, replace=False))
+            nbad, ndraw, t_cv2, t_gpu = 0, 0, 0.0, 0.0
+            for im in imgs[:4]:
+                h, w = im.shape[:2]
+                heads = []
+                for _ in range(6):
+                    size, cx, cy = rng.uniform(0.1, 0.6) * min(h, w), rng.uniform(-0.1 * w, 1.1 * w), rng.uniform(-0.1 * h, 1.1 * h)
+                    xyz = np.stack([cx + size * ((col + rng.uniform(-0.4, 0.4, V)) / (cols - 1) - 0.5), cy + 1.2 * size * ((row + rng.uniform(-0.4, 0.4, V)) / (cols - 1) - 0.5),
+                                    np.zeros(V)], axis=1).astype(np.float32)
+                    x0, y0, x1, y1 = (int(q) for q in (xyz[:, 0].min(), xyz[:, 1].min(), xyz[:, 0].max(), xyz[:, 1].max()))
+                    heads.append(types.SimpleNamespace(vertices_3d=xyz, bbox=Bbox(x0, y0, x1 - x0, y1 - y0)))
+                radius = max(1, int(min(h, w) * 0.001))
+                for method in ("full", "bbox", "landmarks", "points"):
+                    t0 = time.perf_counter()
+                    got = draw.draw_heads(im, heads, method, triangles=tri, head_indices=hidx, face_indices=fidx)
+                    t1 = time.perf_counter()
+                    ref = im.copy()
+                    for head in heads:  # the reference's loop, call for call
+                        pv = head.vertices_3d[:, :2]
+                        if method in ("full", "bbox"):
+                            x, y, bw, bh = head.bbox
+                            cv2.rectangle(ref, (x, y), (x + bw, y + bh), (255, 0, 0), 2)
+                        if method in ("full", "landmarks"):
+                            for t in tri:
+                                cv2.polylines(ref, [np.array([(pv[i][0], pv[i][1]) for i in t], np.int32).reshape((-1, 1, 2))], isClosed=True, color=(0, 0, 255), thickness=1)
+                        for pt in np.take(pv, hidx if method != "points" else fidx, axis=0) if method != "bbox" else []:
+                            cv2.circle(ref, (int(pt[0]), int(pt[1])), radius, (255, 255, 255), -1)
+                    t2 = time.perf_counter()
+                    nbad += int((got != ref).any(axis=2).sum())
+                    ndraw += 1
+                    t_gpu, t_cv2 = t_gpu + (t1 - t0), t_cv2 + (t2 - t1)
+            report("draw vs the reference's cv2 loop (bit for bit)", nbad == 0, f"{ndraw} pictures of 6 heads, {nbad} differing pixels; the cv2 loop took {t_cv2:.2f} s, "
+                   f"draw() with upload and download {t_gpu:.2f} s")
     else:
-        skipped("letterbox vs cv2", "needs --cv2 and a GPU")
+        skipped("letterbox, warp and draw vs cv2", "needs --cv2 and a GPU")
     # ---- 4. throughput modes against the parity mode on real photographs ----
     if gpu and sd is not None and args.images:
         from head_detector_amd.engine import VGHeadsEngine
