@@ -29,6 +29,14 @@ class DrawJob(C.Structure):
                 ("boxes", C.c_void_p), ("triangles", C.c_void_p), ("indices", C.c_void_p), ("half_widths", C.c_void_p)]
 
 
+class MeshJob(C.Structure):
+    """vghv_mesh_job: one image and the meshes blended over it (vertices and colours on the device, topology and per-head pixel bounds on the host)."""
+    _fields_ = [("src_dev", C.c_void_p), ("src_pitch_bytes", C.c_int64), ("dst_dev", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("n_heads", C.c_int32), ("n_vertices", C.c_int32), ("n_triangles", C.c_int32), ("reverse", C.c_int32), ("colors_per_head", C.c_int32), ("shade", C.c_int32),
+                ("alpha", C.c_float), ("z_sign", C.c_float), ("ambient", C.c_float), ("diffuse", C.c_float), ("verts_dev", C.c_void_p), ("triangles", C.c_void_p),
+                ("bounds", C.c_void_p), ("colors_dev", C.c_void_p), ("color", C.c_float * 3), ("light", C.c_float * 3)]
+
+
 # every symbol include/vgh_view.h declares: (restype, argtypes)
 _P, _I, _I64 = C.c_void_p, C.c_int, C.c_int64
 SYMBOLS = {
@@ -36,6 +44,8 @@ SYMBOLS = {
     "vghv_last_error": (C.c_char_p, []),
     "vghv_warp_crops": (_I, [C.POINTER(Crop), _I, _P, _I64, _P, _I64, _P]),
     "vghv_draw_heads": (_I, [C.POINTER(DrawJob), _P]),
+    "vghv_vertex_normals": (_I, [_P, _I, _I, _P, _I, _P, _P]),
+    "vghv_render_meshes": (_I, [C.POINTER(MeshJob), _P]),
 }
 
 _lib: Optional[C.CDLL] = None

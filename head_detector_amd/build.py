@@ -13,7 +13,7 @@ SOURCES = ["conv_igemm.hip", "conv_patch.hip", "conv_rings.hip", "conv_pp.hip", 
 EXPERIMENT_SOURCES = ["stem_ds.hip"]  # measured losers kept for tools/: part of libvgh_exp.so (-DVGH_EXPERIMENTS) only
 # libvghview.so (include/vgh_view.h): result-side image helpers, a library of its own -- never linked into libvgh.so, hidden visibility but for its vghv_* exports
 LIB_VIEW = os.path.join(HERE, "libvghview.so")
-VIEW_SOURCES = ["aligned.hip", "draw.hip"]
+VIEW_SOURCES = ["aligned.hip", "draw.hip", "mesh_render.hip"]
 VIEW_HEADERS = ["vghv_internal.h"]  # shared by the view library's sources only: a dependency of libvghview.so, not of libvgh.so
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]
 

@@ -1,0 +1,421 @@
+// libvghview.so (include/vgh_view.h): the other half of Sim3DR (head_detector/Sim3DR/Sim3DR.py) -- `get_normal` and `_rasterize` with
+// alpha < 1 -- and what they exist for: the lit, semi-transparent solid mesh over the photograph (PredictionResult.render_mesh).
+//
+// NORMALS (`_get_normal`, rasterize_kernel.cpp:158-215).  The reference adds every triangle's un-normalised cross product to its three
+// corners, serially over triangles; float sums depend on their order, so each vertex adds its incident triangles in ASCENDING TRIANGLE
+// INDEX, corner 0 before 1 before 2 (a vertex named twice by one triangle is added twice).  The host builds that list (a stable counting
+// sort of the 3 T corners by vertex) and one lane per (head, vertex) walks it.  No float atomics: the result would depend on arrival order.
+//
+// BLENDED RASTERISER (`_rasterize`, :219-293).  With alpha < 1 a pixel is blended once for EVERY triangle that beats the running depth, in
+// triangle order, and truncated to a byte each time, so the winner alone does not determine the byte: csrc/raster.hip's "atomic max, then
+// resolve" cannot express it.  Per pixel the result is a fold over heads (in order, each with a fresh depth) and over the head's
+// triangles in index order.  Tile-major:
+//   boxes    one lane per (head, triangle): the triangle's clamped integer bounding box as 4 x int16 (8 B a triangle for the scans below)
+//   tiles    one 256-lane workgroup per 16 x 16 image tile that some head touches (the host builds "tile -> heads in order" from the
+//            per-head pixel bounds); a lane owns one pixel and keeps its bytes and depth in registers.  For every head of the tile the
+//            workgroup scans the head's boxes 256 at a time, compacts the ones that overlap the tile IN INDEX ORDER into LDS (ballot +
+//            prefix) together with their pixel-independent set-up, and every lane then walks that list serially with exactly the
+//            reference's arithmetic.  One write per pixel at the end.  Deterministic, no atomics, launches independent of the head count.
+// All arithmetic is IEEE float32 in the reference's operation order (contraction off, true division, correctly rounded sqrt): normals
+// and images are bit-identical to the reference's own C++ (tests/test_gpu_shaded_mesh.py).
+#include <string.h>
+
+#include <map>
+#include <mutex>
+#include <vector>
+
+#include "vghv_internal.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+using namespace vghv;
+
+constexpr int TILE = 16;  // 16 x 16 pixels = the 256 lanes of a workgroup
+
+// ---- normals, and the colours of the shaded mesh ----------------------------------------------------------------------------------------
+struct Shade {
+    float cr, cg, cb, ambient, diffuse, lx, ly, lz;
+};
+
+// One lane per (head, vertex).  first[v] .. first[v + 1] are the vertex's entries of `incident` (triangle indices, ascending, a triangle
+// once per corner that names the vertex).  shade == 0: out = the normal; shade == 1: out = the colour of the lit vertex:
+//   s = |(nx * lx + ny * ly) + nz * lz|,  t = a < 1 ? a : 1 with a = ambient + diffuse * s,  c_k = t * colour_k.
+__global__ __launch_bounds__(256) void normals_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tri, const int32_t* __restrict__ first,
+                                                      const int32_t* __restrict__ incident, int n_total, int V, float zsign, int shade, Shade sh, float* __restrict__ out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_total) return;
+    const int head = i / V, v = i - head * V;
+    const float* p = verts + (size_t)head * V * 3;
+    float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+    for (int e = first[v]; e < first[v + 1]; ++e) {
+        const int t = incident[e];
+        const int i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
+        const float ax = p[3 * i0], ay = p[3 * i0 + 1], az = zsign * p[3 * i0 + 2];
+        const float v1x = p[3 * i1] - ax, v1y = p[3 * i1 + 1] - ay, v1z = zsign * p[3 * i1 + 2] - az;
+        const float v2x = p[3 * i2] - ax, v2y = p[3 * i2 + 1] - ay, v2z = zsign * p[3 * i2 + 2] - az;
+        nx += v1y * v2z - v1z * v2y;
+        ny += v1z * v2x - v1x * v2z;
+        nz += v1x * v2y - v1y * v2x;
+    }
+    float det = sqrtf(nx * nx + ny * ny + nz * nz);
+    if (det <= 0) det = 1e-6f;
+    nx = nx / det;
+    ny = ny / det;
+    nz = nz / det;
+    float* o = out + (size_t)i * 3;
+    if (shade) {
+        const float s = fabsf((nx * sh.lx + ny * sh.ly) + nz * sh.lz);
+        const float a = sh.ambient + sh.diffuse * s;
+        const float t = a < 1.0f ? a : 1.0f;
+        o[0] = t * sh.cr;
+        o[1] = t * sh.cg;
+        o[2] = t * sh.cb;
+    } else {
+        o[0] = nx;
+        o[1] = ny;
+        o[2] = nz;
+    }
+}
+
+// ---- the triangle's integer box (rasterize_kernel.cpp:245-253) ------------------------------------------------------------------------------
+struct alignas(8) Box {
+    int16_t x0, y0, x1, y1;  // inclusive; x1 < x0 = covers nothing
+};
+
+__global__ __launch_bounds__(256) void boxes_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tri, int n_total, int V, int T, int h, int w,
+                                                    Box* __restrict__ boxes) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_total) return;
+    const int head = i / T, t = i - head * T;
+    const float* p = verts + (size_t)head * V * 3;
+    const int i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
+    const float p0x = p[3 * i0], p0y = p[3 * i0 + 1], p1x = p[3 * i1], p1y = p[3 * i1 + 1], p2x = p[3 * i2], p2y = p[3 * i2 + 1];
+    const float fx0 = fminf(p0x, fminf(p1x, p2x)), fx1 = fmaxf(p0x, fmaxf(p1x, p2x));
+    const float fy0 = fminf(p0y, fminf(p1y, p2y)), fy1 = fmaxf(p0y, fmaxf(p1y, p2y));
+    Box b = {1, 1, 0, 0};
+    // a triangle with a non-finite corner is skipped ((int)ceil(nan) is undefined in C; fminf / fmaxf would hide a NaN, so look at the corners)
+    const bool finite = isfinite(p0x) && isfinite(p0y) && isfinite(p1x) && isfinite(p1y) && isfinite(p2x) && isfinite(p2y);
+    if (finite) {
+        // clamp in float first: (int)ceil(1e30f) is undefined in C; the clamped result is what any in-range input gives
+        const int x_min = max((int)ceilf(fmaxf(fx0, -1.0f)), 0), x_max = min((int)floorf(fminf(fx1, (float)w)), w - 1);
+        const int y_min = max((int)ceilf(fmaxf(fy0, -1.0f)), 0), y_max = min((int)floorf(fminf(fy1, (float)h)), h - 1);
+        if (x_max >= x_min && y_max >= y_min) b = {(int16_t)x_min, (int16_t)y_min, (int16_t)x_max, (int16_t)y_max};  // w, h <= VGHV_MAX_SIDE
+    }
+    boxes[i] = b;
+}
+
+// ---- tiles ------------------------------------------------------------------------------------------------------------------------------------
+// What a lane needs of a triangle that overlaps the tile: get_point_weight's pixel-independent part (rasterize_kernel.cpp:55-72), the three
+// depths, the nine colour values and the box.  96 B x 256 = 24 KB of LDS a workgroup.
+struct Hit {
+    float p0x, p0y, v0x, v0y, v1x, v1y, dot00, dot01, dot11, inv;
+    float d0, d1, d2;
+    float c0[3], c1[3], c2[3];
+    Box box;
+};
+
+__device__ __forceinline__ void tri_setup(Hit& t, float p1x, float p1y, float p2x, float p2y) {
+    t.v0x = p2x - t.p0x;
+    t.v0y = p2y - t.p0y;
+    t.v1x = p1x - t.p0x;
+    t.v1y = p1y - t.p0y;
+    t.dot00 = t.v0x * t.v0x + t.v0y * t.v0y;
+    t.dot01 = t.v0x * t.v1x + t.v0y * t.v1y;
+    t.dot11 = t.v1x * t.v1x + t.v1y * t.v1y;
+    const float den = t.dot00 * t.dot11 - t.dot01 * t.dot01;
+    t.inv = (den == 0.0f) ? 0.0f : 1.0f / den;
+}
+__device__ __forceinline__ void tri_weights(const Hit& t, float px, float py, float& w0, float& w1, float& w2) {
+    const float v2x = px - t.p0x, v2y = py - t.p0y;
+    const float dot02 = t.v0x * v2x + t.v0y * v2y;
+    const float dot12 = t.v1x * v2x + t.v1y * v2y;
+    const float u = (t.dot11 * dot02 - t.dot01 * dot12) * t.inv;
+    const float v = (t.dot00 * dot12 - t.dot01 * dot02) * t.inv;
+    w0 = 1.0f - u - v;
+    w1 = v;
+    w2 = u;
+}
+
+// (unsigned char)((1 - alpha) * byte + alpha * 255 * p_color): truncation, the low 8 bits for in-range values (as csrc/raster.hip)
+__device__ __forceinline__ uint32_t blend(uint32_t byte, float pc, float one_minus_alpha, float alpha255) {
+    const float val = one_minus_alpha * (float)byte + alpha255 * pc;
+    return (uint32_t)((int)val & 0xFF);
+}
+
+// blockIdx.x = an entry of the tile list: tile_xy = tile column | tile row << 16, its heads are tile_heads[tile_first[b] .. tile_first[b + 1]).
+// colours: [V, 3] shared by all heads (colour_stride 0) or [n, V, 3] (colour_stride V * 3).
+__global__ __launch_bounds__(256) void tiles_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tri, const float* __restrict__ colours, size_t colour_stride,
+                                                    const Box* __restrict__ boxes, const uint32_t* __restrict__ tile_xy, const int32_t* __restrict__ tile_first,
+                                                    const int32_t* __restrict__ tile_heads, int V, int T, int h, int w, int reverse, float zsign, float alpha,
+                                                    const uint8_t* __restrict__ src, int64_t src_pitch, uint8_t* __restrict__ dst) {
+    __shared__ Hit hits[256];
+    __shared__ int wave_hits[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t xy = tile_xy[blockIdx.x];
+    const int tx0 = (int)(xy & 0xffffu) * TILE, ty0 = (int)(xy >> 16) * TILE;
+    const int tx1 = min(tx0 + TILE - 1, w - 1), ty1 = min(ty0 + TILE - 1, h - 1);
+    const int x = tx0 + (tid & (TILE - 1)), y = ty0 + (tid >> 4);
+    const bool live = x < w && y < h;
+    const size_t row = (size_t)(reverse ? h - 1 - y : y);  // `reverse` flips the row that is read and written, not the geometry's
+    uint32_t q0 = 0, q1 = 0, q2 = 0;
+    if (live) {
+        const uint8_t* s = src + row * (size_t)src_pitch + (size_t)x * 3;
+        q0 = s[0];
+        q1 = s[1];
+        q2 = s[2];
+    }
+    const float px = (float)x, py = (float)y;
+    const float one_minus_alpha = 1.0f - alpha, alpha255 = alpha * 255.0f;
+    for (int e = tile_first[blockIdx.x]; e < tile_first[blockIdx.x + 1]; ++e) {
+        const int head = tile_heads[e];
+        const float* p = verts + (size_t)head * V * 3;
+        const float* col = colours + (size_t)head * colour_stride;
+        const Box* hb = boxes + (size_t)head * T;
+        float depth = -1e8f;  // a fresh depth buffer for every head (Sim3DR.py:30)
+        for (int base = 0; base < T; base += 256) {
+            const int t = base + tid;
+            Box b = {1, 1, 0, 0};
+            if (t < T) b = hb[t];
+            const bool hit = b.x1 >= b.x0 && b.x1 >= tx0 && b.x0 <= tx1 && b.y1 >= ty0 && b.y0 <= ty1;
+            const unsigned long long mask = __ballot(hit);
+            if (lane == 0) wave_hits[wave] = __popcll(mask);
+            __syncthreads();
+            int slot = __popcll(mask & ((1ull << lane) - 1ull)), count = 0;
+            for (int k = 0; k < 4; ++k) {
+                const int c = wave_hits[k];
+                if (k < wave) slot += c;
+                count += c;
+            }
+            if (hit) {  // index order: waves in order, lanes in order
+                const int i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
+                Hit k;
+                k.p0x = p[3 * i0];
+                k.p0y = p[3 * i0 + 1];
+                tri_setup(k, p[3 * i1], p[3 * i1 + 1], p[3 * i2], p[3 * i2 + 1]);
+                k.d0 = zsign * p[3 * i0 + 2];
+                k.d1 = zsign * p[3 * i1 + 2];
+                k.d2 = zsign * p[3 * i2 + 2];
+                for (int c = 0; c < 3; ++c) {
+                    k.c0[c] = col[3 * i0 + c];
+                    k.c1[c] = col[3 * i1 + c];
+                    k.c2[c] = col[3 * i2 + c];
+                }
+                k.box = b;
+                hits[slot] = k;
+            }
+            __syncthreads();
+            for (int s = 0; s < count; ++s) {
+                const Hit& k = hits[s];  // every lane reads the same entry: a broadcast
+                // the triangle's own box, per pixel: in float arithmetic all three weights can be positive one pixel outside it
+                if (x < k.box.x0 || x > k.box.x1 || y < k.box.y0 || y > k.box.y1) continue;
+                float w0, w1, w2;
+                tri_weights(k, px, py, w0, w1, w2);
+                if (w2 > 0 && w1 > 0 && w0 > 0) {
+                    const float pd = w0 * k.d0 + w1 * k.d1 + w2 * k.d2;
+                    if (pd > depth) {  // false for NaN; -0 and +0 compare equal, as in the reference
+                        q0 = blend(q0, w0 * k.c0[0] + w1 * k.c1[0] + w2 * k.c2[0], one_minus_alpha, alpha255);
+                        q1 = blend(q1, w0 * k.c0[1] + w1 * k.c1[1] + w2 * k.c2[1], one_minus_alpha, alpha255);
+                        q2 = blend(q2, w0 * k.c0[2] + w1 * k.c1[2] + w2 * k.c2[2], one_minus_alpha, alpha255);
+                        depth = pd;
+                    }
+                }
+            }
+            // the next chunk's wave_hits are written before, its hits after, a barrier every wave reaches only when it is done with this list
+        }
+    }
+    if (live) {
+        uint8_t* o = dst + (row * (size_t)w + (size_t)x) * 3;
+        o[0] = (uint8_t)q0;
+        o[1] = (uint8_t)q1;
+        o[2] = (uint8_t)q2;
+    }
+}
+
+// ---- per-device state ---------------------------------------------------------------------------------------------------------------------
+struct MeshState {
+    Staging staging;
+    Box* boxes = nullptr;  // library scratch [n, T], grown on demand
+    size_t box_bytes = 0;
+};
+
+std::mutex g_mutex;
+std::map<int, MeshState> g_state;
+
+// every triangle index against V
+int check_triangles(const char* who, const int32_t* triangles, int T, int V) {
+    for (int64_t i = 0; i < (int64_t)T * 3; ++i)
+        VGHV_REQUIRE(triangles[i] >= 0 && triangles[i] < V, "%s: triangle %lld: index %d outside the %d vertices", who, (long long)(i / 3), triangles[i], V);
+    return VGHV_OK;
+}
+
+// [first (V + 1) | incident (3 T)]: a stable counting sort of the 3 T corners by vertex, so that a vertex's triangles come in ascending index
+void build_incidence(const int32_t* triangles, int T, int V, int32_t* first, int32_t* incident) {
+    memset(first, 0, ((size_t)V + 1) * sizeof(int32_t));
+    for (int64_t i = 0; i < (int64_t)T * 3; ++i) first[triangles[i] + 1]++;
+    for (int v = 0; v < V; ++v) first[v + 1] += first[v];
+    std::vector<int32_t> at(first, first + V);
+    for (int64_t i = 0; i < (int64_t)T * 3; ++i) incident[at[triangles[i]]++] = (int32_t)(i / 3);
+}
+
+size_t incidence_bytes(int T, int V) { return align16(((size_t)V + 1) * 4) + align16((size_t)T * 12); }
+
+void launch_normals(const float* verts, const uint8_t* d_tri, const uint8_t* d_inc, int n, int V, float zsign, int shade, const Shade& sh, float* out, hipStream_t st) {
+    const int total = n * V;
+    hipLaunchKernelGGL(normals_kernel, dim3((unsigned)(total + 255) / 256), dim3(256), 0, st, verts, (const int32_t*)d_tri, (const int32_t*)d_inc,
+                       (const int32_t*)(d_inc + align16(((size_t)V + 1) * 4)), total, V, zsign, shade, sh, out);
+}
+
+}  // namespace
+
+extern "C" VGHV_API int vghv_vertex_normals(const float* verts_dev, int n, int V, const int32_t* triangles, int T, float* normals_dev, void* stream) {
+    VGHV_REQUIRE(n >= 0 && V >= 1 && T >= 0, "vertex_normals: bad sizes (n %d, V %d, T %d)", n, V, T);
+    VGHV_REQUIRE((int64_t)n * V <= INT32_MAX / 4 && T <= INT32_MAX / 4, "vertex_normals: %lld vertices or %d triangles exceed one launch", (long long)n * V, T);
+    if (n == 0) return VGHV_OK;
+    VGHV_REQUIRE(verts_dev && normals_dev, "vertex_normals: null vertices or normals (verts_dev %p, normals_dev %p)", (const void*)verts_dev, (void*)normals_dev);
+    VGHV_REQUIRE(triangles || T == 0, "vertex_normals: null triangles");
+    VGHV_REQUIRE(verts_dev != normals_dev, "vertex_normals: normals_dev overlaps verts_dev");
+    if (int rc = check_triangles("vertex_normals", triangles, T, V)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    int device = 0;
+    VGHV_HIP(hipGetDevice(&device));
+    std::lock_guard<std::mutex> lock(g_mutex);
+    MeshState& s = g_state[device];
+    const size_t at_inc = align16((size_t)T * 12), total = at_inc + incidence_bytes(T, V);
+    if (int rc = staging_reserve(s.staging, total, "vertex_normals")) return rc;
+    uint8_t* h = s.staging.host;
+    if (T) memcpy(h, triangles, (size_t)T * 12);
+    build_incidence(triangles, T, V, (int32_t*)(h + at_inc), (int32_t*)(h + at_inc + align16(((size_t)V + 1) * 4)));
+    VGHV_HIP(hipMemcpyAsync(s.staging.dev, h, total, hipMemcpyHostToDevice, st));
+    launch_normals(verts_dev, s.staging.dev, s.staging.dev + at_inc, n, V, 1.0f, 0, Shade{}, normals_dev, st);
+    VGHV_HIP(hipGetLastError());
+    VGHV_HIP(hipEventRecord(s.staging.ev, st));
+    s.staging.recorded = true;
+    return VGHV_OK;
+}
+
+extern "C" VGHV_API int vghv_render_meshes(const vghv_mesh_job* job, void* stream) {
+    VGHV_REQUIRE(job, "render_meshes: null job");
+    const vghv_mesh_job& j = *job;
+    // everything is checked before anything is allocated, written or queued
+    VGHV_REQUIRE(j.src_dev && j.dst_dev, "render_meshes: null image (src_dev %p, dst_dev %p)", (const void*)j.src_dev, (void*)j.dst_dev);
+    VGHV_REQUIRE(j.channels == 3, "render_meshes: %d channels (needs 3: u8 RGB)", j.channels);
+    VGHV_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHV_MAX_SIDE && j.width <= VGHV_MAX_SIDE, "render_meshes: image %d x %d outside 1 .. %d", j.height, j.width,
+                 VGHV_MAX_SIDE);
+    VGHV_REQUIRE(j.src_pitch_bytes >= (int64_t)j.width * 3, "render_meshes: src_pitch_bytes %lld < width * 3 = %lld", (long long)j.src_pitch_bytes, (long long)j.width * 3);
+    const int W = j.width, H = j.height, n = j.n_heads, V = j.n_vertices, T = j.n_triangles;
+    {
+        const uintptr_t s0 = (uintptr_t)j.src_dev, s1 = s0 + (size_t)(H - 1) * (size_t)j.src_pitch_bytes + (size_t)W * 3, d0 = (uintptr_t)j.dst_dev, d1 = d0 + (size_t)H * W * 3;
+        VGHV_REQUIRE(s1 <= d0 || d1 <= s0, "render_meshes: dst_dev overlaps src_dev");
+    }
+    VGHV_REQUIRE(n >= 0 && n <= VGHV_MAX_DRAW_HEADS, "render_meshes: %d heads outside 0 .. %d", n, VGHV_MAX_DRAW_HEADS);
+    VGHV_REQUIRE(V >= 0 && T >= 0, "render_meshes: negative count");
+    VGHV_REQUIRE(j.alpha >= 0.0f && j.alpha <= 1.0f, "render_meshes: alpha %g outside 0 .. 1", (double)j.alpha);
+    VGHV_REQUIRE(j.z_sign == 1.0f || j.z_sign == -1.0f, "render_meshes: z_sign %g is neither +1 nor -1", (double)j.z_sign);
+    VGHV_REQUIRE(j.shade == 0 || j.shade == 1, "render_meshes: shade %d is neither 0 nor 1", j.shade);
+    VGHV_REQUIRE(j.colors_per_head == 0 || j.colors_per_head == 1, "render_meshes: colors_per_head %d is neither 0 nor 1", j.colors_per_head);
+    const bool paint = n > 0 && T > 0;
+    if (paint) {
+        VGHV_REQUIRE(V >= 1 && j.verts_dev && j.triangles && j.bounds && j.colors_dev, "render_meshes: null vertices, triangles, bounds or colours (n_vertices %d)", V);
+        VGHV_REQUIRE((int64_t)n * T <= INT32_MAX / 4 && (int64_t)n * V <= INT32_MAX / 4, "render_meshes: %lld triangles or %lld vertices exceed one launch", (long long)n * T,
+                     (long long)n * V);
+        VGHV_REQUIRE(!j.shade || j.colors_per_head, "render_meshes: shading writes one colour table per head (colors_per_head must be 1)");
+        if (j.shade) {
+            const float c[8] = {j.color[0], j.color[1], j.color[2], j.ambient, j.diffuse, j.light[0], j.light[1], j.light[2]};
+            for (int i = 0; i < 8; ++i) VGHV_REQUIRE(c[i] == c[i] && c[i] - c[i] == 0.0f, "render_meshes: a shading constant is not finite");
+            VGHV_REQUIRE(j.color[0] >= 0 && j.color[0] <= 1 && j.color[1] >= 0 && j.color[1] <= 1 && j.color[2] >= 0 && j.color[2] <= 1 && j.ambient >= 0 && j.diffuse >= 0,
+                         "render_meshes: colour outside 0 .. 1 or negative ambient / diffuse");
+        }
+        if (int rc = check_triangles("render_meshes", j.triangles, T, V)) return rc;
+        for (int i = 0; i < n; ++i) {
+            const int32_t* b = j.bounds + 4 * i;
+            const bool empty = b[2] < b[0] || b[3] < b[1];
+            VGHV_REQUIRE(empty || (b[0] >= 0 && b[1] >= 0 && b[2] < W && b[3] < H), "render_meshes: head %d: bounds (%d, %d, %d, %d) outside the image", i, b[0], b[1], b[2], b[3]);
+        }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int device = 0;
+    VGHV_HIP(hipGetDevice(&device));
+    std::lock_guard<std::mutex> lock(g_mutex);
+    MeshState& s = g_state[device];
+
+    // "tile -> heads in order" for the tiles some head touches: count, prefix, fill (heads are visited in order, so every list is ascending)
+    const int tiles_x = (W + TILE - 1) / TILE, tiles_y = (H + TILE - 1) / TILE;
+    std::vector<int32_t> grid;
+    size_t n_tiles = 0, n_pairs = 0;
+    if (paint) {
+        grid.assign((size_t)tiles_x * tiles_y + 1, 0);
+        for (int i = 0; i < n; ++i) {
+            const int32_t* b = j.bounds + 4 * i;
+            if (b[2] < b[0] || b[3] < b[1]) continue;
+            for (int ty = b[1] / TILE; ty <= b[3] / TILE; ++ty)
+                for (int tx = b[0] / TILE; tx <= b[2] / TILE; ++tx) grid[(size_t)ty * tiles_x + tx]++;
+        }
+        for (size_t t = 0; t < (size_t)tiles_x * tiles_y; ++t) {
+            n_tiles += grid[t] != 0;
+            n_pairs += (size_t)grid[t];
+        }
+    }
+    VGHV_REQUIRE(n_pairs <= (size_t)INT32_MAX, "render_meshes: %zu (tile, head) pairs exceed one launch", n_pairs);
+    const bool tiles = n_tiles > 0, work = tiles || (paint && j.shade);  // with shade the colours are written even when no head touches the image
+    // one upload: [triangles | first, incident (shading only) | tile_xy | tile_first | tile_heads], each from a 16-byte boundary
+    const size_t at_inc = align16((size_t)T * 12), at_xy = at_inc + (work && j.shade ? incidence_bytes(T, V) : 0), at_first = at_xy + align16(n_tiles * 4);
+    const size_t at_heads = at_first + align16((n_tiles + 1) * 4), total = at_heads + align16(n_pairs * 4);
+    if (work) {
+        if (int rc = staging_reserve(s.staging, total, "render_meshes")) return rc;  // also waits for this device's previous call
+        const size_t need = tiles ? (size_t)n * T * sizeof(Box) : 0;
+        if (need > s.box_bytes) {  // nothing is using the old boxes: the wait above covered the previous call's kernels
+            hipFree(s.boxes);
+            s.boxes = nullptr;
+            s.box_bytes = 0;
+            if (hipMalloc((void**)&s.boxes, need) != hipSuccess) {
+                set_error("render_meshes: allocating %zu bytes of triangle boxes failed", need);
+                return VGHV_ERR_NOMEM;
+            }
+            s.box_bytes = need;
+        }
+        uint8_t* h = s.staging.host;
+        memcpy(h, j.triangles, (size_t)T * 12);
+        if (j.shade) build_incidence(j.triangles, T, V, (int32_t*)(h + at_inc), (int32_t*)(h + at_inc + align16(((size_t)V + 1) * 4)));
+        uint32_t* xy = (uint32_t*)(h + at_xy);
+        int32_t* first = (int32_t*)(h + at_first);
+        int32_t* heads = (int32_t*)(h + at_heads);
+        size_t k = 0, at = 0;
+        for (size_t t = 0; t < (size_t)tiles_x * tiles_y; ++t) {  // grid[t] becomes the position of the tile's next head
+            const int32_t c = grid[t];
+            if (c) {
+                xy[k] = (uint32_t)(t % tiles_x) | (uint32_t)(t / tiles_x) << 16;
+                first[k++] = (int32_t)at;
+            }
+            grid[t] = (int32_t)at;
+            at += (size_t)c;
+        }
+        first[k] = (int32_t)at;
+        for (int i = 0; i < n; ++i) {
+            const int32_t* b = j.bounds + 4 * i;
+            if (b[2] < b[0] || b[3] < b[1]) continue;
+            for (int ty = b[1] / TILE; ty <= b[3] / TILE; ++ty)
+                for (int tx = b[0] / TILE; tx <= b[2] / TILE; ++tx) heads[grid[(size_t)ty * tiles_x + tx]++] = i;
+        }
+    }
+    // dst = src everywhere; the tiles that some head touches are then rewritten from src
+    VGHV_HIP(hipMemcpy2DAsync(j.dst_dev, (size_t)W * 3, j.src_dev, (size_t)j.src_pitch_bytes, (size_t)W * 3, (size_t)H, hipMemcpyDeviceToDevice, st));
+    if (!work) return VGHV_OK;
+    const uint8_t* d = s.staging.dev;
+    VGHV_HIP(hipMemcpyAsync(s.staging.dev, s.staging.host, total, hipMemcpyHostToDevice, st));
+    if (j.shade) {
+        const Shade sh = {j.color[0], j.color[1], j.color[2], j.ambient, j.diffuse, j.light[0], j.light[1], j.light[2]};
+        launch_normals(j.verts_dev, d, d + at_inc, n, V, j.z_sign, 1, sh, j.colors_dev, st);
+    }
+    if (tiles) {
+        hipLaunchKernelGGL(boxes_kernel, dim3((unsigned)(n * T + 255) / 256), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, n * T, V, T, H, W, s.boxes);
+        hipLaunchKernelGGL(tiles_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, (const float*)j.colors_dev,
+                           j.colors_per_head ? (size_t)V * 3 : (size_t)0, (const Box*)s.boxes, (const uint32_t*)(d + at_xy), (const int32_t*)(d + at_first),
+                           (const int32_t*)(d + at_heads), V, T, H, W, j.reverse ? 1 : 0, j.z_sign, j.alpha, j.src_dev, j.src_pitch_bytes, j.dst_dev);
+    }
+    VGHV_HIP(hipGetLastError());
+    VGHV_HIP(hipEventRecord(s.staging.ev, st));
+    s.staging.recorded = true;
+    return VGHV_OK;
+}

@@ -38,6 +38,15 @@ class PredictionResult:
 
         return draw_heads(self.original_image, self.heads, method, triangles=self.triangles, head_indices=self.head_indices, face_indices=self.face_indices, to_host=to_host)
 
+    def render_mesh(self, alpha: float = 0.7, color=(0.75, 0.75, 0.8), ambient: float = 0.35, diffuse: float = 0.65, light=(0.0, 0.0, 1.0), to_host: bool = True):
+        """A NEW uint8 [H, W, 3] image: every head's solid mesh, lit (two-sided Lambert term from Sim3DR's vertex normals) and blended with ``alpha`` by
+        Sim3DR's rasteriser over a copy of the original, in the order of ``heads`` (``head_detector_amd.mesh_render`` states the composition).  Needs
+        the FLAME model's own triangles (``faces``).  Neither the image nor any head's ``vertices_3d`` is modified.  ``to_host=False`` returns a GPU
+        ``torch.uint8`` tensor."""
+        from .mesh_render import render_mesh
+
+        return render_mesh(self.original_image, self.heads, self._faces, alpha=alpha, color=color, ambient=ambient, diffuse=diffuse, light=light, to_host=to_host)
+
     def get_pncc(self):
         """detection_result.py:58-59: PNCC image of all heads (uint8 [H,W,3]); like the reference it negates z of every
         head's ``vertices_3d`` in place."""

@@ -1,6 +1,7 @@
 """Result-side consumers on the GPU, with the reference's names:
 
-  rasterize(vertices, triangles, colors, bg=..., reverse=False)   <- head_detector/Sim3DR/Sim3DR.py:17-38
+  rasterize(vertices, triangles, colors, bg=..., reverse=False)   <- head_detector/Sim3DR/Sim3DR.py:17-38 (+ ``alpha``, the C++'s own parameter)
+  get_normal(vertices, triangles)                                 <- head_detector/Sim3DR/Sim3DR.py:9-12
   compute_ncc_color_codes(template, subset)                       <- head_detector/pncc_processor.py:40-55
   PNCCProcessor(...)(image, heads)                                <- head_detector/pncc_processor.py:58-73
   refined_head_bbox(vertices)                                     <- head_detector/utils.py:26-35
@@ -8,7 +9,8 @@
 The reference ships three mesh assets next to its sources (assets/full_faces.npy, assets/v_template.npy,
 assets/flame_indices/{head_w_ears,head_indices}.npy).  They are data the user supplies here (``assets_dir`` = the
 reference's ``head_detector/assets`` directory, or the arrays themselves); nothing is bundled.
-All arithmetic runs in libvgh (csrc/raster.hip); there is no CPU path."""
+All arithmetic runs in libvgh (csrc/raster.hip) and, for ``get_normal`` and ``rasterize(alpha < 1)``, in libvghview (csrc/mesh_render.hip); there is
+no CPU path."""
 from __future__ import annotations
 
 import os
@@ -32,9 +34,15 @@ def _stream() -> int:
 
 
 def rasterize(vertices: np.ndarray, triangles: np.ndarray, colors: np.ndarray, bg: Optional[np.ndarray] = None, height: Optional[int] = None,
-              width: Optional[int] = None, channel: Optional[int] = None, reverse: bool = False) -> np.ndarray:
+              width: Optional[int] = None, channel: Optional[int] = None, reverse: bool = False, alpha: float = 1.0) -> np.ndarray:
     """Drop-in for Sim3DR.rasterize: z-buffer render of one mesh onto ``bg`` (uint8 [H,W,C]); like the reference, ``bg`` itself is
-    painted and returned."""
+    painted and returned.  ``alpha`` is the blending weight of the reference's C++ ``_rasterize`` (which Sim3DR.py leaves at 1): with
+    ``0 <= alpha < 1`` every triangle that beats the running depth of a pixel is blended over it, in triangle order (3 channels only)."""
+    alpha = float(alpha)
+    if not 0.0 <= alpha <= 1.0:  # false for NaN
+        raise ValueError(f"alpha must lie in 0 .. 1, got {alpha}")
+    if alpha < 1.0:
+        return _rasterize_blended(vertices, triangles, colors, bg, height, width, channel, reverse, alpha)
     lib, dev = _lib.load(), _dev()
     if bg is not None:
         height, width, channel = bg.shape
@@ -58,6 +66,43 @@ def rasterize(vertices: np.ndarray, triangles: np.ndarray, colors: np.ndarray, b
         bg[...] = out
         return bg
     return out
+
+
+def _rasterize_blended(vertices, triangles, colors, bg, height, width, channel, reverse, alpha) -> np.ndarray:
+    """``rasterize`` with ``alpha < 1``: one mesh with the caller's colours through csrc/mesh_render.hip."""
+    from . import mesh_render
+
+    if bg is not None:
+        height, width, channel = bg.shape
+    else:
+        assert height is not None and width is not None and channel is not None
+        bg = np.zeros((height, width, channel), dtype=np.uint8)
+    if bg.dtype != np.uint8:
+        raise ValueError("bg must be uint8 [H,W,C]")
+    if channel != 3:
+        raise ValueError(f"rasterize with alpha < 1 supports 3 channels, got {channel} (alpha == 1 supports 1 .. 8)")
+    v = np.ascontiguousarray(vertices, dtype=np.float32)
+    c = np.ascontiguousarray(colors, dtype=np.float32)
+    if v.ndim != 2 or v.shape[1] != 3 or c.shape != (v.shape[0], 3):
+        raise ValueError(f"vertices must be [V,3] and colors [V,3], got {v.shape} and {c.shape}")
+    t = np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+    if t.size and (int(t.min()) < 0 or int(t.max()) >= v.shape[0]):
+        raise ValueError("triangle index out of range")
+    dev = _dev()
+    out = mesh_render.blend_meshes(np.ascontiguousarray(bg), torch.from_numpy(v).to(dev).unsqueeze(0), t, alpha=float(np.float32(alpha)), z_sign=1.0, reverse=reverse,
+                                   colors=torch.from_numpy(c).to(dev)).cpu().numpy()
+    if bg.flags.c_contiguous and bg.flags.writeable:
+        bg[...] = out
+        return bg
+    return out
+
+
+def get_normal(vertices, triangles):
+    """Drop-in for Sim3DR.get_normal: NumPy [V,3] float32 + [T,3] int32 -> float32 [V,3] vertex normals, bit for bit the reference's.  Also a GPU
+    tensor [n,V,3] (n meshes of one topology) -> a GPU tensor [n,V,3], nothing visiting the host."""
+    from . import mesh_render
+
+    return mesh_render.vertex_normals(vertices, triangles)
 
 
 def compute_ncc_color_codes(template_face: np.ndarray, subset_indexes: Optional[np.ndarray] = None) -> np.ndarray:

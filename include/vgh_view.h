@@ -89,6 +89,50 @@ typedef struct vghv_draw_job {
 /* Everything is checked (every index against V, every coordinate against VGHV_MAX_COORD) before anything is queued. */
 VGHV_API int vghv_draw_heads(const vghv_draw_job* job, void* stream);
 
+/* ---- shaded mesh: Sim3DR's get_normal and its alpha-blended _rasterize ------------------------------------------------------------------------
+ * Vertex normals of n meshes of one topology, bit for bit Sim3DR's _get_normal (head_detector/Sim3DR/lib/rasterize_kernel.cpp): every vertex adds
+ * the un-normalised cross products of its triangles in ascending triangle index, then normalises (a length <= 0 is replaced by 1e-6).
+ * verts_dev, normals_dev: float32 [n, V, 3] on the device (they must not overlap); triangles: host, int32 [T, 3], indices < V. */
+VGHV_API int vghv_vertex_normals(const float* verts_dev, int n, int V, const int32_t* triangles, int T, float* normals_dev, void* stream);
+
+/* One image; for every head in order one Sim3DR _rasterize(image, vertices, triangles, colours, depth = -1e8 everywhere, alpha, reverse):
+ * per pixel, every triangle (in index order) whose integer bounding box holds the pixel, whose three barycentric weights are > 0 and whose
+ * interpolated depth is > the running depth of this head paints  byte = (unsigned char)((1 - alpha) * byte + alpha * 255 * colour)  per channel
+ * in float32 and becomes the running depth.  Depth = z_sign * z.  dst is a dense copy of src with the heads painted; the number of launches does
+ * not depend on n_heads.
+ * Colours: shade == 0: colors_dev holds the caller's float32 per-vertex colours, [V, 3] for all heads (colors_per_head == 0) or [n, V, 3] (== 1).
+ *          shade == 1: colors_dev [n, V, 3] (colors_per_head must be 1) is WRITTEN by the call before it is used: with N the normal of the
+ *          vertices whose z is multiplied by z_sign,  s = |(Nx * light[0] + Ny * light[1]) + Nz * light[2]|,  t = min(1, ambient + diffuse * s),
+ *          colour_k = t * color[k], all float32 without contraction.
+ * bounds: host, per head (x0, y0, x1, y1), inclusive, inside the image, x1 < x0 or y1 < y0 = the head paints nothing.  A CONTRACT: every pixel
+ * the head can paint lies inside them (max(ceil(min x), 0) .. min(floor(max x), width - 1) over the vertices its triangles name, y alike);
+ * pixels outside them are not painted for that head. */
+typedef struct vghv_mesh_job {
+    const uint8_t* src_dev;   /* u8 [height, width, 3] on the device */
+    int64_t src_pitch_bytes;  /* >= width * 3 */
+    uint8_t* dst_dev;         /* u8 [height, width, 3] on the device, dense, not overlapping src */
+    int32_t height, width;    /* 1 .. VGHV_MAX_SIDE */
+    int32_t channels;         /* 3 */
+    int32_t n_heads;          /* 0 .. VGHV_MAX_DRAW_HEADS; 0 makes dst a copy of src */
+    int32_t n_vertices;       /* V */
+    int32_t n_triangles;      /* T; 0 makes dst a copy of src */
+    int32_t reverse;          /* 0 / 1: pixel (x, y) is read from and written to row height - 1 - y */
+    int32_t colors_per_head;  /* 0 / 1 */
+    int32_t shade;            /* 0 / 1 */
+    float alpha;              /* 0 .. 1 */
+    float z_sign;             /* +1 or -1 */
+    float ambient, diffuse;   /* shade == 1: finite, >= 0 */
+    const float* verts_dev;   /* f32 [n_heads, V, 3] on the device */
+    const int32_t* triangles; /* host, [T, 3]: indices < V, shared by all heads */
+    const int32_t* bounds;    /* host, [n_heads, 4] */
+    float* colors_dev;        /* f32 on the device, read (shade == 0) or written and read (shade == 1) */
+    float color[3];           /* shade == 1: 0 .. 1 */
+    float light[3];           /* shade == 1: finite; the caller normalises it */
+} vghv_mesh_job;
+
+/* Everything is checked (every triangle index against V, every head's bounds against the image) before anything is queued. */
+VGHV_API int vghv_render_meshes(const vghv_mesh_job* job, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

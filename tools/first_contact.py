@@ -8,7 +8,8 @@ check prints PASS / FAIL / SKIPPED with the number behind it, and the exit code 
   1. --trcd / --onnx : load_weights -> weight_manifest_diff (every missing / unexpected / mis-shaped tensor; an .onnx also says whether it was read by name or by graph
                        position and which Conv nodes stayed unbound) -> build_program in every precision.
   2. --pkl           : FLAMELayer from the pickle; the reference's known-answer fixture (yolo_head_training/tests/1.json, committed as tests/golden/fixture_1json.npz):
-                       its 413 parameters through vgh_flame_decode against its vertices_3d (the one full known answer the reference holds; 1e-4).
+                       its 413 parameters through vgh_flame_decode against its vertices_3d (SURVEY 8(c)(ii): the one full known answer the reference holds; 1e-4);
+                       that head, 400 px across, through render_mesh (csrc/mesh_render.hip) with the pickle's own faces against the composition of Sim3DR calls, bit for bit.
   3. --cv2           : the letterbox kernel (csrc/letterbox.hip, OpenCV's 8-bit LANCZOS4 restated) against cv2.resize + copyMakeBorder on seeded images and on --images,
                        bit for bit (detector.py:40-52); the warp of get_aligned_heads (csrc/aligned.hip, OpenCV's 8-bit bilinear warpAffine restated) against
                        cv2.getRotationMatrix2D + cv2.warpAffine, bit for bit (utils.py:93-117); PredictionResult.draw (csrc/draw.hip, OpenCV's rectangle / polylines /
@@ -93,6 +94,21 @@ def main():
             ref = g["vertices_3d"].astype(np.float64)
             err = float(np.abs(v3[: ref.shape[0]] - ref).max()) if v3.shape[0] >= ref.shape[0] else float("inf")
             report("1.json known answer through vgh_flame_decode", err < 1e-4, f"max |vertex - fixture| = {err:.3e} m over {ref.shape[0]} vertices (bar 1e-4)")
+            # the shaded mesh (csrc/mesh_render.hip) with the REAL FLAME faces: the fixture's head scaled to 400 px, against the composition of Sim3DR calls
+            # (tests/shade_ref.py: the reference's own C++ where oracle/_ref has it, its CPU restatement otherwise), bit for bit
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            import shade_ref as sr
+            from head_detector_amd import mesh_render
+
+            faces = np.ascontiguousarray(fl.faces, dtype=np.int32)
+            span = float(np.ptp(v3[:, :2], axis=0).max())
+            head = ((v3 - v3.mean(axis=0)) * (400.0 / span) * np.array([1.0, -1.0, 1.0]) + np.array([256.0, 240.0, 0.0])).astype(np.float32)
+            photo = np.random.default_rng(1).integers(0, 256, (480, 512, 3), dtype=np.uint8)
+            got = mesh_render.render_mesh(photo, [sr.make_head(head)], faces)
+            want = sr.render_mesh(photo, [head], faces, sr.live() is not None)
+            nbad = int((got != want).any(axis=2).sum())
+            report("render_mesh with the FLAME faces (bit for bit)", nbad == 0 and bool((got != photo).any()),
+                   f"{faces.shape[0]} triangles, {int((got != photo).any(axis=2).sum())} painted pixels, {nbad} differing; against {'the reference library' if sr.live() is not None else 'tests/shade_ref.py'}")
         except Exception as e:  # noqa: BLE001
             report("FLAME pickle", False, f"{type(e).__name__}: {e}")
     else:
