@@ -1,4 +1,4 @@
-"""In-tree build of libvgh.so and its companion libvghview.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
+"""In-tree build of libvgh.so and its companions libvghview.so and libvghvis.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
 from __future__ import annotations
 
 import os
@@ -15,6 +15,10 @@ EXPERIMENT_SOURCES = ["stem_ds.hip"]  # measured losers kept for tools/: part of
 LIB_VIEW = os.path.join(HERE, "libvghview.so")
 VIEW_SOURCES = ["aligned.hip", "draw.hip", "mesh_render.hip"]
 VIEW_HEADERS = ["vghv_internal.h"]  # shared by the view library's sources only: a dependency of libvghview.so, not of libvgh.so
+# libvghvis.so (include/vgh_vis.h): head visibility buffers, a library of its own like the view library -- hidden visibility but for its vghvis_* exports
+LIB_VIS = os.path.join(HERE, "libvghvis.so")
+VIS_SOURCES = ["visibility.hip"]
+VIS_HEADERS = []  # visibility.hip shares no header with the other two libraries
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -29,7 +33,7 @@ def _core_needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in VIEW_SOURCES + VIEW_HEADERS] + [os.path.join(HERE, "..", "include", "vgh.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in VIEW_SOURCES + VIEW_HEADERS + VIS_SOURCES + VIS_HEADERS] + [os.path.join(HERE, "..", "include", "vgh.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -41,8 +45,16 @@ def _view_needs_build() -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _vis_needs_build() -> bool:
+    if not os.path.exists(LIB_VIS):
+        return True
+    t = os.path.getmtime(LIB_VIS)
+    deps = [os.path.join(CSRC, f) for f in VIS_SOURCES + VIS_HEADERS] + [os.path.join(HERE, "..", "include", "vgh_vis.h")]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
 def needs_build() -> bool:
-    return _core_needs_build() or _view_needs_build()
+    return _core_needs_build() or _view_needs_build() or _vis_needs_build()
 
 
 LIB_EXP = os.path.join(HERE, "libvgh_exp.so")  # -DVGH_EXPERIMENTS build (work-skipping switches, env-var knobs): tools/ only
@@ -53,6 +65,8 @@ def build_lib(force: bool = False, verbose: bool = True, experiments: bool = Fal
         return _build(os.path.join(HERE, "libvgh_var.so"), [f"-D{d}" for d in variant_defines], "build_var", verbose)
     if experiments:
         return _build(LIB_EXP, ["-DVGH_EXPERIMENTS"], "build_exp", verbose)
+    if force or _vis_needs_build():
+        _build(LIB_VIS, ["-fvisibility=hidden"], "build_vis", verbose, VIS_SOURCES)
     if force or _view_needs_build():
         _build(LIB_VIEW, ["-fvisibility=hidden"], "build_view", verbose, VIEW_SOURCES)
     if force or _core_needs_build():

@@ -7,7 +7,9 @@ reference, user-supplied like the other mesh assets).  ``draw`` paints boxes, th
 with the kernels of csrc/draw.hip (libvghview.so, ``head_detector_amd.draw``) for the methods "full", "bbox", "landmarks" and "points"; it needs
 ``triangles`` (assets/triangles.txt), ``head_indices`` and ``face_indices`` (assets/flame_indices/face.npy) as the method requires.  Its pixel
 rules are OpenCV's as restated in tests/draw_ref.py (parity with cv2 itself is unpinned, like the warp of the aligned crops); "pose" raises
-NotImplementedError instead of drawing something approximately right."""
+NotImplementedError instead of drawing something approximately right.  ``get_visibility`` measures instead of painting: per pixel the head and
+triangle that show, per head the covered and the visible pixels and the visible vertices (csrc/visibility.hip, libvghvis.so,
+``head_detector_amd.visibility``); like ``render_mesh`` it needs ``faces``."""
 from __future__ import annotations
 
 import os
@@ -46,6 +48,17 @@ class PredictionResult:
         from .mesh_render import render_mesh
 
         return render_mesh(self.original_image, self.heads, self._faces, alpha=alpha, color=color, ambient=ambient, diffuse=diffuse, light=light, to_host=to_host)
+
+    def get_visibility(self, occlusion: str = "order", barycentric: bool = False, to_host: bool = True):
+        """A ``visibility.HeadVisibility``: Sim3DR's ``rasterize_triangles`` over every head's mesh (the FLAME model's own triangles, ``faces``), depth = -z
+        like get_pncc and render_mesh.  ``occlusion="order"``: a later head hides an earlier one, as in those pictures (FLAME's weak-perspective z is not
+        calibrated between heads); ``"depth"``: one z-buffer for all heads.  No head's ``vertices_3d`` is modified.  ``to_host=False`` returns GPU tensors."""
+        from .visibility import head_visibility
+
+        shape = tuple(self.original_image.shape)
+        if len(shape) < 2:
+            raise ValueError(f"the image must be [H, W, ...], got {shape}")
+        return head_visibility(self.heads, self._faces, shape[0], shape[1], occlusion=occlusion, barycentric=barycentric, to_host=to_host)
 
     def get_pncc(self):
         """detection_result.py:58-59: PNCC image of all heads (uint8 [H,W,3]); like the reference it negates z of every

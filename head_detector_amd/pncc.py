@@ -2,6 +2,7 @@
 
   rasterize(vertices, triangles, colors, bg=..., reverse=False)   <- head_detector/Sim3DR/Sim3DR.py:17-38 (+ ``alpha``, the C++'s own parameter)
   get_normal(vertices, triangles)                                 <- head_detector/Sim3DR/Sim3DR.py:9-12
+  rasterize_triangles(vertices, triangles, height, width)         <- head_detector/Sim3DR/lib/rasterize.pyx:74-86 (the binding's third function)
   compute_ncc_color_codes(template, subset)                       <- head_detector/pncc_processor.py:40-55
   PNCCProcessor(...)(image, heads)                                <- head_detector/pncc_processor.py:58-73
   refined_head_bbox(vertices)                                     <- head_detector/utils.py:26-35
@@ -10,7 +11,7 @@ The reference ships three mesh assets next to its sources (assets/full_faces.npy
 assets/flame_indices/{head_w_ears,head_indices}.npy).  They are data the user supplies here (``assets_dir`` = the
 reference's ``head_detector/assets`` directory, or the arrays themselves); nothing is bundled.
 All arithmetic runs in libvgh (csrc/raster.hip) and, for ``get_normal`` and ``rasterize(alpha < 1)``, in libvghview (csrc/mesh_render.hip); there is
-no CPU path."""
+no CPU path.  ``rasterize_triangles`` runs in libvghvis (csrc/visibility.hip)."""
 from __future__ import annotations
 
 import os
@@ -103,6 +104,20 @@ def get_normal(vertices, triangles):
     from . import mesh_render
 
     return mesh_render.vertex_normals(vertices, triangles)
+
+
+def rasterize_triangles(vertices, triangles, height: int, width: int):
+    """Sim3DR_Cython.rasterize_triangles for one mesh on fresh buffers -> (depth_buffer float32 [H, W] (-1e8 where nothing shows), triangle_buffer int32
+    [H, W] (-1), barycentric_weight float32 [H, 3 W]): the three 2-D C arrays the binding fills, the weights of pixel (y, x) at [y, 3 x : 3 x + 3]
+    (``.reshape(H, W, 3)``).  Depth is z as given (``z_sign`` = +1).  ``vertices``: NumPy or a GPU tensor.  For all heads of an image at once: ``head_detector_amd.visibility``."""
+    from . import visibility
+
+    on_device = isinstance(vertices, torch.Tensor)  # a GPU tensor is passed through; the three arrays come back as NumPy either way
+    shape = tuple(vertices.shape) if on_device else np.shape(vertices)
+    if len(shape) != 2 or shape[1] != 3:
+        raise ValueError(f"vertices must be [V, 3], got {shape}")
+    res = visibility.rasterize_heads(vertices if on_device else np.asarray(vertices), triangles, height, width, occlusion="order", z_sign=1.0, barycentric=True, to_host=True)
+    return res.depth, res.triangle_index, res.barycentric.reshape(res.depth.shape[0], -1)
 
 
 def compute_ncc_color_codes(template_face: np.ndarray, subset_indexes: Optional[np.ndarray] = None) -> np.ndarray:
