@@ -9,6 +9,7 @@
 
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "vgh_internal.h"
 
@@ -28,8 +29,19 @@ struct vgh_detector {
     int32_t* head_image = nullptr; // [max_batch * keep_k]
     int32_t* ticket = nullptr;     // [1], zero between launches: vgh_nms_select's last-block ticket
     // lazy FLAME gather (r06, vgh_detector_set_lazy_flame): the candidate stage gathers boxes only; the 413-vectors of the SURVIVORS are built by the select from the
-    // prediction buffers (106 MB of candidate vectors per 64 images for ~3 survivors per image otherwise).  flame_pending: a lazy candidate stage is waiting for its select
-    bool lazy_flame = false, flame_pending = false;
+    // prediction buffers (106 MB of candidate vectors per 64 images for ~3 survivors per image otherwise).
+    bool lazy_flame = false;
+    // Where a select finds the 413-vectors of candidate row r (row_src[r], one byte per row of max_batch):
+    //   SRC_NONE   nothing decoded into the row yet, or a lazy decode whose rows were since given up (a shorter lazy decode took its place)
+    //   SRC_EAGER  cand_flame[r] was written together with cand_boxes[r] / cand_scores[r]
+    //   SRC_LAZY   prediction row r of forward generation lazy_gen (vgh_net_generation), through idx[r]; always a prefix [0, lazy_rows) of ONE decode call
+    // A select reads the state and leaves it alone: any number of selects may follow one candidate stage.  It refuses (VGH_ERR_INVALID, nothing queued) rows without a
+    // source, a lazy source whose generation has passed -- a forward has been queued since, the prediction buffers belong to another batch -- and a batch that mixes lazy and
+    // eager rows (the kernel gathers every survivor of a launch the same way, and lazy row r IS prediction row r).
+    enum : uint8_t { SRC_NONE = 0, SRC_EAGER = 1, SRC_LAZY = 2 };
+    std::vector<uint8_t> row_src;
+    int lazy_rows = 0;
+    uint64_t lazy_gen = 0;
     // overlap mode: the select half (NMS .. FLAME decode: small, latency-bound kernels) runs on a detector-owned side stream,
     // concurrently with the network of the NEXT batch on the caller's stream
     bool overlap = false, side_pending = false;
@@ -132,6 +144,7 @@ int vgh_detector_create(vgh_net* net, vgh_flame* flame, const vgh_detect_cfg* cf
         A += cfg->level_h[l] * cfg->level_w[l];
     }
     d->A = A;
+    d->row_src.assign((size_t)cfg->max_batch, vgh_detector::SRC_NONE);
     if (cfg->pre_k > A) {
         delete d;
         vgh_set_error("detector_create: pre_k %d exceeds the %d anchors", cfg->pre_k, A);
@@ -246,7 +259,16 @@ int vgh_detector_decode_candidates(vgh_detector* d, int n, int at, void* stream)
     if ((rc = vgh_gather_candidates(lv, c.n_levels, n, d->A, c.shape_live, c.expr_live, ba, ix, c.pre_k, d->cand_boxes + (size_t)at * c.pre_k * 4,
                                     lazy ? nullptr : d->cand_flame + (size_t)at * c.pre_k * VGH_NUM_FLAME_PARAMS, st)))
         return rc;
-    d->flame_pending = lazy;
+    // the rows' source, once everything above is queued (a failed call leaves the old record: its rows were at most partly rewritten by kernels that never ran)
+    if (lazy) {  // rows [0, n) from the prediction buffers as they are now; lazy rows of an earlier decode behind them have lost their predictions
+        for (int r = n; r < d->lazy_rows; ++r)
+            if (d->row_src[r] == vgh_detector::SRC_LAZY) d->row_src[r] = vgh_detector::SRC_NONE;
+        std::memset(d->row_src.data(), vgh_detector::SRC_LAZY, (size_t)n);
+        d->lazy_rows = n;
+        d->lazy_gen = vgh_net_generation(d->net);
+    } else {
+        std::memset(d->row_src.data() + at, vgh_detector::SRC_EAGER, (size_t)n);
+    }
     if (d->overlap) {  // the next forward may run its backbone / neck now, but must not overwrite the predictions before this point
         VGH_HIP(hipEventRecord(d->ev_cand, d->side));
         if ((rc = vgh_net_set_pred_guard(d->net, d->ev_cand))) return rc;
@@ -291,8 +313,20 @@ static int select_on(vgh_detector* d, int B, float conf_thr, float iou_thr, vgh_
     const int cap_all = B * c.keep_k;
     const int capacity = (o->head_capacity > 0 && o->head_capacity < cap_all) ? o->head_capacity : cap_all;
     int32_t* himg = o->head_image_dev ? o->head_image_dev : d->head_image;
-    const bool lazy = d->flame_pending;
-    d->flame_pending = false;
+    // the source of rows [0, B): checked on the host before anything is queued (see vgh_detector::row_src)
+    int n_lazy = 0, n_none = 0;
+    for (int r = 0; r < B; ++r) {
+        n_lazy += d->row_src[r] == vgh_detector::SRC_LAZY;
+        n_none += d->row_src[r] == vgh_detector::SRC_NONE;
+    }
+    VGH_REQUIRE(n_none == 0, "detector_select: %d of the candidate rows [0,%d) have no valid source (no candidate stage has filled them, or a shorter lazy one replaced theirs)", n_none, B);
+    VGH_REQUIRE(n_lazy == 0 || n_lazy == B,
+                "detector_select: rows [0,%d) mix %d lazily gathered rows with eagerly gathered ones; decode every chunk of such a batch with the lazy FLAME gather off", B, n_lazy);
+    const bool lazy = n_lazy > 0;
+    VGH_REQUIRE(!lazy || d->lazy_gen == vgh_net_generation(d->net),
+                "detector_select: the candidates were gathered lazily from the predictions of forward %llu, but %llu forward(s) have been queued on the net since: the prediction "
+                "buffers no longer hold that batch (queue the select before the next forward, or decode with the lazy FLAME gather off)",
+                (unsigned long long)d->lazy_gen, (unsigned long long)(vgh_net_generation(d->net) - d->lazy_gen));
     VGH_REQUIRE(!lazy || c.keep_k <= 1024, "detector_select: the lazy FLAME gather needs keep_k <= 1024");
     if (c.keep_k <= 1024) {  // r06: NMS + compaction + head list as one launch
         vgh_head_level lv[VGH_MAX_LEVELS];
@@ -308,7 +342,8 @@ static int select_on(vgh_detector* d, int B, float conf_thr, float iou_thr, vgh_
                                  c.n_levels, lazy ? d->idx : nullptr, c.shape_live, c.expr_live, stream)))
             return rc;
         if (lazy && d->overlap && stream == (void*)d->side) {
-            // the select has just read the prediction buffers: the next forward's guard moves behind it (same event, recorded again; the net waits for the latest record)
+            // the select has just read the prediction buffers: the next forward's guard moves behind it (same event, recorded again; the net waits for the latest record).
+            // A forward queued BEFORE this select never saw that record -- which is why select_on refuses a lazy source whose generation has passed.
             VGH_HIP(hipEventRecord(d->ev_cand, d->side));
         }
         if (!want_heads) return VGH_OK;

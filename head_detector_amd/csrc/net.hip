@@ -92,6 +92,9 @@ struct vgh_net {
     bool lane_wait_cycle = false;
     int fuse_b2b = 1;   // vgh_net_set_b2b: the back-to-back pairs found at create time run fused (default) or as their two launches (every intermediate tensor then exists)
     int stem3_ok = -1;  // the stem + stage-1 pair as ONE launch (ds_b2b.hip, "u" tile; u8 images, fuse_b2b == 1): -1 not yet checked (first forward), 0 / 1
+    // forward generation: bumped by every call that (re)writes the prediction buffers -- vgh_net_forward (and with it every chunk of vgh_detector_candidates and the
+    // capture's recording pass), vgh_net_forward_graph, vgh_net_profile.  A detector's lazy FLAME gather remembers the generation it decoded and its select refuses another one
+    uint64_t generation = 0;
     int fuse_stem = 0;  // opt-in (vgh_net_set_fuse_stem): measured r03, the fused kernel saves 1.5 GB of HBM traffic per L b64 forward but no time (EXPERIMENTS.md 8c)
 };
 
@@ -617,6 +620,7 @@ int vgh_net_forward(vgh_net* n, const void* image_dev, int image_fmt, int B, voi
     // the first op of a lane after it makes that lane's stream wait for the event, and every used lane is joined back into
     // the main stream at the end (also valid under stream capture: the graph gets parallel branches).
     hipStream_t main = (hipStream_t)stream;
+    ++n->generation;  // before anything is queued: a forward that fails half-way has touched the prediction buffers too
     if (int rc = ensure_lanes(n, main)) return rc;
     if (n->nsplit > 1 && B > 1) return net_forward_split(n, image_dev, image_fmt, B, main);
     bool pending[vgh_net::kLanes] = {false, false, false, false}, used[vgh_net::kLanes] = {false, false, false, false};
@@ -662,6 +666,7 @@ int vgh_net_profile(vgh_net* n, const void* image_dev, int image_fmt, int B, voi
     VGH_REQUIRE(image_fmt == VGH_IMG_F32_NCHW || image_fmt == VGH_IMG_U8_NHWC, "net_profile: image format %d is not a canvas (VGH_IMG_U8_RAW is letterboxed by vgh_detect)", image_fmt);
     VGH_REQUIRE(B >= 0 && B <= n->max_batch, "net_profile: B=%d exceeds max_batch=%d", B, n->max_batch);
     hipStream_t st = (hipStream_t)stream;
+    ++n->generation;
     if (int rc = ensure_lanes(n, st)) return rc;
     const size_t m = n->ops.size();
     std::vector<hipEvent_t> ev(m + 1);
@@ -723,6 +728,7 @@ int vgh_net_capture(vgh_net* n, const void* image_dev, int image_fmt, int B, voi
 int vgh_net_forward_graph(vgh_net* n, void* stream) {
     VGH_REQUIRE(n && n->graph_exec, "net_forward_graph: call vgh_net_capture first");
     VGH_REQUIRE(!n->pred_guard, "net_forward_graph: a prediction guard event is set (detector overlap mode); use vgh_net_forward");
+    ++n->generation;
     VGH_HIP(hipGraphLaunch(n->graph_exec, (hipStream_t)stream));
     return VGH_OK;
 }
@@ -776,6 +782,7 @@ int vgh_net_b2b_pairs(vgh_net* n) {
     return k;
 }
 
+uint64_t vgh_net_generation(vgh_net* n) { return n ? n->generation : 0; }
 int vgh_net_max_batch(vgh_net* n) { return n ? n->max_batch : 0; }
 int vgh_net_device(vgh_net* n) { return n ? n->device : 0; }
 int vgh_net_image_size(vgh_net* n) { return n ? n->image_size : 0; }

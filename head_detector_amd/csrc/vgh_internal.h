@@ -221,6 +221,9 @@ int vgh_net_lane_streams(vgh_net* n, hipStream_t main, hipStream_t* out);
 extern "C" __attribute__((visibility("hidden"))) int vgh_net_device(vgh_net* n);  // library-internal
 // net.hip, library-internal since r06 (was exported): the first op of the next forwards that writes a prediction buffer waits for `event` (or nullptr) on its stream
 extern "C" __attribute__((visibility("hidden"))) int vgh_net_set_pred_guard(vgh_net* n, void* event);
+// net.hip, library-internal: how many forwards (vgh_net_forward, vgh_net_forward_graph, vgh_net_profile) have been queued on this net -- the prediction buffers hold the
+// results of the latest one.  The detector's lazy FLAME gather is tied to the generation it decoded (detect.hip)
+extern "C" __attribute__((visibility("hidden"))) uint64_t vgh_net_generation(vgh_net* n);
 
 // letterbox.hip: the batched letterbox of VGH_IMG_U8_RAW, owned by a detector (canvas [arena_batch, S, S, 3] + two pinned / device staging slots)
 struct vgh_lb_batch;

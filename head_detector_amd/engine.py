@@ -372,7 +372,10 @@ class VGHeadsEngine:
 
         ``lazy_flame`` (r06, vgh_detector_set_lazy_flame): gather the candidates' BOXES only; the 413-vectors of the survivors are then built by the next ``select`` straight
         from the prediction buffers (the candidate FLAME tensor -- 1.65 MB per image for typically a handful of survivors -- is neither written nor read; ``cand_flame``
-        is stale).  Contract: that ``select`` is queued before the next forward touches the arena.  Same bits in the detections."""
+        is stale).  Same bits in the detections.  Contract, enforced by the library: such a batch can be selected any number of times until the next forward of this engine
+        (``forward_net``, a graph replay, ``forward_candidates``, ``detect``, ``profile_ops``) is queued -- a ``select`` after that raises ``VghError`` instead of reading
+        the next batch's predictions, in overlap mode too; so does a ``select`` over rows that mix lazy rows with a later eager chunk (``at > 0`` always gathers eagerly) or
+        that no candidate stage has filled.  A lazy batch that is never selected is simply replaced by the next candidate stage."""
         self._set_lazy_flame(lazy_flame)
         _lib.check(self.lib.vgh_detector_decode_candidates(self._det, B, at, self._sp()))
 
@@ -507,7 +510,10 @@ class VGHeadsEngine:
                unpad: Optional[torch.Tensor] = None, n_heads_out: Optional[torch.Tensor] = None, slot: Optional[Dict[str, torch.Tensor]] = None) -> Detections:
         """The post-candidate half of ``detect`` for the B images whose candidates are already in place
         (after ``forward_candidates`` / ``forward_net`` + ``candidates``).  In overlap mode it is queued on the detector's side
-        stream: ``join()`` before reading the result.  ``n_heads_out`` [1] int32: where to write the head count."""
+        stream: ``join()`` before reading the result.  ``n_heads_out`` [1] int32: where to write the head count.
+        The candidates stay selectable: ``select`` may be called again with other thresholds (also after ``detect``), eagerly gathered ones even after later forwards;
+        lazily gathered ones until the next forward (see ``candidates``: ``VghError`` afterwards, nothing is queued).  Selects of one engine run on one stream, one after
+        the other (the head list is built behind a ticket the launches share)."""
         o, det = self._detect_out(B, flame, unpad, n_heads_out, slot)
         _lib.check(self.lib.vgh_detector_select(self._det, B, float(confidence_threshold), float(iou_threshold), C.byref(o), self._sp()))
         return det

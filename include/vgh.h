@@ -371,7 +371,8 @@ void vgh_detector_destroy(vgh_detector* d);
 int vgh_detector_candidates(vgh_detector* d, const void* images_dev, int image_fmt, int B, void* stream);
 /* The post-network half of vgh_detector_candidates alone (box/score decode, top-k, gather) for the n images currently in the
  * net's prediction buffers -> candidate rows [at, at+n).  With vgh_net_forward before it, this is what vgh_detector_candidates
- * does per arena-sized chunk; separate so a caller can bracket the network with its own events. */
+ * does per arena-sized chunk; separate so a caller can bracket the network with its own events.  Rows decoded with `at` > 0 are gathered eagerly whatever
+ * vgh_detector_set_lazy_flame says (lazy row r is prediction row r: only a batch that starts at row 0 of one forward can be lazy). */
 int vgh_detector_decode_candidates(vgh_detector* d, int n, int at, void* stream);
 int vgh_detector_candidate_buffers(vgh_detector* d, float** boxes_dev, float** scores_dev, float** flame_dev);
 int vgh_detector_set_flame(vgh_detector* d, vgh_flame* flame);
@@ -387,6 +388,17 @@ int vgh_detector_set_flame(vgh_detector* d, vgh_flame* flame);
 #define VGH_SCRATCH_UNPAD 5
 #define VGH_SCRATCH_CANVAS 6
 void* vgh_detector_scratch(vgh_detector* d, int which);
+/* Selects rows [0, B) of the candidate buffers.  It reads the candidate stage's record of where each row's 413-vector comes from and leaves it alone: any number of
+ * selects (other thresholds, other outputs) may follow one candidate stage.  Refused with VGH_ERR_INVALID -- on the host, before anything is queued -- when
+ *   - a row in [0, B) has no source: no candidate stage has filled it, or a shorter lazy stage has replaced the lazy one it came from;
+ *   - the rows were gathered lazily (vgh_detector_set_lazy_flame) and a forward has been queued on the net since -- vgh_net_forward, vgh_net_forward_graph, vgh_net_profile,
+ *     vgh_detector_candidates, on any stream, overlap mode included: the prediction buffers belong to that forward now.  Eagerly gathered rows own their vectors and
+ *     may be selected after later forwards;
+ *   - rows [0, B) mix lazily and eagerly gathered rows (vgh_detector_decode_candidates with `at` > 0 always gathers eagerly: decode every chunk of such a batch with the
+ *     lazy gather off, as vgh_detector_candidates does).
+ * ONE STREAM AT A TIME: NMS, compaction and the head list are one launch whose last block to finish builds the head list behind a ticket in detector-owned device memory
+ * (zero between launches).  Two selects of one detector that run concurrently on different streams would share that ticket and both head lists would be wrong: selects of
+ * one detector must be ordered on the device (one stream -- in overlap mode the detector's side stream, which the library sees to -- or explicit events). */
 int vgh_detector_select(vgh_detector* d, int B, float conf_thr, float iou_thr, vgh_detect_out* out, void* stream);
 int vgh_detect(vgh_detector* d, const void* images_dev, int image_fmt, int B, float conf_thr, float iou_thr, vgh_detect_out* out, void* stream);
 /* Throughput mode.  With overlap enabled the select half (NMS, compaction, head list, FLAME decode: small latency-bound
@@ -399,8 +411,10 @@ int vgh_detect(vgh_detector* d, const void* images_dev, int image_fmt, int B, fl
 int vgh_detector_set_overlap(vgh_detector* d, int enable);
 /* r06 (additive): LAZY FLAME GATHER.  enable = 1: vgh_detector_decode_candidates / vgh_detector_candidates gather the candidates' boxes only; the next
  * vgh_detector_select builds the 413-vectors of the SURVIVORS straight from the prediction buffers (the [B, pre_k, 413] candidate tensor -- 106 MB per 64 images for a handful of
- * survivors per image -- is neither written nor read: VGH_SCRATCH_CAND_FLAME is stale).  Contract: that select is queued before the next forward overwrites the prediction
- * buffers (vgh_detect does; in overlap mode the prediction guard moves behind the select by itself).  A batch that runs in several arena chunks gathers eagerly whatever the
+ * survivors per image -- is neither written nor read: the candidate FLAME buffer is stale).  Contract, enforced by vgh_detector_select: the select is queued before the next
+ * forward of the net (vgh_detect does; in overlap mode the prediction guard then moves behind the select by itself) -- the candidate stage remembers the net's forward
+ * generation and a select that finds another one fails with VGH_ERR_INVALID instead of reading the next batch's predictions.  Until then the batch may be selected any
+ * number of times; a lazy batch that is never selected is simply replaced by the next candidate stage.  A batch that runs in several arena chunks gathers eagerly whatever the
  * flag says.  The detections are the same bits.  Default 0. */
 int vgh_detector_set_lazy_flame(vgh_detector* d, int enable);
 int vgh_detector_join(vgh_detector* d, void* stream);
