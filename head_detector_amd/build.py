@@ -1,4 +1,4 @@
-"""In-tree build of libvgh.so and its companions libvghview.so and libvghvis.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
+"""In-tree build of libvgh.so and its companions libvghview.so, libvghvis.so and libvghtex.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
 from __future__ import annotations
 
 import os
@@ -19,6 +19,10 @@ VIEW_HEADERS = ["vghv_internal.h"]  # shared by the view library's sources only:
 LIB_VIS = os.path.join(HERE, "libvghvis.so")
 VIS_SOURCES = ["visibility.hip"]
 VIS_HEADERS = []  # visibility.hip shares no header with the other two libraries
+# libvghtex.so (include/vgh_tex.h): head textures (Sim3DR's render_texture), a library of its own like the other two companions -- hidden visibility but for its vghtex_* exports
+LIB_TEX = os.path.join(HERE, "libvghtex.so")
+TEX_SOURCES = ["texture.hip"]
+TEX_HEADERS = []  # texture.hip shares no header with the other libraries
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -33,7 +37,7 @@ def _core_needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in VIEW_SOURCES + VIEW_HEADERS + VIS_SOURCES + VIS_HEADERS] + [os.path.join(HERE, "..", "include", "vgh.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in VIEW_SOURCES + VIEW_HEADERS + VIS_SOURCES + VIS_HEADERS + TEX_SOURCES + TEX_HEADERS] + [os.path.join(HERE, "..", "include", "vgh.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -53,8 +57,16 @@ def _vis_needs_build() -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _tex_needs_build() -> bool:
+    if not os.path.exists(LIB_TEX):
+        return True
+    t = os.path.getmtime(LIB_TEX)
+    deps = [os.path.join(CSRC, f) for f in TEX_SOURCES + TEX_HEADERS] + [os.path.join(HERE, "..", "include", "vgh_tex.h")]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
 def needs_build() -> bool:
-    return _core_needs_build() or _view_needs_build() or _vis_needs_build()
+    return _core_needs_build() or _view_needs_build() or _vis_needs_build() or _tex_needs_build()
 
 
 LIB_EXP = os.path.join(HERE, "libvgh_exp.so")  # -DVGH_EXPERIMENTS build (work-skipping switches, env-var knobs): tools/ only
@@ -65,6 +77,8 @@ def build_lib(force: bool = False, verbose: bool = True, experiments: bool = Fal
         return _build(os.path.join(HERE, "libvgh_var.so"), [f"-D{d}" for d in variant_defines], "build_var", verbose)
     if experiments:
         return _build(LIB_EXP, ["-DVGH_EXPERIMENTS"], "build_exp", verbose)
+    if force or _tex_needs_build():
+        _build(LIB_TEX, ["-fvisibility=hidden"], "build_tex", verbose, TEX_SOURCES)
     if force or _vis_needs_build():
         _build(LIB_VIS, ["-fvisibility=hidden"], "build_vis", verbose, VIS_SOURCES)
     if force or _view_needs_build():

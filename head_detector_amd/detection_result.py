@@ -9,7 +9,10 @@ with the kernels of csrc/draw.hip (libvghview.so, ``head_detector_amd.draw``) fo
 rules are OpenCV's as restated in tests/draw_ref.py (parity with cv2 itself is unpinned, like the warp of the aligned crops); "pose" raises
 NotImplementedError instead of drawing something approximately right.  ``get_visibility`` measures instead of painting: per pixel the head and
 triangle that show, per head the covered and the visible pixels and the visible vertices (csrc/visibility.hip, libvghvis.so,
-``head_detector_amd.visibility``); like ``render_mesh`` it needs ``faces``."""
+``head_detector_amd.visibility``); like ``render_mesh`` it needs ``faces``.  ``get_textures`` and ``render_texture`` move colour between the photograph
+and the heads' surface with Sim3DR's ``render_texture`` (csrc/texture.hip, libvghtex.so, ``head_detector_amd.texture``): the first cuts every head's UV
+texture map out of the image, the second paints textures back onto the heads; both need ``faces`` and a per-vertex UV layout (``texture.cylindrical_uv``
+makes one from the template mesh)."""
 from __future__ import annotations
 
 import os
@@ -59,6 +62,26 @@ class PredictionResult:
         if len(shape) < 2:
             raise ValueError(f"the image must be [H, W, ...], got {shape}")
         return head_visibility(self.heads, self._faces, shape[0], shape[1], occlusion=occlusion, barycentric=barycentric, to_host=to_host)
+
+    def get_textures(self, uv, size=256, mapping: str = "bilinear", visible_only: bool = True, occlusion: str = "order", faces=None, to_host: bool = True):
+        """A ``texture.HeadTextures``: every head's appearance as a UV texture map [n, th, tw, C] cut out of the image (``texture.unwrap_heads`` with the
+        head's ``vertices_3d`` as texture coordinates).  ``uv`` [V, 2] in [0, 1] per vertex, ``size`` the atlas side or (th, tw), ``faces`` a triangle list
+        to use instead of the FLAME model's own (``faces[keep]`` of ``texture.cylindrical_uv``).  ``mask`` marks the texels that were written; with
+        ``visible_only`` their triangle must also own a pixel of that head in ``get_visibility(occlusion)``.  Nothing is modified.  ``to_host=False``
+        returns GPU tensors."""
+        from .texture import head_textures
+
+        return head_textures(self.original_image, self.heads, self._faces if faces is None else faces, uv, size=size, mapping=mapping, visible_only=visible_only,
+                             occlusion=occlusion, to_host=to_host)
+
+    def render_texture(self, textures, uv, mapping: str = "bilinear", occlusion: str = "order", faces=None, to_host: bool = True):
+        """A NEW uint8 [H, W, 3] image: every head painted from its own texture (``textures`` [n, th, tw, C] or a ``HeadTextures``) or from a shared one
+        ([th, tw, C]), uint8 or float, over a copy of the original, depth = -z, composed like ``render_mesh`` (``occlusion="order"``) or through one
+        z-buffer (``"depth"``).  The float32 result is clamped to [0, 255] and truncated to bytes.  Neither the image nor any head is modified.
+        ``to_host=False`` returns a GPU ``torch.uint8`` tensor."""
+        from .texture import paint_heads
+
+        return paint_heads(self.original_image, self.heads, self._faces if faces is None else faces, textures, uv, mapping=mapping, occlusion=occlusion, to_host=to_host)
 
     def get_pncc(self):
         """detection_result.py:58-59: PNCC image of all heads (uint8 [H,W,3]); like the reference it negates z of every
