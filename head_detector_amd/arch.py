@@ -404,6 +404,7 @@ class Program:
             res_buf=res[0].buf if res else -1, res_coff=res[0].coff if res else 0, alpha=float(res[1]) if res else 0.0,
             ksize=k, stride=stride, act=act, shuffle=int(shuffle), w_off=wo, b_off=bo, force_cfg=-1,
             grp_cout=groups[0] if groups else 0, grp_in_stride=groups[1] if groups else 0,
+            out_f32=int(self.bufs[dst.buf]["is_f32"] == FMT_F32),  # (not a vgh_op_desc field: the tile table keys an fp32-output conv apart, engine.tuning_key)
             macs=float(ho * wo_) * float(flops_macs if flops_macs is not None else rows * k * k * cin),
             gemm=(ho * wo_, rp, k * k * cin),
         ))

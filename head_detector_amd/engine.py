@@ -580,27 +580,11 @@ class VGHeadsEngine:
 
     def cfg_names(self) -> List[str]:
         """Tile names ``set_cfg`` indexes: the bf16 table, or the split-precision table for the fp16x3 / bf16x3 modes."""
-        if self.precision in ("fp16x3", "bf16x3", "fp16"):
-            return [self.lib.vgh_conv_split_cfg_name(i).decode() for i in range(self.lib.vgh_conv_split_num_cfgs())]
-        return [self.lib.vgh_conv_cfg_name(i).decode() for i in range(self.lib.vgh_conv_num_cfgs())]
+        return tile_names(self.lib, self.precision)
 
     def cfg_ok(self, cfg: int, op: dict) -> bool:
         """Can tile ``cfg`` of this engine's table run ``op`` (tuning tools)?"""
-        ob = self.program.bufs[op["out_buf"]]
-        al = all(op[k] % 8 == 0 for k in ("out_coff", "out_coff2", "out_split", "cout_store", "res_coff")) and ob["pitch"] % 8 == 0
-        fast = int(ob["is_f32"] != arch.FMT_F32 and al)
-        if self.precision in ("fp16x3", "bf16x3", "fp16"):
-            if self.precision != "fp16" and self.cfg_names()[cfg][0] == "g":
-                return False  # the fp16 ping-pong pseudo-entries of the split table run single-plane fp16 nets only (vgh_conv_split_cfg_ok answers for those); a two-plane
-                # net would fall back to another tile at launch and a tuner would time the fallback under the g name (ADVICE r05)
-            return bool(self.lib.vgh_conv_split_cfg_ok(cfg, op["ksize"], op["stride"], op["cout_pad"], fast, op["shuffle"], op.get("grp_cout", 0)))
-        if not self.lib.vgh_conv_cfg_ok(cfg, op["ksize"], op["stride"], op["cout_pad"], fast, op["shuffle"]):
-            return False
-        if self.cfg_names()[cfg].startswith("t") and (op.get("res_buf", -1) >= 0 or op.get("grp_cout") or op.get("act") == 2):
-            return False  # streaming 1x1 tiles: plain bf16 -> bf16 convs only (the executor would fall back to another tile)
-        if self.cfg_names()[cfg][0] in "ghs" and (op.get("grp_cout") or op.get("act") == 2):
-            return False  # ping-pong 3x3 tiles: dense convs, ReLU / none
-        return not op.get("grp_cout") or op["grp_cout"] % self.lib.vgh_conv_cfg_cout_tile(cfg) == 0
+        return tile_can_run(self.lib, self.program, self.precision, cfg, op)
 
     def load_tuning(self, path: Optional[str] = None) -> int:
         """Apply a measured per-layer tile table: {gemm-shape key: cfg name}. Missing file -> heuristic choice."""
@@ -623,6 +607,34 @@ class VGHeadsEngine:
             else:
                 self.set_cfg(i, -1)  # back to the library's own choice: set_split(2) then set_split(1) must not leave the two-lane table's tile on a shape the one-lane table lacks
         return applied
+
+
+def tile_names(lib, precision: str) -> List[str]:
+    """Tile names of the library's table for this precision: the bf16 table, or the split-precision table for the fp16x3 / bf16x3 / fp16 modes."""
+    if precision in ("fp16x3", "bf16x3", "fp16"):
+        return [lib.vgh_conv_split_cfg_name(i).decode() for i in range(lib.vgh_conv_split_num_cfgs())]
+    return [lib.vgh_conv_cfg_name(i).decode() for i in range(lib.vgh_conv_num_cfgs())]
+
+
+def tile_can_run(lib, program: "arch.Program", precision: str, cfg: int, op: dict) -> bool:
+    """Can tile ``cfg`` of the table of ``precision`` run ``op`` of ``program``?  Host logic only (the loaded library's predicates; no GPU, no engine): what
+    ``VGHeadsEngine.cfg_ok`` answers, and what decides whether ``load_tuning`` applies a table entry or leaves the library's own choice in place."""
+    names = tile_names(lib, precision)
+    ob = program.bufs[op["out_buf"]]
+    al = all(op[k] % 8 == 0 for k in ("out_coff", "out_coff2", "out_split", "cout_store", "res_coff")) and ob["pitch"] % 8 == 0
+    fast = int(ob["is_f32"] != arch.FMT_F32 and al)
+    if precision in ("fp16x3", "bf16x3", "fp16"):
+        if precision != "fp16" and names[cfg][0] == "g":
+            return False  # the fp16 ping-pong pseudo-entries of the split table run single-plane fp16 nets only (vgh_conv_split_cfg_ok answers for those); a two-plane
+            # net would fall back to another tile at launch and a tuner would time the fallback under the g name (ADVICE r05)
+        return bool(lib.vgh_conv_split_cfg_ok(cfg, op["ksize"], op["stride"], op["cout_pad"], fast, op["shuffle"], op.get("grp_cout", 0)))
+    if not lib.vgh_conv_cfg_ok(cfg, op["ksize"], op["stride"], op["cout_pad"], fast, op["shuffle"]):
+        return False
+    if names[cfg].startswith("t") and (op.get("res_buf", -1) >= 0 or op.get("grp_cout") or op.get("act") == 2):
+        return False  # streaming 1x1 tiles: plain bf16 -> bf16 convs only (the executor would fall back to another tile)
+    if names[cfg][0] in "ghs" and (op.get("grp_cout") or op.get("act") == 2):
+        return False  # ping-pong 3x3 tiles: dense convs, ReLU / none
+    return not op.get("grp_cout") or op["grp_cout"] % lib.vgh_conv_cfg_cout_tile(cfg) == 0
 
 
 def calibrate_fp8(variant: str, state_dict: Optional[Dict[str, np.ndarray]], image_size: int, images: torch.Tensor, device: Optional[int] = None, fp8_min_px: int = 40) -> Dict[str, float]:
@@ -655,7 +667,11 @@ CALIB_CHUNK = 8  # images per calibration forward
 LATENCY_MAX_BATCH = 2  # engines built for at most this many images schedule their heads on lane streams (arch.schedule_latency)
 
 
-def tuning_key(op: dict, batch: int, nsplit: int = 1, bucket: Optional[int] = None, res: Optional[bool] = None) -> str:
+def _epilogue_class(op: dict) -> str:
+    return "_f32" if op.get("out_f32") else "_sh" if op.get("shuffle") else ""
+
+
+def tuning_key(op: dict, batch: int, nsplit: int = 1, bucket: Optional[int] = None, res: Optional[bool] = None, cls: Optional[str] = None) -> str:
     m, n, k = op["gemm"]
     if bucket is None:  # b64 (r03): the 20^2 / 40^2 maps of a 32-image batch fill the chip differently from those of 64 images
         bucket = 1 if batch <= 2 else (8 if batch <= 16 else (32 if batch <= 32 else 64))
@@ -663,18 +679,30 @@ def tuning_key(op: dict, batch: int, nsplit: int = 1, bucket: Optional[int] = No
     grp = f"_g{op['grp_cout']}" if op.get("grp_cout") else ""
     # r04: a conv with a residual input has another epilogue (16 more 1-KiB loads per wave through the per-CU path): its own entry, the plain key as fallback
     rs = "_res" if (op.get("res_buf", -1) >= 0 if res is None else res) else ""
-    return f"b{bucket}{lanes}_m{m}_n{n}_k{k}_ks{op['ksize']}_s{op['stride']}{grp}{rs}"
+    # a conv with an fp32 (prediction) output or a pixel-shuffle store runs the plain implicit-GEMM tiles only: the streaming 1x1 tile measured for the plain conv of the same
+    # GEMM shape (the prediction conv of head 1 shares m, n, k with neck2's conv3) cannot run it.  Its own entry, the plain key as fallback
+    cl = _epilogue_class(op) if cls is None else cls
+    return f"b{bucket}{lanes}_m{m}_n{n}_k{k}_ks{op['ksize']}_s{op['stride']}{grp}{rs}{cl}"
 
 
 def tuning_lookup(table: Dict[str, str], op: dict, batch: int, nsplit: int = 1, prefix: str = "") -> Optional[str]:
     """Tile name of the measured table for this op: the key of this batch bucket and lane count first (for batches above 32 then the b32 entry of that
-    lane count: b32 covered every large batch before the b64 bucket existed), then the same without lanes."""
+    lane count: b32 covered every large batch before the b64 bucket existed), then the same without lanes; the entries of the op's own epilogue class
+    (fp32 output, pixel shuffle; residual) before the plain ones."""
     b32 = batch > 32
+    cls = _epilogue_class(op)
     keys = []
-    for r in ((None, False) if op.get("res_buf", -1) >= 0 else (None,)):  # the residual entry first, then the plain one
-        keys += [tuning_key(op, batch, nsplit, res=r)] + ([tuning_key(op, batch, nsplit, bucket=32, res=r)] if b32 else [])  # entries measured with this lane count first
-        keys += [tuning_key(op, batch, res=r)] + ([tuning_key(op, batch, bucket=32, res=r)] if b32 else [])
+    for c in ((None, "") if cls else (None,)):
+        for r in ((None, False) if op.get("res_buf", -1) >= 0 else (None,)):  # the residual entry first, then the plain one
+            keys += [tuning_key(op, batch, nsplit, res=r, cls=c)] + ([tuning_key(op, batch, nsplit, bucket=32, res=r, cls=c)] if b32 else [])  # entries measured with this lane count first
+            keys += [tuning_key(op, batch, res=r, cls=c)] + ([tuning_key(op, batch, bucket=32, res=r, cls=c)] if b32 else [])
     for k in keys:
-        if prefix + k in table:
-            return table[prefix + k]
+        name = table.get(prefix + k)
+        if name is None:
+            continue
+        if cls and not k.endswith(cls) and not prefix and not name[0].isdigit():
+            # a plain key that names a streaming 1x1 / halo-patch / ping-pong tile was measured for the plain conv of this GEMM shape: those families store neither fp32 nor
+            # pixel-shuffled outputs (vgh_conv_cfg_ok), so it is not this op's entry -- load_tuning used to look it up and drop it without a word
+            continue
+        return name
     return None

@@ -4,6 +4,9 @@ fp32 accumulation).  Used (a) on CPU to prove that fold + fusion + concat-by-off
 unfused oracle network, (b) on the GPU box as the per-op checker of the HIP kernels on the engine's own inputs."""
 from __future__ import annotations
 
+import copy
+import functools
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -99,6 +102,148 @@ def run_program(P, image, bf16: bool):
     return bufs
 
 
+def fp16_weights(P, w_all):
+    """Copy of the program's weights as the single-plane fp16 mode stores them: per conv a power-of-two prescale into [512, 1024), rounded to fp16
+    (vgh_pack_conv_weights_split, fmt VGH_FMT_F16), back in real units."""
+    w_all = w_all.copy()
+    for op in P.ops:
+        if op["kind"] != 1:
+            continue
+        sl = slice(op["w_off"], op["w_off"] + op["cout_pad"] * op["ksize"] ** 2 * op["cin"])
+        w = torch.from_numpy(w_all[sl])
+        mx = float(w.abs().max())
+        sc = 2.0 ** (10 - int(np.frexp(mx)[1])) if mx > 0 else 1.0
+        w_all[sl] = ((w * sc).half().float() / sc).numpy()
+    return w_all
+
+
+# ------------------------------------------------------------------------------------------------------
+# per-op checker of a whole forward (tests/test_gpu_tuned_ops.py on the GPU; tests/test_host_logic.py proves on the CPU that it discriminates)
+# ------------------------------------------------------------------------------------------------------
+# |fp32 evaluation - float64 evaluation| at the output of a fused chain, both with bf16 storage: two correct evaluations differ where an intermediate value (stem or
+# downsample output) lands on the other side of a bf16 rounding boundary.  MEASURED on the CPU alone (no kernel involved; `python tests/program_ref.py` prints it; x86-64,
+# torch CPU convolutions, seed-7 weights, two u8 images of seed 640): the chains of L @640 and M @640 (the l64 / m32 programs of tests/test_gpu_tuned_ops.py) below -- the
+# worst is one bf16 ulp of an output in [16, 32).  A chain is held to the single-op tolerance plus TWICE the worst value: either side of the comparison may flip.
+CHAIN_FLOOR_MEASURED = {"vgg_heads_l@640": {"backbone.stage1.blocks.conv1|conv2": 0.015625, "neck.neck2.blocks.conv1|conv2": 0.125},
+                        "vgg_heads_m@640": {"backbone.stage1.blocks.conv1|conv2": 0.015625, "neck.neck2.blocks.conv1|conv2": 0.125}}
+CHAIN_FLOOR = max(v for d in CHAIN_FLOOR_MEASURED.values() for v in d.values())  # 0.125
+
+# absolute + relative tolerance of one fp16x3 conv with O(1) values (tests/test_gpu_split.py TOL[FMT_F16X2]); scaled by max(1, max|e|) of the op's output
+F16X3_TOL = (2e-5, 1e-5)
+
+
+def own_channels(P, op):
+    """(buffer, [(first channel, count), ...]): the channels of the arena this op writes."""
+    if op["kind"] == 2:
+        return op["in_buf"], [(op["in_coff"] + op["cin"], 3 * op["cin"])]
+    if op["kind"] == 0:
+        return op["out_buf"], [(op["out_coff"], op["cout_store"])]
+    store = op["cout_store"] if not op["shuffle"] else op["cout_pad"] // 4
+    split = min(op["out_split"], store)
+    return op["out_buf"], [(op["out_coff"], split)] + ([(op["out_coff2"], store - split)] if store > split else [])
+
+
+def seg(P, op, t):
+    """The op's own channels of its output buffer `t`, concatenated (a CSP concat buffer: other ops write the rest of it)."""
+    return torch.cat([t[..., c0 : c0 + n] for c0, n in own_channels(P, op)[1]], -1)
+
+
+def fused_chains(P, stem_fused: bool):
+    """Op-index chains the engine's default mode runs as ONE launch each: every arch.b2b_pairs pair (i, i + 1); the stem in front of the pair that reads its tensor when the
+    engine fuses it (u8 images, VGHeadsEngine.stem_fused).  The tensors between the ops of a chain are never written."""
+    from head_detector_amd import arch
+
+    out = []
+    for i in arch.b2b_pairs(P):
+        ch = [i, i + 1]
+        if stem_fused and i > 0 and P.ops[i - 1]["kind"] == 0 and P.ops[i]["in_buf"] == P.ops[i - 1]["out_buf"]:
+            ch = [i - 1] + ch
+        out.append(ch)
+    return out
+
+
+def run_chain(P, chain, got, image, w_all, b_all, f64: bool = False):
+    """Reference of a fused chain on the inputs of its first op: every op in turn, each intermediate tensor rounded to bf16 (run_op's storage); returns the last op's output buffer."""
+    exp = list(got)
+    for i in chain:
+        ob = P.ops[i]["out_buf"]
+        exp[ob] = torch.zeros_like(got[ob]) if i != chain[-1] else got[ob].clone()
+    for i in chain:
+        run_op(P, P.ops[i], exp, image, True, w_all, b_all, f64=f64)
+    return exp[P.ops[chain[-1]]["out_buf"]]
+
+
+def op_tolerance(mode: str, is_f32: bool, e, chained: bool = False):
+    """The project's per-op tolerances (test_network_every_op, test_fp16_network_every_op, test_gpu_split.TOL) for an expected tensor `e` (the op's own channels)."""
+    if mode == "bf16":
+        tol = (2e-3 + 1e-4 * e.abs()) if is_f32 else (2e-2 + 1.0 / 64 * e.abs())  # bf16: 2 ulps (accumulation order can cross a rounding boundary)
+        return tol + 2.0 * CHAIN_FLOOR if chained else tol
+    assert not chained, "only bf16 programs have fused chains"
+    if mode == "fp16":
+        return (2e-3 + 2e-4 * e.abs()) if is_f32 else (1e-3 + 1.0 / 1024 * e.abs())  # exact operands: one fp16 ulp + accumulation-order slack
+    if mode == "fp16x3":
+        atol, rtol = F16X3_TOL
+        return atol * max(1.0, float(e.abs().max())) + rtol * e.abs()
+    raise ValueError(mode)
+
+
+def check_ops(P, got, image, probes, mode: str = "bf16", chains=(), tiles=None, w_all=None, b_all=None):
+    """Every op of kind 0 / 1 / 2 of a forward against run_op on the forward's OWN inputs of that op (no error accumulates across layers).
+    got[b]: float32 CPU tensor [len(probes), h, w, pitch] of buffer b for the probe images; image: the probe images (u8 NHWC / f32 NCHW); probes: their indices in the
+    batch (for the messages).  mode: "bf16" (bf16-emulating fp32 reference), "fp16" (float64 reference on the prescaled fp16 weights: pass fp16_weights as w_all),
+    "fp16x3" (float64 reference).  chains (fused_chains): the ops of a chain are checked as one reference chain at the last op's output, and the tensors between them must
+    be all zero (never written).  tiles {op index: tile name}: for the messages.
+    Returns dict(single=ops checked singly, chained=ops inside chains, failures=[(op name, message)]); nothing is raised for a mismatch."""
+    if w_all is None:
+        w_all, b_all = P.arrays()
+    tiles = tiles or {}
+    f64 = mode != "bf16"
+    in_chain = {i: ch for ch in chains for i in ch}
+    rep = dict(single=0, chained=0, failures=[])
+
+    def compare(op_idx, names, a_buf, e_buf):
+        op = P.ops[op_idx]
+        ob, _ = own_channels(P, op)
+        a, e = seg(P, op, a_buf), seg(P, op, e_buf)
+        tol = op_tolerance(mode, P.bufs[ob]["is_f32"] == 1, e, chained=len(names) > 1)
+        err = (a - e).abs()
+        bad = ~(err <= tol)  # (a NaN is a mismatch)
+        if not bool(bad.any()):
+            return
+        idx = bad.nonzero()
+        worst = int((torch.nan_to_num(err, nan=float("inf")) * bad).flatten().argmax())
+        key = "m%d_n%d_k%d_ks%d_s%d" % (*op["gemm"], op["ksize"], op["stride"]) + ("_res" if op.get("res_buf", -1) >= 0 else "") if op["kind"] == 1 else f"kind{op['kind']}"
+        tile = "|".join(str(tiles.get(i, "library's choice")) for i in (in_chain.get(op_idx) or [op_idx]))
+        for p in sorted(set(idx[:, 0].tolist())):
+            sel = idx[idx[:, 0] == p]
+            pix = (sel[:, 1] * e.shape[2] + sel[:, 2]) % 32
+            rep["failures"].append((names[-1], f"op {' -> '.join(names)} tile {tile} gemm {key} map {e.shape[1]}x{e.shape[2]} probe image {probes[p]}: {len(sel)}/{e[p].numel()} mismatches; "
+                                    f"worst of the op got {float(a.flatten()[worst])} want {float(e.flatten()[worst])} at {[int(v) for v in np.unravel_index(worst, tuple(e.shape))]}; "
+                                    f"first {sel[:4, 1:].tolist()}; pixel%32 hist {torch.bincount(pix, minlength=32).tolist()}; chan%32 hist {torch.bincount(sel[:, 3] % 32, minlength=32).tolist()}"))
+
+    for i, op in enumerate(P.ops):
+        if op["kind"] == 3:
+            continue
+        ch = in_chain.get(i)
+        if ch is not None:
+            rep["chained"] += 1
+            if i != ch[-1]:
+                ob = op["out_buf"]
+                if float(got[ob].abs().max()) != 0.0:
+                    rep["failures"].append((op["name"], f"op {op['name']}: its output tensor lies inside a fused chain and must never be written, but holds max |x| = {float(got[ob].abs().max())}"))
+                continue
+            e_buf = run_chain(P, ch, got, image, w_all, b_all, f64=f64)
+            compare(i, [P.ops[j]["name"] for j in ch], got[op["out_buf"]], e_buf)
+            continue
+        rep["single"] += 1
+        ob, _ = own_channels(P, op)
+        exp = list(got)
+        exp[ob] = got[ob].clone()
+        run_op(P, op, exp, image, mode == "bf16", w_all, b_all, f64=f64)
+        compare(i, [op["name"]], got[ob], exp[ob])
+    return rep
+
+
 def head_outputs(P, bufs):
     """per level: (reg [B,68,H,W], cls [B,1,H,W], raw branch dict) as NCHW torch tensors (oracle format)."""
     out = []
@@ -110,3 +255,62 @@ def head_outputs(P, bufs):
                    trans=t[:, o + S + E + 9 : o + S + E + 12], scale=t[:, o + S + E + 12 : o + S + E + 13])
         out.append((t[:, :68], t[:, 68:69], raw))
     return out
+
+
+# the benchmarked workloads whose tuned tile choices are checked op by op: id -> (variant, image size, max_batch, lanes, precision).  The lane counts are bench.py's: its
+# run_workload sets --split (default 2) for every timed workload, its one_image_latency builds max_batch = 1 engines and never splits.
+TUNED_CASES = {
+    "l64": ("vgg_heads_l", 640, 64, 2, "bf16"),  # the benchmark line
+    "m32": ("vgg_heads_m", 640, 32, 2, "bf16"),
+    "l8": ("vgg_heads_l", 640, 8, 2, "bf16"),
+    "l1": ("vgg_heads_l", 640, 1, 1, "bf16"),  # latency lanes
+    "m1": ("vgg_heads_m", 640, 1, 1, "bf16"),
+    "l16_1280": ("vgg_heads_l", 1280, 16, 2, "bf16"),
+    "l256_1280": ("vgg_heads_l", 1280, 256, 2, "bf16"),  # runs arena_batch (27) images per chunk
+    "l64_fp16": ("vgg_heads_l", 640, 64, 2, "fp16"),
+    "l32_fp16x3": ("vgg_heads_l", 640, 32, 2, "fp16x3"),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def _built_program(variant, S, precision, seed):
+    from head_detector_amd import arch
+
+    return arch.build_program(variant, arch.random_state_dict(variant, seed), S, precision)
+
+
+def case_program(cid: str, seed: int = 7):
+    """The op program VGHeadsEngine(variant, image_size=S, max_batch=MB, seed=seed, precision=prec) runs for a TUNED_CASES id, built on the host (no GPU, no library)."""
+    from head_detector_amd import arch
+    from head_detector_amd.engine import LATENCY_MAX_BATCH
+
+    variant, S, MB, _, prec = TUNED_CASES[cid]
+    P = copy.copy(_built_program(variant, S, prec, seed))
+    P.ops = [dict(op) for op in P.ops]
+    return arch.schedule_latency(P) if MB <= LATENCY_MAX_BATCH else P
+
+
+def chain_floor(P, image):
+    """max |fp32 - float64| evaluation of every fused chain of P at the chain's output (bf16 storage in both), on the reference's own forward of `image`: {last op name: value}."""
+    w_all, b_all = P.arrays()
+    got = run_program(P, image, True)
+    out = {}
+    for ch in fused_chains(P, image.dtype == torch.uint8):
+        last = P.ops[ch[-1]]
+        a = run_chain(P, ch, got, image, w_all, b_all, f64=False)
+        b = run_chain(P, ch, got, image, w_all, b_all, f64=True)
+        out[last["name"]] = float((seg(P, last, a) - seg(P, last, b)).abs().max())
+    return out
+
+
+if __name__ == "__main__":  # python tests/program_ref.py: re-measures CHAIN_FLOOR_MEASURED (CPU only)
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from head_detector_amd import arch
+
+    for variant in ("vgg_heads_l", "vgg_heads_m"):
+        Q = arch.build_program(variant, arch.random_state_dict(variant, 7), 640)
+        img = torch.randint(0, 256, (2, 640, 640, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(640))
+        print(variant, chain_floor(Q, img))

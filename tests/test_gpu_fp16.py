@@ -175,15 +175,7 @@ def test_fp16_network_every_op(gpu_lib, variant, S, B):
     eng.forward_net(x.to(_dev()))
     got = [eng.buffer(i, B).float().cpu() for i in range(len(P.bufs))]
     w_all, b_all = P.arrays()
-    w_all = w_all.copy()
-    for op in P.ops:  # the weights as the library stores them: per-op power-of-two prescale into [512, 1024), rounded to fp16 (vgh_pack_conv_weights_split, fmt VGH_FMT_F16)
-        if op["kind"] != 1:
-            continue
-        sl = slice(op["w_off"], op["w_off"] + op["cout_pad"] * op["ksize"] ** 2 * op["cin"])
-        w = torch.from_numpy(w_all[sl])
-        mx = float(w.abs().max())
-        sc = 2.0 ** (10 - int(np.frexp(mx)[1])) if mx > 0 else 1.0
-        w_all[sl] = ((w * sc).half().float() / sc).numpy()
+    w_all = pr.fp16_weights(P, w_all)  # the weights as the library stores them: per-op power-of-two prescale into [512, 1024), rounded to fp16 (vgh_pack_conv_weights_split, fmt VGH_FMT_F16)
     for op in P.ops:
         if op["kind"] == 3:
             continue
