@@ -1132,7 +1132,7 @@ __global__ __launch_bounds__((3 * VG + NPW + NHL) * 64) void flame_c3_kernel(Ver
 #pragma unroll
             for (int i = 0; i < NB_; ++i) {
                 const int e = e0 + i * KPI + ks;
-                t[i] = src[kof_e(min(e, nlive - 1))];
+                t[i] = src[kof_e(max(min(e, nlive - 1), 0))];  // (no live coefficient at all, shape_live = expr_live = 0: element 0 -- a valid, unused address, not src[-1])
             }
         };
         auto stage_write = [&](const float (&t)[NB_], int e0) {

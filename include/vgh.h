@@ -292,7 +292,9 @@ void vgh_flame_destroy(vgh_flame* f);
  *                      (x - pad_x, y - pad_y, z) / scale_factor with unpad_dev [n,3] = (pad_x,pad_y,scale)
  * shape_live / expr_live: number of leading shape / expression coefficients that can be non-zero
  * (300/100 = no assumption). Coefficients beyond them MUST be exactly 0 (the detector zero-pads them,
- * yolo_head_dfl_head.py:170-182); skipping them is then bit-exact. */
+ * yolo_head_dfl_head.py:170-182); skipping them is then bit-exact.
+ * A head's outputs depend on its own row only: a NaN or Inf in one head's parameters changes no bit of any other head.  That head's own values are
+ * not those of the reference for a NaN scale: fmaxf(NaN, 1e-8) is 1e-8, torch.clamp(NaN, 1e-8) is NaN. */
 int vgh_flame_decode(vgh_flame* f, const float* params_dev, int n, int shape_live, int expr_live, const float* unpad_dev, float* verts_dev,
                      float* rot_dev, float* proj_dev, void* stream);
 
