@@ -1,4 +1,4 @@
-"""In-tree build of libvgh.so and its companions libvghview.so, libvghvis.so and libvghtex.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
+"""In-tree build of libvgh.so and its companions libvghview.so, libvghvis.so, libvghtex.so and libvgheval.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
 from __future__ import annotations
 
 import os
@@ -23,6 +23,10 @@ VIS_HEADERS = []  # visibility.hip shares no header with the other two libraries
 LIB_TEX = os.path.join(HERE, "libvghtex.so")
 TEX_SOURCES = ["texture.hip"]
 TEX_HEADERS = []  # texture.hip shares no header with the other libraries
+# libvgheval.so (include/vgh_eval.h): mesh benchmark metrics (Z_n, chamfer), a library of its own like the other companions -- hidden visibility but for its vghev_* exports
+LIB_EVAL = os.path.join(HERE, "libvgheval.so")
+EVAL_SOURCES = ["mesh_metrics.hip"]
+EVAL_HEADERS = []  # mesh_metrics.hip shares no header with the other libraries
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -37,7 +41,7 @@ def _core_needs_build() -> bool:
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in VIEW_SOURCES + VIEW_HEADERS + VIS_SOURCES + VIS_HEADERS + TEX_SOURCES + TEX_HEADERS] + [os.path.join(HERE, "..", "include", "vgh.h")]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in VIEW_SOURCES + VIEW_HEADERS + VIS_SOURCES + VIS_HEADERS + TEX_SOURCES + TEX_HEADERS + EVAL_SOURCES + EVAL_HEADERS] + [os.path.join(HERE, "..", "include", "vgh.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -65,8 +69,16 @@ def _tex_needs_build() -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+def _eval_needs_build() -> bool:
+    if not os.path.exists(LIB_EVAL):
+        return True
+    t = os.path.getmtime(LIB_EVAL)
+    deps = [os.path.join(CSRC, f) for f in EVAL_SOURCES + EVAL_HEADERS] + [os.path.join(HERE, "..", "include", "vgh_eval.h")]
+    return any(os.path.getmtime(d) > t for d in deps)
+
+
 def needs_build() -> bool:
-    return _core_needs_build() or _view_needs_build() or _vis_needs_build() or _tex_needs_build()
+    return _core_needs_build() or _view_needs_build() or _vis_needs_build() or _tex_needs_build() or _eval_needs_build()
 
 
 LIB_EXP = os.path.join(HERE, "libvgh_exp.so")  # -DVGH_EXPERIMENTS build (work-skipping switches, env-var knobs): tools/ only
@@ -77,6 +89,8 @@ def build_lib(force: bool = False, verbose: bool = True, experiments: bool = Fal
         return _build(os.path.join(HERE, "libvgh_var.so"), [f"-D{d}" for d in variant_defines], "build_var", verbose)
     if experiments:
         return _build(LIB_EXP, ["-DVGH_EXPERIMENTS"], "build_exp", verbose)
+    if force or _eval_needs_build():  # float64 distances in a stated operation order: no contraction into fused multiply-adds anywhere in this library
+        _build(LIB_EVAL, ["-fvisibility=hidden", "-ffp-contract=off"], "build_eval", verbose, EVAL_SOURCES)
     if force or _tex_needs_build():
         _build(LIB_TEX, ["-fvisibility=hidden"], "build_tex", verbose, TEX_SOURCES)
     if force or _vis_needs_build():

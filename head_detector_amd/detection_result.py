@@ -12,7 +12,8 @@ triangle that show, per head the covered and the visible pixels and the visible 
 ``head_detector_amd.visibility``); like ``render_mesh`` it needs ``faces``.  ``get_textures`` and ``render_texture`` move colour between the photograph
 and the heads' surface with Sim3DR's ``render_texture`` (csrc/texture.hip, libvghtex.so, ``head_detector_amd.texture``): the first cuts every head's UV
 texture map out of the image, the second paints textures back onto the heads; both need ``faces`` and a per-vertex UV layout (``texture.cylindrical_uv``
-makes one from the template mesh)."""
+makes one from the template mesh).  ``compare_meshes`` judges the heads against ground-truth meshes with the reference's benchmark metrics (Z_n, chamfer;
+csrc/mesh_metrics.hip, libvgheval.so, ``head_detector_amd.mesh_metrics``)."""
 from __future__ import annotations
 
 import os
@@ -82,6 +83,19 @@ class PredictionResult:
         from .texture import paint_heads
 
         return paint_heads(self.original_image, self.heads, self._faces if faces is None else faces, textures, uv, mapping=mapping, occlusion=occlusion, to_host=to_host)
+
+    def compare_meshes(self, gt_vertices, subset=None, top_k: int = 5, neighbours: str = "reference", to_host: bool = True, *, gt_landmarks7=None,
+                       pred_landmarks7=None, chamfer_subset=None):
+        """A ``mesh_metrics.HeadMeshMetrics``: every head's ``vertices_3d`` against its ground-truth mesh ``gt_vertices`` [n, V, 3] (the same topology, in the
+        heads' order).  ``z_n`` is the reference's ``calc_zn`` on the vertices ``subset`` (its head_indices; default: all), per head, with ``neighbours`` =
+        "reference" (the source as written) or "nearest" (``mesh_metrics`` states both); the source's caller negates the ground truth first
+        (evaluate_dad.py:294), which is left to the caller here too.  With ``gt_landmarks7`` and ``pred_landmarks7`` [n, 7, 3] ``chamfer`` is filled as
+        well (``mesh_metrics.chamfer_to_gt``, ``chamfer_subset`` = the source's face.npy).  No head's ``vertices_3d`` is modified.  ``to_host=False``
+        returns GPU tensors."""
+        from .mesh_metrics import compare_heads
+
+        return compare_heads(self.heads, gt_vertices, subset=subset, top_k=top_k, neighbours=neighbours, gt_landmarks7=gt_landmarks7,
+                             pred_landmarks7=pred_landmarks7, chamfer_subset=chamfer_subset, to_host=to_host)
 
     def get_pncc(self):
         """detection_result.py:58-59: PNCC image of all heads (uint8 [H,W,3]); like the reference it negates z of every
