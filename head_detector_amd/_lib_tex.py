@@ -6,7 +6,8 @@ import ctypes as C
 import os
 from typing import Optional
 
-from ._lib import VghError
+from ._companion import load_library, raise_for
+from ._lib import VghError  # noqa: F401 (callers name it through this module)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libvghtex.so")
@@ -42,27 +43,11 @@ _lib: Optional[C.CDLL] = None
 def load() -> C.CDLL:
     """Load libvghtex.so and bind every declared symbol. Raises VghError if the library is absent."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise VghError(f"{LIB_PATH} not found: the HIP extension is not built. Run `python -m head_detector_amd.build` (needs hipcc). "
-                       "There is no CPU fallback in this package.")
-    try:
-        lib = C.CDLL(LIB_PATH)
-    except OSError as e:
-        raise VghError(f"failed to load {LIB_PATH}: {e}") from e
-    for name, (res, args) in SYMBOLS.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise VghError(f"{LIB_PATH} does not export {name} (stale build?)") from e
-        fn.restype = res
-        fn.argtypes = args
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = load_library(LIB_PATH, SYMBOLS)
+    return _lib
 
 
 def check(rc: int) -> None:
     if rc != 0:
-        msg = load().vghtex_last_error().decode("utf-8", "replace")
-        raise VghError(f"libvghtex error {rc}: {msg}")
+        raise_for(rc, "libvghtex", load().vghtex_last_error)

@@ -5,28 +5,34 @@ import os
 import subprocess
 import sys
 import time
+from typing import NamedTuple
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvgh.so")
 SOURCES = ["conv_igemm.hip", "conv_patch.hip", "conv_rings.hip", "conv_pp.hip", "ds_b2b.hip", "conv_split.hip", "conv_f32.hip", "stem_pool.hip", "postproc.hip", "flame.hip", "net.hip", "detect.hip", "raster.hip", "letterbox.hip", "ctx.hip", "streams.hip"]
 EXPERIMENT_SOURCES = ["stem_ds.hip"]  # measured losers kept for tools/: part of libvgh_exp.so (-DVGH_EXPERIMENTS) only
-# libvghview.so (include/vgh_view.h): result-side image helpers, a library of its own -- never linked into libvgh.so, hidden visibility but for its vghv_* exports
-LIB_VIEW = os.path.join(HERE, "libvghview.so")
-VIEW_SOURCES = ["aligned.hip", "draw.hip", "mesh_render.hip"]
-VIEW_HEADERS = ["vghv_internal.h"]  # shared by the view library's sources only: a dependency of libvghview.so, not of libvgh.so
-# libvghvis.so (include/vgh_vis.h): head visibility buffers, a library of its own like the view library -- hidden visibility but for its vghvis_* exports
-LIB_VIS = os.path.join(HERE, "libvghvis.so")
-VIS_SOURCES = ["visibility.hip"]
-VIS_HEADERS = []  # visibility.hip shares no header with the other two libraries
-# libvghtex.so (include/vgh_tex.h): head textures (Sim3DR's render_texture), a library of its own like the other two companions -- hidden visibility but for its vghtex_* exports
-LIB_TEX = os.path.join(HERE, "libvghtex.so")
-TEX_SOURCES = ["texture.hip"]
-TEX_HEADERS = []  # texture.hip shares no header with the other libraries
-# libvgheval.so (include/vgh_eval.h): mesh benchmark metrics (Z_n, chamfer), a library of its own like the other companions -- hidden visibility but for its vghev_* exports
-LIB_EVAL = os.path.join(HERE, "libvgheval.so")
-EVAL_SOURCES = ["mesh_metrics.hip"]
-EVAL_HEADERS = []  # mesh_metrics.hip shares no header with the other libraries
+
+
+class Companion(NamedTuple):
+    """A library of its own: never linked into libvgh.so or into another companion, hidden visibility but for the exports of its public header."""
+    lib: str  # file name, next to this file
+    sources: list
+    headers: list  # private headers under csrc/
+    public: str  # under include/
+    flags: list  # beyond FLAGS and -fvisibility=hidden
+    objdir: str
+
+
+RASTER_HEADERS = ["tile_fold.h"]  # the tile-major triangle fold: header-only, compiled into each of the three libraries that rasterise
+COMPANIONS = [  # built in this order, before the core
+    # mesh benchmark metrics (Z_n, chamfer): float64 distances in a stated operation order, so no contraction into fused multiply-adds anywhere in this library
+    Companion("libvgheval.so", ["mesh_metrics.hip"], [], "vgh_eval.h", ["-ffp-contract=off"], "build_eval"),
+    Companion("libvghtex.so", ["texture.hip"], RASTER_HEADERS, "vgh_tex.h", [], "build_tex"),  # head textures (Sim3DR's render_texture)
+    Companion("libvghvis.so", ["visibility.hip"], RASTER_HEADERS, "vgh_vis.h", [], "build_vis"),  # head visibility buffers
+    # result-side image helpers; vghv_internal.h is what its three sources share
+    Companion("libvghview.so", ["aligned.hip", "draw.hip", "mesh_render.hip"], ["vghv_internal.h"] + RASTER_HEADERS, "vgh_view.h", [], "build_view"),
+]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -37,48 +43,21 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found")
 
 
-def _core_needs_build() -> bool:
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in VIEW_SOURCES + VIEW_HEADERS + VIS_SOURCES + VIS_HEADERS + TEX_SOURCES + TEX_HEADERS + EVAL_SOURCES + EVAL_HEADERS] + [os.path.join(HERE, "..", "include", "vgh.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+def _stale(lib: str, deps) -> bool:
+    return not os.path.exists(lib) or any(os.path.getmtime(d) > os.path.getmtime(lib) for d in deps)
 
 
-def _view_needs_build() -> bool:
-    if not os.path.exists(LIB_VIEW):
-        return True
-    t = os.path.getmtime(LIB_VIEW)
-    deps = [os.path.join(CSRC, f) for f in VIEW_SOURCES + VIEW_HEADERS] + [os.path.join(HERE, "..", "include", "vgh_view.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+def _core_needs_build() -> bool:  # everything in csrc/ that no companion claims
+    claimed = {f for c in COMPANIONS for f in c.sources + c.headers}
+    return _stale(LIB, [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in claimed] + [os.path.join(HERE, "..", "include", "vgh.h")])
 
 
-def _vis_needs_build() -> bool:
-    if not os.path.exists(LIB_VIS):
-        return True
-    t = os.path.getmtime(LIB_VIS)
-    deps = [os.path.join(CSRC, f) for f in VIS_SOURCES + VIS_HEADERS] + [os.path.join(HERE, "..", "include", "vgh_vis.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
-def _tex_needs_build() -> bool:
-    if not os.path.exists(LIB_TEX):
-        return True
-    t = os.path.getmtime(LIB_TEX)
-    deps = [os.path.join(CSRC, f) for f in TEX_SOURCES + TEX_HEADERS] + [os.path.join(HERE, "..", "include", "vgh_tex.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
-
-
-def _eval_needs_build() -> bool:
-    if not os.path.exists(LIB_EVAL):
-        return True
-    t = os.path.getmtime(LIB_EVAL)
-    deps = [os.path.join(CSRC, f) for f in EVAL_SOURCES + EVAL_HEADERS] + [os.path.join(HERE, "..", "include", "vgh_eval.h")]
-    return any(os.path.getmtime(d) > t for d in deps)
+def _needs_build(c: Companion) -> bool:
+    return _stale(os.path.join(HERE, c.lib), [os.path.join(CSRC, f) for f in c.sources + c.headers] + [os.path.join(HERE, "..", "include", c.public)])
 
 
 def needs_build() -> bool:
-    return _core_needs_build() or _view_needs_build() or _vis_needs_build() or _tex_needs_build() or _eval_needs_build()
+    return _core_needs_build() or any(_needs_build(c) for c in COMPANIONS)
 
 
 LIB_EXP = os.path.join(HERE, "libvgh_exp.so")  # -DVGH_EXPERIMENTS build (work-skipping switches, env-var knobs): tools/ only
@@ -89,14 +68,9 @@ def build_lib(force: bool = False, verbose: bool = True, experiments: bool = Fal
         return _build(os.path.join(HERE, "libvgh_var.so"), [f"-D{d}" for d in variant_defines], "build_var", verbose)
     if experiments:
         return _build(LIB_EXP, ["-DVGH_EXPERIMENTS"], "build_exp", verbose)
-    if force or _eval_needs_build():  # float64 distances in a stated operation order: no contraction into fused multiply-adds anywhere in this library
-        _build(LIB_EVAL, ["-fvisibility=hidden", "-ffp-contract=off"], "build_eval", verbose, EVAL_SOURCES)
-    if force or _tex_needs_build():
-        _build(LIB_TEX, ["-fvisibility=hidden"], "build_tex", verbose, TEX_SOURCES)
-    if force or _vis_needs_build():
-        _build(LIB_VIS, ["-fvisibility=hidden"], "build_vis", verbose, VIS_SOURCES)
-    if force or _view_needs_build():
-        _build(LIB_VIEW, ["-fvisibility=hidden"], "build_view", verbose, VIEW_SOURCES)
+    for c in COMPANIONS:
+        if force or _needs_build(c):
+            _build(os.path.join(HERE, c.lib), ["-fvisibility=hidden", *c.flags], c.objdir, verbose, c.sources)
     if force or _core_needs_build():
         _build(LIB, [], "build", verbose)
     return LIB

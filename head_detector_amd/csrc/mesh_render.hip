@@ -9,13 +9,8 @@
 // BLENDED RASTERISER (`_rasterize`, :219-293).  With alpha < 1 a pixel is blended once for EVERY triangle that beats the running depth, in
 // triangle order, and truncated to a byte each time, so the winner alone does not determine the byte: csrc/raster.hip's "atomic max, then
 // resolve" cannot express it.  Per pixel the result is a fold over heads (in order, each with a fresh depth) and over the head's
-// triangles in index order.  Tile-major:
-//   boxes    one lane per (head, triangle): the triangle's clamped integer bounding box as 4 x int16 (8 B a triangle for the scans below)
-//   tiles    one 256-lane workgroup per 16 x 16 image tile that some head touches (the host builds "tile -> heads in order" from the
-//            per-head pixel bounds); a lane owns one pixel and keeps its bytes and depth in registers.  For every head of the tile the
-//            workgroup scans the head's boxes 256 at a time, compacts the ones that overlap the tile IN INDEX ORDER into LDS (ballot +
-//            prefix) together with their pixel-independent set-up, and every lane then walks that list serially with exactly the
-//            reference's arithmetic.  One write per pixel at the end.  Deterministic, no atomics, launches independent of the head count.
+// triangles in index order: the tile-major scheme of csrc/tile_fold.h (boxes, then tiles), with the pixel's bytes and depth in a lane's
+// registers and one write per pixel at the end.
 // All arithmetic is IEEE float32 in the reference's operation order (contraction off, true division, correctly rounded sqrt): normals
 // and images are bit-identical to the reference's own C++ (tests/test_gpu_shaded_mesh.py).
 #include <string.h>
@@ -25,14 +20,15 @@
 #include <vector>
 
 #include "vghv_internal.h"
+#define TILE_FOLD_SET_ERROR vghv::set_error  // one message for all of libvghview.so (csrc/aligned.hip)
+#include "tile_fold.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-using namespace vghv;
-
-constexpr int TILE = 16;  // 16 x 16 pixels = the 256 lanes of a workgroup
+using namespace tile_fold;
+static_assert(VGHV_OK == OK && VGHV_ERR_INVALID == ERR_INVALID && VGHV_ERR_HIP == ERR_HIP && VGHV_ERR_NOMEM == ERR_NOMEM, "tile_fold.h returns these codes");
 
 // ---- normals, and the colours of the shaded mesh ----------------------------------------------------------------------------------------
 struct Shade {
@@ -79,64 +75,14 @@ __global__ __launch_bounds__(256) void normals_kernel(const float* __restrict__ 
     }
 }
 
-// ---- the triangle's integer box (rasterize_kernel.cpp:245-253) ------------------------------------------------------------------------------
-struct alignas(8) Box {
-    int16_t x0, y0, x1, y1;  // inclusive; x1 < x0 = covers nothing
-};
-
-__global__ __launch_bounds__(256) void boxes_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tri, int n_total, int V, int T, int h, int w,
-                                                    Box* __restrict__ boxes) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_total) return;
-    const int head = i / T, t = i - head * T;
-    const float* p = verts + (size_t)head * V * 3;
-    const int i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
-    const float p0x = p[3 * i0], p0y = p[3 * i0 + 1], p1x = p[3 * i1], p1y = p[3 * i1 + 1], p2x = p[3 * i2], p2y = p[3 * i2 + 1];
-    const float fx0 = fminf(p0x, fminf(p1x, p2x)), fx1 = fmaxf(p0x, fmaxf(p1x, p2x));
-    const float fy0 = fminf(p0y, fminf(p1y, p2y)), fy1 = fmaxf(p0y, fmaxf(p1y, p2y));
-    Box b = {1, 1, 0, 0};
-    // a triangle with a non-finite corner is skipped ((int)ceil(nan) is undefined in C; fminf / fmaxf would hide a NaN, so look at the corners)
-    const bool finite = isfinite(p0x) && isfinite(p0y) && isfinite(p1x) && isfinite(p1y) && isfinite(p2x) && isfinite(p2y);
-    if (finite) {
-        // clamp in float first: (int)ceil(1e30f) is undefined in C; the clamped result is what any in-range input gives
-        const int x_min = max((int)ceilf(fmaxf(fx0, -1.0f)), 0), x_max = min((int)floorf(fminf(fx1, (float)w)), w - 1);
-        const int y_min = max((int)ceilf(fmaxf(fy0, -1.0f)), 0), y_max = min((int)floorf(fminf(fy1, (float)h)), h - 1);
-        if (x_max >= x_min && y_max >= y_min) b = {(int16_t)x_min, (int16_t)y_min, (int16_t)x_max, (int16_t)y_max};  // w, h <= VGHV_MAX_SIDE
-    }
-    boxes[i] = b;
-}
-
 // ---- tiles ------------------------------------------------------------------------------------------------------------------------------------
-// What a lane needs of a triangle that overlaps the tile: get_point_weight's pixel-independent part (rasterize_kernel.cpp:55-72), the three
-// depths, the nine colour values and the box.  96 B x 256 = 24 KB of LDS a workgroup.
-struct Hit {
-    float p0x, p0y, v0x, v0y, v1x, v1y, dot00, dot01, dot11, inv;
+// What a lane needs of a triangle that overlaps the tile: the set-up, the three depths, the nine colour values and the box.  96 B x 256 = 24 KB
+// of LDS a workgroup.
+struct Hit : TriSetup {
     float d0, d1, d2;
     float c0[3], c1[3], c2[3];
     Box box;
 };
-
-__device__ __forceinline__ void tri_setup(Hit& t, float p1x, float p1y, float p2x, float p2y) {
-    t.v0x = p2x - t.p0x;
-    t.v0y = p2y - t.p0y;
-    t.v1x = p1x - t.p0x;
-    t.v1y = p1y - t.p0y;
-    t.dot00 = t.v0x * t.v0x + t.v0y * t.v0y;
-    t.dot01 = t.v0x * t.v1x + t.v0y * t.v1y;
-    t.dot11 = t.v1x * t.v1x + t.v1y * t.v1y;
-    const float den = t.dot00 * t.dot11 - t.dot01 * t.dot01;
-    t.inv = (den == 0.0f) ? 0.0f : 1.0f / den;
-}
-__device__ __forceinline__ void tri_weights(const Hit& t, float px, float py, float& w0, float& w1, float& w2) {
-    const float v2x = px - t.p0x, v2y = py - t.p0y;
-    const float dot02 = t.v0x * v2x + t.v0y * v2y;
-    const float dot12 = t.v1x * v2x + t.v1y * v2y;
-    const float u = (t.dot11 * dot02 - t.dot01 * dot12) * t.inv;
-    const float v = (t.dot00 * dot12 - t.dot01 * dot02) * t.inv;
-    w0 = 1.0f - u - v;
-    w1 = v;
-    w2 = u;
-}
 
 // (unsigned char)((1 - alpha) * byte + alpha * 255 * p_color): truncation, the low 8 bits for in-range values (as csrc/raster.hip)
 __device__ __forceinline__ uint32_t blend(uint32_t byte, float pc, float one_minus_alpha, float alpha255) {
@@ -173,21 +119,13 @@ __global__ __launch_bounds__(256) void tiles_kernel(const float* __restrict__ ve
         const float* p = verts + (size_t)head * V * 3;
         const float* col = colours + (size_t)head * colour_stride;
         const Box* hb = boxes + (size_t)head * T;
-        float depth = -1e8f;  // a fresh depth buffer for every head (Sim3DR.py:30)
+        float depth = BACKGROUND;  // a fresh depth buffer for every head (Sim3DR.py:30)
         for (int base = 0; base < T; base += 256) {
             const int t = base + tid;
             Box b = {1, 1, 0, 0};
             if (t < T) b = hb[t];
             const bool hit = b.x1 >= b.x0 && b.x1 >= tx0 && b.x0 <= tx1 && b.y1 >= ty0 && b.y0 <= ty1;
-            const unsigned long long mask = __ballot(hit);
-            if (lane == 0) wave_hits[wave] = __popcll(mask);
-            __syncthreads();
-            int slot = __popcll(mask & ((1ull << lane) - 1ull)), count = 0;
-            for (int k = 0; k < 4; ++k) {
-                const int c = wave_hits[k];
-                if (k < wave) slot += c;
-                count += c;
-            }
+            compact_hits(hit, wave_hits, lane, wave, slot, count);  // declares both
             if (hit) {  // index order: waves in order, lanes in order
                 const int i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
                 Hit k;
@@ -210,8 +148,9 @@ __global__ __launch_bounds__(256) void tiles_kernel(const float* __restrict__ ve
                 const Hit& k = hits[s];  // every lane reads the same entry: a broadcast
                 // the triangle's own box, per pixel: in float arithmetic all three weights can be positive one pixel outside it
                 if (x < k.box.x0 || x > k.box.x1 || y < k.box.y0 || y > k.box.y1) continue;
-                float w0, w1, w2;
-                tri_weights(k, px, py, w0, w1, w2);
+                float u, v;
+                tri_uv(k, px, py, u, v);
+                const float w0 = 1.0f - u - v, w1 = v, w2 = u;  // get_point_weight
                 if (w2 > 0 && w1 > 0 && w0 > 0) {
                     const float pd = w0 * k.d0 + w1 * k.d1 + w2 * k.d2;
                     if (pd > depth) {  // false for NaN; -0 and +0 compare equal, as in the reference
@@ -222,7 +161,6 @@ __global__ __launch_bounds__(256) void tiles_kernel(const float* __restrict__ ve
                     }
                 }
             }
-            // the next chunk's wave_hits are written before, its hits after, a barrier every wave reaches only when it is done with this list
         }
     }
     if (live) {
@@ -233,21 +171,14 @@ __global__ __launch_bounds__(256) void tiles_kernel(const float* __restrict__ ve
     }
 }
 
-// ---- per-device state ---------------------------------------------------------------------------------------------------------------------
-struct MeshState {
-    Staging staging;
-    Box* boxes = nullptr;  // library scratch [n, T], grown on demand
-    size_t box_bytes = 0;
-};
-
 std::mutex g_mutex;
-std::map<int, MeshState> g_state;
+std::map<int, State> g_state;
 
 // every triangle index against V
 int check_triangles(const char* who, const int32_t* triangles, int T, int V) {
-    for (int64_t i = 0; i < (int64_t)T * 3; ++i)
-        VGHV_REQUIRE(triangles[i] >= 0 && triangles[i] < V, "%s: triangle %lld: index %d outside the %d vertices", who, (long long)(i / 3), triangles[i], V);
-    return VGHV_OK;
+    const int64_t bad = first_bad_index(triangles, (int64_t)T * 3, V);
+    TF_REQUIRE(bad < 0, "%s: triangle %lld: index %d outside the %d vertices", who, (long long)(bad / 3), triangles[bad], V);
+    return OK;
 }
 
 // [first (V + 1) | incident (3 T)]: a stable counting sort of the 3 T corners by vertex, so that a vertex's triangles come in ascending index
@@ -270,152 +201,101 @@ void launch_normals(const float* verts, const uint8_t* d_tri, const uint8_t* d_i
 }  // namespace
 
 extern "C" VGHV_API int vghv_vertex_normals(const float* verts_dev, int n, int V, const int32_t* triangles, int T, float* normals_dev, void* stream) {
-    VGHV_REQUIRE(n >= 0 && V >= 1 && T >= 0, "vertex_normals: bad sizes (n %d, V %d, T %d)", n, V, T);
-    VGHV_REQUIRE((int64_t)n * V <= INT32_MAX / 4 && T <= INT32_MAX / 4, "vertex_normals: %lld vertices or %d triangles exceed one launch", (long long)n * V, T);
-    if (n == 0) return VGHV_OK;
-    VGHV_REQUIRE(verts_dev && normals_dev, "vertex_normals: null vertices or normals (verts_dev %p, normals_dev %p)", (const void*)verts_dev, (void*)normals_dev);
-    VGHV_REQUIRE(triangles || T == 0, "vertex_normals: null triangles");
-    VGHV_REQUIRE(verts_dev != normals_dev, "vertex_normals: normals_dev overlaps verts_dev");
+    TF_REQUIRE(n >= 0 && V >= 1 && T >= 0, "vertex_normals: bad sizes (n %d, V %d, T %d)", n, V, T);
+    TF_REQUIRE((int64_t)n * V <= INT32_MAX / 4 && T <= INT32_MAX / 4, "vertex_normals: %lld vertices or %d triangles exceed one launch", (long long)n * V, T);
+    if (n == 0) return OK;
+    TF_REQUIRE(verts_dev && normals_dev, "vertex_normals: null vertices or normals (verts_dev %p, normals_dev %p)", (const void*)verts_dev, (void*)normals_dev);
+    TF_REQUIRE(triangles || T == 0, "vertex_normals: null triangles");
+    TF_REQUIRE(verts_dev != normals_dev, "vertex_normals: normals_dev overlaps verts_dev");
     if (int rc = check_triangles("vertex_normals", triangles, T, V)) return rc;
     hipStream_t st = (hipStream_t)stream;
     int device = 0;
-    VGHV_HIP(hipGetDevice(&device));
+    TF_HIP(hipGetDevice(&device));
     std::lock_guard<std::mutex> lock(g_mutex);
-    MeshState& s = g_state[device];
+    State& s = g_state[device];
     const size_t at_inc = align16((size_t)T * 12), total = at_inc + incidence_bytes(T, V);
-    if (int rc = staging_reserve(s.staging, total, "vertex_normals")) return rc;
-    uint8_t* h = s.staging.host;
+    if (int rc = reserve(s, total, 0, "vertex_normals")) return rc;
+    uint8_t* h = s.host;
     if (T) memcpy(h, triangles, (size_t)T * 12);
     build_incidence(triangles, T, V, (int32_t*)(h + at_inc), (int32_t*)(h + at_inc + align16(((size_t)V + 1) * 4)));
-    VGHV_HIP(hipMemcpyAsync(s.staging.dev, h, total, hipMemcpyHostToDevice, st));
-    launch_normals(verts_dev, s.staging.dev, s.staging.dev + at_inc, n, V, 1.0f, 0, Shade{}, normals_dev, st);
-    VGHV_HIP(hipGetLastError());
-    VGHV_HIP(hipEventRecord(s.staging.ev, st));
-    s.staging.recorded = true;
-    return VGHV_OK;
+    Queue q;  // from here on work is queued (tile_fold.h, queue-then-record)
+    TF_QUEUE(q, hipMemcpyAsync(s.dev, h, total, hipMemcpyHostToDevice, st));
+    if (q.ok()) launch_normals(verts_dev, s.dev, s.dev + at_inc, n, V, 1.0f, 0, Shade{}, normals_dev, st);
+    return finish(q, s, true, st, "vertex_normals");
 }
 
 extern "C" VGHV_API int vghv_render_meshes(const vghv_mesh_job* job, void* stream) {
-    VGHV_REQUIRE(job, "render_meshes: null job");
+    TF_REQUIRE(job, "render_meshes: null job");
     const vghv_mesh_job& j = *job;
     // everything is checked before anything is allocated, written or queued
-    VGHV_REQUIRE(j.src_dev && j.dst_dev, "render_meshes: null image (src_dev %p, dst_dev %p)", (const void*)j.src_dev, (void*)j.dst_dev);
-    VGHV_REQUIRE(j.channels == 3, "render_meshes: %d channels (needs 3: u8 RGB)", j.channels);
-    VGHV_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHV_MAX_SIDE && j.width <= VGHV_MAX_SIDE, "render_meshes: image %d x %d outside 1 .. %d", j.height, j.width,
-                 VGHV_MAX_SIDE);
-    VGHV_REQUIRE(j.src_pitch_bytes >= (int64_t)j.width * 3, "render_meshes: src_pitch_bytes %lld < width * 3 = %lld", (long long)j.src_pitch_bytes, (long long)j.width * 3);
+    TF_REQUIRE(j.src_dev && j.dst_dev, "render_meshes: null image (src_dev %p, dst_dev %p)", (const void*)j.src_dev, (void*)j.dst_dev);
+    TF_REQUIRE(j.channels == 3, "render_meshes: %d channels (needs 3: u8 RGB)", j.channels);
+    TF_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHV_MAX_SIDE && j.width <= VGHV_MAX_SIDE, "render_meshes: image %d x %d outside 1 .. %d", j.height, j.width,
+               VGHV_MAX_SIDE);
+    TF_REQUIRE(j.src_pitch_bytes >= (int64_t)j.width * 3, "render_meshes: src_pitch_bytes %lld < width * 3 = %lld", (long long)j.src_pitch_bytes, (long long)j.width * 3);
     const int W = j.width, H = j.height, n = j.n_heads, V = j.n_vertices, T = j.n_triangles;
     {
         const uintptr_t s0 = (uintptr_t)j.src_dev, s1 = s0 + (size_t)(H - 1) * (size_t)j.src_pitch_bytes + (size_t)W * 3, d0 = (uintptr_t)j.dst_dev, d1 = d0 + (size_t)H * W * 3;
-        VGHV_REQUIRE(s1 <= d0 || d1 <= s0, "render_meshes: dst_dev overlaps src_dev");
+        TF_REQUIRE(s1 <= d0 || d1 <= s0, "render_meshes: dst_dev overlaps src_dev");
     }
-    VGHV_REQUIRE(n >= 0 && n <= VGHV_MAX_DRAW_HEADS, "render_meshes: %d heads outside 0 .. %d", n, VGHV_MAX_DRAW_HEADS);
-    VGHV_REQUIRE(V >= 0 && T >= 0, "render_meshes: negative count");
-    VGHV_REQUIRE(j.alpha >= 0.0f && j.alpha <= 1.0f, "render_meshes: alpha %g outside 0 .. 1", (double)j.alpha);
-    VGHV_REQUIRE(j.z_sign == 1.0f || j.z_sign == -1.0f, "render_meshes: z_sign %g is neither +1 nor -1", (double)j.z_sign);
-    VGHV_REQUIRE(j.shade == 0 || j.shade == 1, "render_meshes: shade %d is neither 0 nor 1", j.shade);
-    VGHV_REQUIRE(j.colors_per_head == 0 || j.colors_per_head == 1, "render_meshes: colors_per_head %d is neither 0 nor 1", j.colors_per_head);
+    TF_REQUIRE(n >= 0 && n <= VGHV_MAX_DRAW_HEADS, "render_meshes: %d heads outside 0 .. %d", n, VGHV_MAX_DRAW_HEADS);
+    TF_REQUIRE(V >= 0 && T >= 0, "render_meshes: negative count");
+    TF_REQUIRE(j.alpha >= 0.0f && j.alpha <= 1.0f, "render_meshes: alpha %g outside 0 .. 1", (double)j.alpha);
+    TF_REQUIRE(j.z_sign == 1.0f || j.z_sign == -1.0f, "render_meshes: z_sign %g is neither +1 nor -1", (double)j.z_sign);
+    TF_REQUIRE(j.shade == 0 || j.shade == 1, "render_meshes: shade %d is neither 0 nor 1", j.shade);
+    TF_REQUIRE(j.colors_per_head == 0 || j.colors_per_head == 1, "render_meshes: colors_per_head %d is neither 0 nor 1", j.colors_per_head);
     const bool paint = n > 0 && T > 0;
     if (paint) {
-        VGHV_REQUIRE(V >= 1 && j.verts_dev && j.triangles && j.bounds && j.colors_dev, "render_meshes: null vertices, triangles, bounds or colours (n_vertices %d)", V);
-        VGHV_REQUIRE((int64_t)n * T <= INT32_MAX / 4 && (int64_t)n * V <= INT32_MAX / 4, "render_meshes: %lld triangles or %lld vertices exceed one launch", (long long)n * T,
-                     (long long)n * V);
-        VGHV_REQUIRE(!j.shade || j.colors_per_head, "render_meshes: shading writes one colour table per head (colors_per_head must be 1)");
+        TF_REQUIRE(V >= 1 && j.verts_dev && j.triangles && j.bounds && j.colors_dev, "render_meshes: null vertices, triangles, bounds or colours (n_vertices %d)", V);
+        TF_REQUIRE((int64_t)n * T <= INT32_MAX / 4 && (int64_t)n * V <= INT32_MAX / 4, "render_meshes: %lld triangles or %lld vertices exceed one launch", (long long)n * T,
+                   (long long)n * V);
+        TF_REQUIRE(!j.shade || j.colors_per_head, "render_meshes: shading writes one colour table per head (colors_per_head must be 1)");
         if (j.shade) {
             const float c[8] = {j.color[0], j.color[1], j.color[2], j.ambient, j.diffuse, j.light[0], j.light[1], j.light[2]};
-            for (int i = 0; i < 8; ++i) VGHV_REQUIRE(c[i] == c[i] && c[i] - c[i] == 0.0f, "render_meshes: a shading constant is not finite");
-            VGHV_REQUIRE(j.color[0] >= 0 && j.color[0] <= 1 && j.color[1] >= 0 && j.color[1] <= 1 && j.color[2] >= 0 && j.color[2] <= 1 && j.ambient >= 0 && j.diffuse >= 0,
-                         "render_meshes: colour outside 0 .. 1 or negative ambient / diffuse");
+            for (int i = 0; i < 8; ++i) TF_REQUIRE(c[i] == c[i] && c[i] - c[i] == 0.0f, "render_meshes: a shading constant is not finite");
+            TF_REQUIRE(j.color[0] >= 0 && j.color[0] <= 1 && j.color[1] >= 0 && j.color[1] <= 1 && j.color[2] >= 0 && j.color[2] <= 1 && j.ambient >= 0 && j.diffuse >= 0,
+                       "render_meshes: colour outside 0 .. 1 or negative ambient / diffuse");
         }
         if (int rc = check_triangles("render_meshes", j.triangles, T, V)) return rc;
-        for (int i = 0; i < n; ++i) {
+        if (const int i = first_bad_bound(j.bounds, n, W, H); i >= 0) {
             const int32_t* b = j.bounds + 4 * i;
-            const bool empty = b[2] < b[0] || b[3] < b[1];
-            VGHV_REQUIRE(empty || (b[0] >= 0 && b[1] >= 0 && b[2] < W && b[3] < H), "render_meshes: head %d: bounds (%d, %d, %d, %d) outside the image", i, b[0], b[1], b[2], b[3]);
+            TF_REQUIRE(false, "render_meshes: head %d: bounds (%d, %d, %d, %d) outside the image", i, b[0], b[1], b[2], b[3]);
         }
     }
     hipStream_t st = (hipStream_t)stream;
     int device = 0;
-    VGHV_HIP(hipGetDevice(&device));
+    TF_HIP(hipGetDevice(&device));
     std::lock_guard<std::mutex> lock(g_mutex);
-    MeshState& s = g_state[device];
-
-    // "tile -> heads in order" for the tiles some head touches: count, prefix, fill (heads are visited in order, so every list is ascending)
-    const int tiles_x = (W + TILE - 1) / TILE, tiles_y = (H + TILE - 1) / TILE;
-    std::vector<int32_t> grid;
-    size_t n_tiles = 0, n_pairs = 0;
-    if (paint) {
-        grid.assign((size_t)tiles_x * tiles_y + 1, 0);
-        for (int i = 0; i < n; ++i) {
-            const int32_t* b = j.bounds + 4 * i;
-            if (b[2] < b[0] || b[3] < b[1]) continue;
-            for (int ty = b[1] / TILE; ty <= b[3] / TILE; ++ty)
-                for (int tx = b[0] / TILE; tx <= b[2] / TILE; ++tx) grid[(size_t)ty * tiles_x + tx]++;
-        }
-        for (size_t t = 0; t < (size_t)tiles_x * tiles_y; ++t) {
-            n_tiles += grid[t] != 0;
-            n_pairs += (size_t)grid[t];
-        }
-    }
-    VGHV_REQUIRE(n_pairs <= (size_t)INT32_MAX, "render_meshes: %zu (tile, head) pairs exceed one launch", n_pairs);
+    State& s = g_state[device];
+    TileLists lists;
+    if (paint) lists.count(j.bounds, n, W, H);
+    const size_t n_tiles = lists.n_tiles, n_pairs = lists.n_pairs;
+    TF_REQUIRE(n_pairs <= (size_t)INT32_MAX, "render_meshes: %zu (tile, head) pairs exceed one launch", n_pairs);
     const bool tiles = n_tiles > 0, work = tiles || (paint && j.shade);  // with shade the colours are written even when no head touches the image
     // one upload: [triangles | first, incident (shading only) | tile_xy | tile_first | tile_heads], each from a 16-byte boundary
     const size_t at_inc = align16((size_t)T * 12), at_xy = at_inc + (work && j.shade ? incidence_bytes(T, V) : 0), at_first = at_xy + align16(n_tiles * 4);
     const size_t at_heads = at_first + align16((n_tiles + 1) * 4), total = at_heads + align16(n_pairs * 4);
     if (work) {
-        if (int rc = staging_reserve(s.staging, total, "render_meshes")) return rc;  // also waits for this device's previous call
-        const size_t need = tiles ? (size_t)n * T * sizeof(Box) : 0;
-        if (need > s.box_bytes) {  // nothing is using the old boxes: the wait above covered the previous call's kernels
-            hipFree(s.boxes);
-            s.boxes = nullptr;
-            s.box_bytes = 0;
-            if (hipMalloc((void**)&s.boxes, need) != hipSuccess) {
-                set_error("render_meshes: allocating %zu bytes of triangle boxes failed", need);
-                return VGHV_ERR_NOMEM;
-            }
-            s.box_bytes = need;
-        }
-        uint8_t* h = s.staging.host;
+        if (int rc = reserve(s, total, tiles ? (size_t)n * T * sizeof(Box) : 0, "render_meshes")) return rc;  // also waits for this device's previous call
+        uint8_t* h = s.host;
         memcpy(h, j.triangles, (size_t)T * 12);
         if (j.shade) build_incidence(j.triangles, T, V, (int32_t*)(h + at_inc), (int32_t*)(h + at_inc + align16(((size_t)V + 1) * 4)));
-        uint32_t* xy = (uint32_t*)(h + at_xy);
-        int32_t* first = (int32_t*)(h + at_first);
-        int32_t* heads = (int32_t*)(h + at_heads);
-        size_t k = 0, at = 0;
-        for (size_t t = 0; t < (size_t)tiles_x * tiles_y; ++t) {  // grid[t] becomes the position of the tile's next head
-            const int32_t c = grid[t];
-            if (c) {
-                xy[k] = (uint32_t)(t % tiles_x) | (uint32_t)(t / tiles_x) << 16;
-                first[k++] = (int32_t)at;
-            }
-            grid[t] = (int32_t)at;
-            at += (size_t)c;
-        }
-        first[k] = (int32_t)at;
-        for (int i = 0; i < n; ++i) {
-            const int32_t* b = j.bounds + 4 * i;
-            if (b[2] < b[0] || b[3] < b[1]) continue;
-            for (int ty = b[1] / TILE; ty <= b[3] / TILE; ++ty)
-                for (int tx = b[0] / TILE; tx <= b[2] / TILE; ++tx) heads[grid[(size_t)ty * tiles_x + tx]++] = i;
-        }
+        lists.fill((uint32_t*)(h + at_xy), (int32_t*)(h + at_first), (int32_t*)(h + at_heads));
     }
-    // dst = src everywhere; the tiles that some head touches are then rewritten from src
-    VGHV_HIP(hipMemcpy2DAsync(j.dst_dev, (size_t)W * 3, j.src_dev, (size_t)j.src_pitch_bytes, (size_t)W * 3, (size_t)H, hipMemcpyDeviceToDevice, st));
-    if (!work) return VGHV_OK;
-    const uint8_t* d = s.staging.dev;
-    VGHV_HIP(hipMemcpyAsync(s.staging.dev, s.staging.host, total, hipMemcpyHostToDevice, st));
-    if (j.shade) {
+    // from here on work is queued (tile_fold.h, queue-then-record).  dst = src everywhere; the tiles that some head touches are then rewritten from src
+    Queue q;
+    TF_QUEUE(q, hipMemcpy2DAsync(j.dst_dev, (size_t)W * 3, j.src_dev, (size_t)j.src_pitch_bytes, (size_t)W * 3, (size_t)H, hipMemcpyDeviceToDevice, st));
+    const uint8_t* d = s.dev;
+    if (work) TF_QUEUE(q, hipMemcpyAsync(s.dev, s.host, total, hipMemcpyHostToDevice, st));
+    if (work && j.shade && q.ok()) {
         const Shade sh = {j.color[0], j.color[1], j.color[2], j.ambient, j.diffuse, j.light[0], j.light[1], j.light[2]};
         launch_normals(j.verts_dev, d, d + at_inc, n, V, j.z_sign, 1, sh, j.colors_dev, st);
     }
-    if (tiles) {
+    if (tiles && q.ok()) {
         hipLaunchKernelGGL(boxes_kernel, dim3((unsigned)(n * T + 255) / 256), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, n * T, V, T, H, W, s.boxes);
         hipLaunchKernelGGL(tiles_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, (const float*)j.colors_dev,
                            j.colors_per_head ? (size_t)V * 3 : (size_t)0, (const Box*)s.boxes, (const uint32_t*)(d + at_xy), (const int32_t*)(d + at_first),
                            (const int32_t*)(d + at_heads), V, T, H, W, j.reverse ? 1 : 0, j.z_sign, j.alpha, j.src_dev, j.src_pitch_bytes, j.dst_dev);
     }
-    VGHV_HIP(hipGetLastError());
-    VGHV_HIP(hipEventRecord(s.staging.ev, st));
-    s.staging.recorded = true;
-    return VGHV_OK;
+    return finish(q, s, work, st, "render_meshes");
 }

@@ -2,68 +2,28 @@
 // z-buffered rasteriser that paints a mesh from a texture image through per-vertex texture coordinates, for all heads of an image at once and in both
 // directions: onto the photograph (wrap) or, with the UV atlas as the image and the photograph as the texture, into one atlas per head (unwrap).
 //
-// Per pixel the result is a serial fold over heads (in order) and over the head's triangles (in index order); csrc/mesh_render.hip's tile-major scheme
-// reproduces such a fold exactly and is restated here (this library shares no object and no header with the other three):
-//   fill     the background of depth, triangle and head (-1e8 is no memset pattern); dst is left alone
-//   boxes    one lane per (head, triangle): the triangle's clamped integer bounding box as 4 x int16
-//   tiles    one 256-lane workgroup per 16 x 16 tile of a destination that some head touches (the host builds "tile -> heads in order" from the
-//            per-head pixel bounds; with one destination per head every (head, tile) pair is a workgroup of its own).  A lane owns one pixel and
-//            keeps depth, owner and the winner's clamped texture position in registers.  For every head of the tile the workgroup scans the head's
-//            boxes 256 at a time, compacts the ones that overlap the tile IN INDEX ORDER into LDS (ballot + prefix) together with their
-//            pixel-independent set-up (88 B a triangle, 22 KB a workgroup, so seven workgroups share a CU's 160 KB of LDS), and
-//            every lane walks that list serially with exactly the reference's arithmetic.
+// Per pixel the result is a serial fold over heads (in order) and over the head's triangles (in index order): the tile-major scheme of csrc/tile_fold.h
+// (fill, then boxes, then tiles; with one destination per head every (head, tile) pair is a workgroup of its own), with depth, owner and the winner's
+// clamped texture position in a lane's registers.  88 B a triangle, 22 KB of LDS a workgroup, so seven workgroups share a CU's 160 KB.
 // In the reference every win rewrites the pixel's colour and only the last one stays, and the colour depends on nothing but the winner's texture
 // position: the lane looks the texture up once, after the fold.  No atomics anywhere.
 // The INSIDE RULE is  x < 2 || x > w - 3 || y < 2 || y > h - 3 || is_point_in_tri:  in a frame two pixels wide every pixel of a triangle's box counts.
 // All arithmetic is IEEE float32 in the reference's operation order (contraction off, true division): every output is bit-identical to the
 // reference's own C++ (tests/test_gpu_texture.py).
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stddef.h>
-#include <stdint.h>
-#include <stdio.h>
 #include <string.h>
 
 #include <map>
 #include <mutex>
-#include <vector>
 
 #include "../../include/vgh_tex.h"
+#include "tile_fold.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-// ---- error plumbing: never throw across the C ABI ---------------------------------------------------------------------------------------------
-thread_local char g_error[512] = "";
-
-void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-}
-
-#define TEX_HIP(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-            return VGHTEX_ERR_HIP;                                                          \
-        }                                                                                   \
-    } while (0)
-
-#define TEX_REQUIRE(cond, ...)         \
-    do {                               \
-        if (!(cond)) {                 \
-            set_error(__VA_ARGS__);    \
-            return VGHTEX_ERR_INVALID; \
-        }                              \
-    } while (0)
-
-constexpr int TILE = 16;             // 16 x 16 pixels = the 256 lanes of a workgroup
-constexpr float BACKGROUND = -1e8f;  // what Sim3DR's callers initialise the depth buffer with (Sim3DR.py:31)
+using namespace tile_fold;
+static_assert(VGHTEX_OK == OK && VGHTEX_ERR_INVALID == ERR_INVALID && VGHTEX_ERR_HIP == ERR_HIP && VGHTEX_ERR_NOMEM == ERR_NOMEM, "tile_fold.h returns these codes");
 
 // ---- the background of depth, triangle and head ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void fill_kernel(size_t n_px, float* __restrict__ depth, int32_t* __restrict__ tri, int32_t* __restrict__ head) {
@@ -74,62 +34,15 @@ __global__ __launch_bounds__(256) void fill_kernel(size_t n_px, float* __restric
     if (head) head[i] = -1;
 }
 
-// ---- the triangle's integer box (rasterize_kernel.cpp:406-415) -----------------------------------------------------------------------------------
-struct alignas(8) Box {
-    int16_t x0, y0, x1, y1;  // inclusive; x1 < x0 = covers nothing
-};
-
-__global__ __launch_bounds__(256) void boxes_kernel(const float* __restrict__ verts, const int32_t* __restrict__ tri, int n_total, int V, int T, int h, int w,
-                                                    Box* __restrict__ boxes) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_total) return;
-    const int head = i / T, t = i - head * T;
-    const float* p = verts + (size_t)head * V * 3;
-    const int i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
-    const float p0x = p[3 * i0], p0y = p[3 * i0 + 1], p1x = p[3 * i1], p1y = p[3 * i1 + 1], p2x = p[3 * i2], p2y = p[3 * i2 + 1];
-    const float fx0 = fminf(p0x, fminf(p1x, p2x)), fx1 = fmaxf(p0x, fmaxf(p1x, p2x));
-    const float fy0 = fminf(p0y, fminf(p1y, p2y)), fy1 = fmaxf(p0y, fmaxf(p1y, p2y));
-    Box b = {1, 1, 0, 0};
-    // a triangle with a non-finite corner is skipped ((int)ceil(nan) is undefined in C; fminf / fmaxf would hide a NaN, so look at the corners)
-    const bool finite = isfinite(p0x) && isfinite(p0y) && isfinite(p1x) && isfinite(p1y) && isfinite(p2x) && isfinite(p2y);
-    if (finite) {
-        // clamp in float first: (int)ceil(1e30f) is undefined in C; the clamped result is what any in-range input gives
-        const int x_min = max((int)ceilf(fmaxf(fx0, -1.0f)), 0), x_max = min((int)floorf(fminf(fx1, (float)w)), w - 1);
-        const int y_min = max((int)ceilf(fmaxf(fy0, -1.0f)), 0), y_max = min((int)floorf(fminf(fy1, (float)h)), h - 1);
-        if (x_max >= x_min && y_max >= y_min) b = {(int16_t)x_min, (int16_t)y_min, (int16_t)x_max, (int16_t)y_max};  // w, h <= VGHTEX_MAX_SIDE
-    }
-    boxes[i] = b;
-}
-
 // ---- tiles ----------------------------------------------------------------------------------------------------------------------------------------
-// What a lane needs of a triangle that overlaps the tile: the pixel-independent part of get_point_weight (rasterize_kernel.cpp:54-82), the three depths,
-// the three texture corners, the box and the triangle's index.  88 B x 256 = 22 KB of LDS a workgroup.
-struct Hit {
-    float p0x, p0y, v0x, v0y, v1x, v1y, dot00, dot01, dot11, inv;
+// What a lane needs of a triangle that overlaps the tile: the set-up, the three depths, the three texture corners, the triangle's index and the box.
+// 88 B x 256 = 22 KB of LDS a workgroup.
+struct Hit : TriSetup {
     float d0, d1, d2;
     float q0x, q0y, q1x, q1y, q2x, q2y;
     int32_t t;
     Box box;
 };
-
-__device__ __forceinline__ void tri_setup(Hit& t, float p1x, float p1y, float p2x, float p2y) {
-    t.v0x = p2x - t.p0x;
-    t.v0y = p2y - t.p0y;
-    t.v1x = p1x - t.p0x;
-    t.v1y = p1y - t.p0y;
-    t.dot00 = t.v0x * t.v0x + t.v0y * t.v0y;
-    t.dot01 = t.v0x * t.v1x + t.v0y * t.v1y;
-    t.dot11 = t.v1x * t.v1x + t.v1y * t.v1y;
-    const float den = t.dot00 * t.dot11 - t.dot01 * t.dot01;
-    t.inv = (den == 0.0f) ? 0.0f : 1.0f / den;
-}
-__device__ __forceinline__ void tri_uv(const Hit& t, float px, float py, float& u, float& v) {
-    const float v2x = px - t.p0x, v2y = py - t.p0y;
-    const float dot02 = t.v0x * v2x + t.v0y * v2y;
-    const float dot12 = t.v1x * v2x + t.v1y * v2y;
-    u = (t.dot11 * dot02 - t.dot01 * dot12) * t.inv;
-    v = (t.dot00 * dot12 - t.dot01 * dot02) * t.inv;
-}
 
 // std::min / std::max as the source calls them: min(a, b) = b < a ? b : a, max(a, b) = a < b ? b : a (a NaN in `a` stays)
 __device__ __forceinline__ float clamp_like_std(float a, float hi) {
@@ -183,15 +96,7 @@ __global__ __launch_bounds__(256) void tiles_kernel(const float* __restrict__ ve
             Box b = {1, 1, 0, 0};
             if (t < T) b = hb[t];
             const bool hit = b.x1 >= b.x0 && b.x1 >= tx0 && b.x0 <= tx1 && b.y1 >= ty0 && b.y0 <= ty1;
-            const unsigned long long mask = __ballot(hit);
-            if (lane == 0) wave_hits[wave] = __popcll(mask);
-            __syncthreads();
-            int slot = __popcll(mask & ((1ull << lane) - 1ull)), count = 0;
-            for (int k = 0; k < 4; ++k) {
-                const int n = wave_hits[k];
-                if (k < wave) slot += n;
-                count += n;
-            }
+            compact_hits(hit, wave_hits, lane, wave, slot, count);  // declares both
             if (hit) {  // index order: waves in order, lanes in order
                 const int i0 = tri[3 * t], i1 = tri[3 * t + 1], i2 = tri[3 * t + 2];
                 Hit k;
@@ -231,7 +136,6 @@ __global__ __launch_bounds__(256) void tiles_kernel(const float* __restrict__ ve
                     }
                 }
             }
-            // the next chunk's wave_hits are written before, its hits after, a barrier every wave reaches only when it is done with this list
         }
     }
     if (o_head < 0) return;  // no barrier follows
@@ -261,53 +165,8 @@ __global__ __launch_bounds__(256) void tiles_kernel(const float* __restrict__ ve
     }
 }
 
-// ---- per-device state: what one call uploads (one pinned and one device block, guarded by an event) and the boxes -----------------------------------
-struct State {
-    uint8_t* host = nullptr;
-    uint8_t* dev = nullptr;
-    size_t bytes = 0;
-    hipEvent_t ev = nullptr;
-    bool recorded = false;
-    Box* boxes = nullptr;  // library scratch [n, T], grown on demand
-    size_t box_bytes = 0;
-};
-
 std::mutex g_mutex;
 std::map<int, State> g_state;
-
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
-
-// waits for the blocks' previous user (whatever stream it was queued on), then makes room for `need` staging bytes and `need_boxes` bytes of boxes
-int reserve(State& s, size_t need, size_t need_boxes) {
-    if (s.recorded) TEX_HIP(hipEventSynchronize(s.ev));
-    s.recorded = false;
-    if (!s.ev) TEX_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    if (need > s.bytes) {
-        hipHostFree(s.host);
-        hipFree(s.dev);
-        s.host = s.dev = nullptr;
-        s.bytes = 0;
-        const size_t cap = align16(need + need / 2);
-        if (hipHostMalloc((void**)&s.host, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&s.dev, cap) != hipSuccess) {
-            hipHostFree(s.host);
-            s.host = nullptr;
-            set_error("render_texture: allocating %zu bytes of staging failed", cap);
-            return VGHTEX_ERR_NOMEM;
-        }
-        s.bytes = cap;
-    }
-    if (need_boxes > s.box_bytes) {
-        hipFree(s.boxes);
-        s.boxes = nullptr;
-        s.box_bytes = 0;
-        if (hipMalloc((void**)&s.boxes, need_boxes) != hipSuccess) {
-            set_error("render_texture: allocating %zu bytes of triangle boxes failed", need_boxes);
-            return VGHTEX_ERR_NOMEM;
-        }
-        s.box_bytes = need_boxes;
-    }
-    return VGHTEX_OK;
-}
 
 inline bool is_flag(int32_t v) { return v == 0 || v == 1; }
 
@@ -315,147 +174,88 @@ inline bool is_flag(int32_t v) { return v == 0 || v == 1; }
 
 extern "C" VGHTEX_API const char* vghtex_version(void) { return "vghtex 1 (gfx950)"; }
 
-extern "C" VGHTEX_API const char* vghtex_last_error(void) { return g_error; }
+extern "C" VGHTEX_API const char* vghtex_last_error(void) { return tile_fold::g_error; }
 
 extern "C" VGHTEX_API int vghtex_render_texture(const vghtex_job* job, void* stream) {
-    TEX_REQUIRE(job, "render_texture: null job");
+    TF_REQUIRE(job, "render_texture: null job");
     const vghtex_job& j = *job;
     // everything is checked before anything is allocated, written or queued
-    TEX_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHTEX_MAX_SIDE && j.width <= VGHTEX_MAX_SIDE, "render_texture: height x width %d x %d outside 1 .. %d", j.height,
-                j.width, VGHTEX_MAX_SIDE);
+    TF_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHTEX_MAX_SIDE && j.width <= VGHTEX_MAX_SIDE, "render_texture: height x width %d x %d outside 1 .. %d", j.height,
+               j.width, VGHTEX_MAX_SIDE);
     const int W = j.width, H = j.height, n = j.n_heads, V = j.n_vertices, T = j.n_triangles, Vt = j.n_tex_vertices, c = j.channels;
-    TEX_REQUIRE(c >= 1 && c <= VGHTEX_MAX_CHANNELS, "render_texture: channels %d outside 1 .. %d", c, VGHTEX_MAX_CHANNELS);
-    TEX_REQUIRE(n >= 0 && n <= VGHTEX_MAX_HEADS, "render_texture: n_heads %d outside 0 .. %d", n, VGHTEX_MAX_HEADS);
-    TEX_REQUIRE(V >= 0, "render_texture: n_vertices %d is negative", V);
-    TEX_REQUIRE(T >= 0, "render_texture: n_triangles %d is negative", T);
-    TEX_REQUIRE(Vt >= 0, "render_texture: n_tex_vertices %d is negative", Vt);
-    TEX_REQUIRE(j.tex_height >= 1 && j.tex_width >= 1 && j.tex_height <= VGHTEX_MAX_SIDE && j.tex_width <= VGHTEX_MAX_SIDE,
-                "render_texture: tex_height x tex_width %d x %d outside 1 .. %d", j.tex_height, j.tex_width, VGHTEX_MAX_SIDE);
-    TEX_REQUIRE(j.tex_channels >= c, "render_texture: tex_channels %d below channels %d", j.tex_channels, c);
-    TEX_REQUIRE(j.tex_dtype == VGHTEX_TEX_F32 || j.tex_dtype == VGHTEX_TEX_U8, "render_texture: tex_dtype %d is neither 0 (f32) nor 1 (u8)", j.tex_dtype);
-    TEX_REQUIRE(is_flag(j.tex_per_head), "render_texture: tex_per_head %d is neither 0 nor 1", j.tex_per_head);
-    TEX_REQUIRE(is_flag(j.tex_coords_per_head), "render_texture: tex_coords_per_head %d is neither 0 nor 1", j.tex_coords_per_head);
-    TEX_REQUIRE(is_flag(j.dst_per_head), "render_texture: dst_per_head %d is neither 0 nor 1", j.dst_per_head);
-    TEX_REQUIRE(j.mapping == VGHTEX_MAP_NEAREST || j.mapping == VGHTEX_MAP_BILINEAR, "render_texture: mapping %d is neither 0 (nearest) nor 1 (bilinear)", j.mapping);
-    TEX_REQUIRE(j.mode == VGHTEX_MODE_ORDER || j.mode == VGHTEX_MODE_DEPTH, "render_texture: mode %d is neither 0 (order) nor 1 (depth)", j.mode);
-    TEX_REQUIRE(j.z_sign == 1.0f || j.z_sign == -1.0f, "render_texture: z_sign %g is neither +1 nor -1", (double)j.z_sign);
+    TF_REQUIRE(c >= 1 && c <= VGHTEX_MAX_CHANNELS, "render_texture: channels %d outside 1 .. %d", c, VGHTEX_MAX_CHANNELS);
+    TF_REQUIRE(n >= 0 && n <= VGHTEX_MAX_HEADS, "render_texture: n_heads %d outside 0 .. %d", n, VGHTEX_MAX_HEADS);
+    TF_REQUIRE(V >= 0, "render_texture: n_vertices %d is negative", V);
+    TF_REQUIRE(T >= 0, "render_texture: n_triangles %d is negative", T);
+    TF_REQUIRE(Vt >= 0, "render_texture: n_tex_vertices %d is negative", Vt);
+    TF_REQUIRE(j.tex_height >= 1 && j.tex_width >= 1 && j.tex_height <= VGHTEX_MAX_SIDE && j.tex_width <= VGHTEX_MAX_SIDE,
+               "render_texture: tex_height x tex_width %d x %d outside 1 .. %d", j.tex_height, j.tex_width, VGHTEX_MAX_SIDE);
+    TF_REQUIRE(j.tex_channels >= c, "render_texture: tex_channels %d below channels %d", j.tex_channels, c);
+    TF_REQUIRE(j.tex_dtype == VGHTEX_TEX_F32 || j.tex_dtype == VGHTEX_TEX_U8, "render_texture: tex_dtype %d is neither 0 (f32) nor 1 (u8)", j.tex_dtype);
+    TF_REQUIRE(is_flag(j.tex_per_head), "render_texture: tex_per_head %d is neither 0 nor 1", j.tex_per_head);
+    TF_REQUIRE(is_flag(j.tex_coords_per_head), "render_texture: tex_coords_per_head %d is neither 0 nor 1", j.tex_coords_per_head);
+    TF_REQUIRE(is_flag(j.dst_per_head), "render_texture: dst_per_head %d is neither 0 nor 1", j.dst_per_head);
+    TF_REQUIRE(j.mapping == VGHTEX_MAP_NEAREST || j.mapping == VGHTEX_MAP_BILINEAR, "render_texture: mapping %d is neither 0 (nearest) nor 1 (bilinear)", j.mapping);
+    TF_REQUIRE(j.mode == VGHTEX_MODE_ORDER || j.mode == VGHTEX_MODE_DEPTH, "render_texture: mode %d is neither 0 (order) nor 1 (depth)", j.mode);
+    TF_REQUIRE(j.z_sign == 1.0f || j.z_sign == -1.0f, "render_texture: z_sign %g is neither +1 nor -1", (double)j.z_sign);
     const size_t slices = j.dst_per_head ? (size_t)n : 1;
     const size_t n_px = slices * (size_t)H * (size_t)W;
-    TEX_REQUIRE(n_px / 256 < (size_t)INT32_MAX, "render_texture: %zu destination pixels exceed one launch", n_px);
+    TF_REQUIRE(n_px / 256 < (size_t)INT32_MAX, "render_texture: %zu destination pixels exceed one launch", n_px);
     if (n_px) {
-        TEX_REQUIRE(j.dst_dev, "render_texture: null dst_dev");
-        TEX_REQUIRE(j.depth_dev, "render_texture: null depth_dev");
+        TF_REQUIRE(j.dst_dev, "render_texture: null dst_dev");
+        TF_REQUIRE(j.depth_dev, "render_texture: null depth_dev");
     }
     const bool raster = n > 0 && T > 0;
     if (raster) {
-        TEX_REQUIRE(V >= 1, "render_texture: n_vertices %d with %d triangles", V, T);
-        TEX_REQUIRE(Vt >= 1, "render_texture: n_tex_vertices %d with %d triangles", Vt, T);
-        TEX_REQUIRE(j.verts_dev, "render_texture: null verts_dev");
-        TEX_REQUIRE(j.triangles, "render_texture: null triangles");
-        TEX_REQUIRE(j.tex_coords_dev, "render_texture: null tex_coords_dev");
-        TEX_REQUIRE(j.tex_triangles, "render_texture: null tex_triangles");
-        TEX_REQUIRE(j.texture_dev, "render_texture: null texture_dev");
-        TEX_REQUIRE(j.bounds, "render_texture: null bounds");
-        TEX_REQUIRE((int64_t)n * T <= INT32_MAX / 4 && (int64_t)n * V <= INT32_MAX / 4 && (int64_t)n * Vt <= INT32_MAX / 4,
-                    "render_texture: n_heads * n_triangles = %lld, n_heads * n_vertices = %lld or n_heads * n_tex_vertices = %lld exceed one launch", (long long)n * T,
-                    (long long)n * V, (long long)n * Vt);
-        const int both = V < Vt ? V : Vt;  // a mesh index reads a vertex and, for the corner's texture y, a texture coordinate
-        for (int64_t i = 0; i < (int64_t)T * 3; ++i) {
-            TEX_REQUIRE(j.triangles[i] >= 0 && j.triangles[i] < V, "render_texture: triangles: triangle %lld: index %d outside the %d vertices", (long long)(i / 3), j.triangles[i], V);
-            TEX_REQUIRE(j.triangles[i] < both, "render_texture: triangles: triangle %lld: index %d outside the %d texture coordinates (a corner's texture y is read through it)",
-                        (long long)(i / 3), j.triangles[i], Vt);
-            TEX_REQUIRE(j.tex_triangles[i] >= 0 && j.tex_triangles[i] < Vt, "render_texture: tex_triangles: triangle %lld: index %d outside the %d texture coordinates",
-                        (long long)(i / 3), j.tex_triangles[i], Vt);
+        TF_REQUIRE(V >= 1, "render_texture: n_vertices %d with %d triangles", V, T);
+        TF_REQUIRE(Vt >= 1, "render_texture: n_tex_vertices %d with %d triangles", Vt, T);
+        TF_REQUIRE(j.verts_dev, "render_texture: null verts_dev");
+        TF_REQUIRE(j.triangles, "render_texture: null triangles");
+        TF_REQUIRE(j.tex_coords_dev, "render_texture: null tex_coords_dev");
+        TF_REQUIRE(j.tex_triangles, "render_texture: null tex_triangles");
+        TF_REQUIRE(j.texture_dev, "render_texture: null texture_dev");
+        TF_REQUIRE(j.bounds, "render_texture: null bounds");
+        TF_REQUIRE((int64_t)n * T <= INT32_MAX / 4 && (int64_t)n * V <= INT32_MAX / 4 && (int64_t)n * Vt <= INT32_MAX / 4,
+                   "render_texture: n_heads * n_triangles = %lld, n_heads * n_vertices = %lld or n_heads * n_tex_vertices = %lld exceed one launch", (long long)n * T,
+                   (long long)n * V, (long long)n * Vt);
+        // a mesh index reads a vertex and, for the corner's texture y, a texture coordinate
+        const int64_t bad = first_bad_index(j.triangles, (int64_t)T * 3, V < Vt ? V : Vt), bad_tex = first_bad_index(j.tex_triangles, (int64_t)T * 3, Vt);
+        // what is reported is what one pass over the corners, looking at triangles[i] before tex_triangles[i], meets first: the earlier corner, the mesh's on a tie
+        if (bad >= 0 && (bad_tex < 0 || bad <= bad_tex)) {
+            const int32_t v = j.triangles[bad];
+            TF_REQUIRE(v >= 0 && v < V, "render_texture: triangles: triangle %lld: index %d outside the %d vertices", (long long)(bad / 3), v, V);
+            TF_REQUIRE(false, "render_texture: triangles: triangle %lld: index %d outside the %d texture coordinates (a corner's texture y is read through it)", (long long)(bad / 3), v, Vt);
         }
-        for (int i = 0; i < n; ++i) {
+        TF_REQUIRE(bad_tex < 0, "render_texture: tex_triangles: triangle %lld: index %d outside the %d texture coordinates", (long long)(bad_tex / 3), j.tex_triangles[bad_tex], Vt);
+        if (const int i = first_bad_bound(j.bounds, n, W, H); i >= 0) {
             const int32_t* b = j.bounds + 4 * i;
-            const bool empty = b[2] < b[0] || b[3] < b[1];
-            TEX_REQUIRE(empty || (b[0] >= 0 && b[1] >= 0 && b[2] < W && b[3] < H), "render_texture: bounds: head %d: (%d, %d, %d, %d) outside the image", i, b[0], b[1], b[2], b[3]);
+            TF_REQUIRE(false, "render_texture: bounds: head %d: (%d, %d, %d, %d) outside the image", i, b[0], b[1], b[2], b[3]);
         }
     }
-    // "tile -> heads in order" for the tiles some head touches: count, prefix, fill (heads are visited in order, so every list is ascending).  With one
-    // destination per head every (head, tile) pair is an entry of its own with that one head.
-    const int tiles_x = (W + TILE - 1) / TILE, tiles_y = (H + TILE - 1) / TILE;
-    std::vector<int32_t> grid;
-    size_t n_tiles = 0, n_pairs = 0;
-    if (raster) {
-        grid.assign((size_t)tiles_x * tiles_y + 1, 0);
-        for (int i = 0; i < n; ++i) {
-            const int32_t* b = j.bounds + 4 * i;
-            if (b[2] < b[0] || b[3] < b[1]) continue;
-            for (int ty = b[1] / TILE; ty <= b[3] / TILE; ++ty)
-                for (int tx = b[0] / TILE; tx <= b[2] / TILE; ++tx) grid[(size_t)ty * tiles_x + tx]++;
-        }
-        for (size_t t = 0; t < (size_t)tiles_x * tiles_y; ++t) {
-            n_tiles += grid[t] != 0;
-            n_pairs += (size_t)grid[t];
-        }
-        if (j.dst_per_head) n_tiles = n_pairs;
-    }
-    TEX_REQUIRE(n_pairs <= (size_t)INT32_MAX, "render_texture: %zu (tile, head) pairs exceed one launch", n_pairs);
+    TileLists lists;
+    if (raster) lists.count(j.bounds, n, W, H, j.dst_per_head != 0);
+    const size_t n_tiles = lists.n_tiles, n_pairs = lists.n_pairs;
+    TF_REQUIRE(n_pairs <= (size_t)INT32_MAX, "render_texture: %zu (tile, head) pairs exceed one launch", n_pairs);
     hipStream_t st = (hipStream_t)stream;
     int device = 0;
-    TEX_HIP(hipGetDevice(&device));
+    TF_HIP(hipGetDevice(&device));
     std::lock_guard<std::mutex> lock(g_mutex);
     State& s = g_state[device];
     // one upload: [triangles | tex_triangles | tile_xy | tile_first | tile_heads], each from a 16-byte boundary
     const size_t at_tt = align16((size_t)T * 12), at_xy = at_tt + align16((size_t)T * 12), at_first = at_xy + align16(n_tiles * 4), at_heads = at_first + align16((n_tiles + 1) * 4);
     const size_t total = at_heads + align16(n_pairs * 4);
     if (n_tiles) {
-        if (int rc = reserve(s, total, (size_t)n * T * sizeof(Box))) return rc;  // also waits for this device's previous call
+        if (int rc = reserve(s, total, (size_t)n * T * sizeof(Box), "render_texture")) return rc;  // also waits for this device's previous call
         uint8_t* h = s.host;
         memcpy(h, j.triangles, (size_t)T * 12);
         memcpy(h + at_tt, j.tex_triangles, (size_t)T * 12);
-        uint32_t* xy = (uint32_t*)(h + at_xy);
-        int32_t* first = (int32_t*)(h + at_first);
-        int32_t* heads = (int32_t*)(h + at_heads);
-        if (j.dst_per_head) {
-            size_t k = 0;
-            for (int i = 0; i < n; ++i) {
-                const int32_t* b = j.bounds + 4 * i;
-                if (b[2] < b[0] || b[3] < b[1]) continue;
-                for (int ty = b[1] / TILE; ty <= b[3] / TILE; ++ty)
-                    for (int tx = b[0] / TILE; tx <= b[2] / TILE; ++tx) {
-                        xy[k] = (uint32_t)tx | (uint32_t)ty << 16;
-                        first[k] = (int32_t)k;
-                        heads[k++] = i;
-                    }
-            }
-            first[k] = (int32_t)k;
-        } else {
-            size_t k = 0, at = 0;
-            for (size_t t = 0; t < (size_t)tiles_x * tiles_y; ++t) {  // grid[t] becomes the position of the tile's next head
-                const int32_t cnt = grid[t];
-                if (cnt) {
-                    xy[k] = (uint32_t)(t % tiles_x) | (uint32_t)(t / tiles_x) << 16;
-                    first[k++] = (int32_t)at;
-                }
-                grid[t] = (int32_t)at;
-                at += (size_t)cnt;
-            }
-            first[k] = (int32_t)at;
-            for (int i = 0; i < n; ++i) {
-                const int32_t* b = j.bounds + 4 * i;
-                if (b[2] < b[0] || b[3] < b[1]) continue;
-                for (int ty = b[1] / TILE; ty <= b[3] / TILE; ++ty)
-                    for (int tx = b[0] / TILE; tx <= b[2] / TILE; ++tx) heads[grid[(size_t)ty * tiles_x + tx]++] = i;
-            }
-        }
+        lists.fill((uint32_t*)(h + at_xy), (int32_t*)(h + at_first), (int32_t*)(h + at_heads));
     }
-    // from here on work is queued: the first failure is kept, nothing more is queued after it, and the event is recorded on every path so that the next
-    // call never rewrites the staging block or the boxes under work that is still queued
-    hipError_t err = hipSuccess;
-    const char* failed = "";
-#define TEX_QUEUE(expr)                            \
-    do {                                           \
-        if (err == hipSuccess) {                   \
-            err = (expr);                          \
-            if (err != hipSuccess) failed = #expr; \
-        }                                          \
-    } while (0)
-    if (n_tiles) TEX_QUEUE(hipMemcpyAsync(s.dev, s.host, total, hipMemcpyHostToDevice, st));  // first: whatever follows, the event below covers the staging block
-    if (n_px && err == hipSuccess) hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, st, n_px, j.depth_dev, j.triangle_dev, j.head_dev);
-    if (n_tiles && err == hipSuccess) {
+    // from here on work is queued (tile_fold.h, queue-then-record)
+    Queue q;
+    if (n_tiles) TF_QUEUE(q, hipMemcpyAsync(s.dev, s.host, total, hipMemcpyHostToDevice, st));  // first: whatever follows, the event covers the staging block
+    if (n_px && q.ok()) hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, st, n_px, j.depth_dev, j.triangle_dev, j.head_dev);
+    if (n_tiles && q.ok()) {
         const uint8_t* d = s.dev;
         TexArgs ta;
         ta.coords = j.tex_coords_dev;
@@ -473,19 +273,5 @@ extern "C" VGHTEX_API int vghtex_render_texture(const vghtex_job* job, void* str
                            (const uint32_t*)(d + at_xy), (const int32_t*)(d + at_first), (const int32_t*)(d + at_heads), ta, V, T, H, W, c, j.mode == VGHTEX_MODE_DEPTH ? 1 : 0,
                            j.dst_per_head, j.z_sign, j.dst_dev, j.depth_dev, j.triangle_dev, j.head_dev);
     }
-    TEX_QUEUE(hipGetLastError());
-    if (n_tiles) {
-        if (hipEventRecord(s.ev, st) == hipSuccess) {
-            s.recorded = true;
-        } else {
-            hipStreamSynchronize(st);  // no event to wait for next time: wait now
-            TEX_QUEUE(hipErrorUnknown);
-        }
-    }
-#undef TEX_QUEUE
-    if (err != hipSuccess) {
-        set_error("render_texture: %s -> %s", failed, hipGetErrorString(err));
-        return VGHTEX_ERR_HIP;
-    }
-    return VGHTEX_OK;
+    return finish(q, s, n_tiles != 0, st, "render_texture");
 }

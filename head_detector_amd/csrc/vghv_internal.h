@@ -1,5 +1,6 @@
-// What the sources of libvghview.so share (csrc/aligned.hip, csrc/draw.hip): the calling thread's error message, the argument / HIP check
-// macros of the C entry points, and the per-device staging block (pinned + device memory, guarded by an event).  Internal: hidden visibility,
+// What the sources of libvghview.so share (csrc/aligned.hip, csrc/draw.hip, csrc/mesh_render.hip): the calling thread's error message and, for
+// aligned.hip and draw.hip, the argument / HIP check macros of the C entry points and the per-device staging block (pinned + device memory,
+// guarded by an event); mesh_render.hip takes those from csrc/tile_fold.h and only the message from here.  Internal: hidden visibility,
 // nothing of libvgh.so (csrc/vgh_internal.h) is used here and libvgh.so uses nothing of this.
 #pragma once
 #include <hip/hip_runtime.h>
