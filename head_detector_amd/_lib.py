@@ -111,6 +111,7 @@ SYMBOLS = {
     "vgh_net_buffer": (_P, [_P, _I]),
     "vgh_net_buffer_bytes": (_I64, [_P, _I]),
     "vgh_net_set_cfg": (_I, [_P, _I, _I]),
+    "vgh_net_op_cfg": (_I, [_P, _I]),
     "vgh_net_set_b2b": (_I, [_P, _I]),
     "vgh_net_stem_fused": (_I, [_P]),
     "vgh_net_b2b_pairs": (_I, [_P]),

@@ -811,6 +811,13 @@ int vgh_net_set_cfg(vgh_net* n, int op_index, int cfg) {
     return VGH_OK;
 }
 
+int vgh_net_op_cfg(vgh_net* n, int op_index) {
+    if (!n || op_index < 0 || op_index >= (int)n->ops.size()) return -1;
+    const NetOp& op = n->ops[op_index];
+    if (op.d.kind != VGH_OP_CONV || n->bufs[op.d.in_buf].is_f32 == VGH_FMT_F32) return -1;  // (fp32 parity nets run the FMA kernel: no tile table)
+    return op.d.force_cfg >= 0 ? op.d.force_cfg : op.auto_cfg;
+}
+
 static uint16_t* g_zeros[16] = {nullptr};
 
 int vgh_conv2d(const vgh_conv_call* c, void* stream) {

@@ -582,6 +582,18 @@ class VGHeadsEngine:
         """Tile names ``set_cfg`` indexes: the bf16 table, or the split-precision table for the fp16x3 / bf16x3 modes."""
         return tile_names(self.lib, self.precision)
 
+    def op_tiles(self) -> Dict[int, str]:
+        """{op index: tile name} of every conv on a tile table (vgh_net_op_cfg): the tile SELECTED for the arena batch -- the one ``set_cfg`` / ``load_tuning`` left in place,
+        else the library's automatic choice.  What launches can differ in three places (include/vgh.h): a forced tile of a split-precision / fp16 net that the launch refuses
+        falls back silently, a "q" tile may launch its "p" twin, and the ops of a back-to-back pair launch together in the default mode (``set_b2b``)."""
+        names = self.cfg_names()
+        out = {}
+        for i in range(len(self.program.ops)):
+            c = int(self.lib.vgh_net_op_cfg(self._net, i))
+            if c >= 0:
+                out[i] = names[c]
+        return out
+
     def cfg_ok(self, cfg: int, op: dict) -> bool:
         """Can tile ``cfg`` of this engine's table run ``op`` (tuning tools)?"""
         return tile_can_run(self.lib, self.program, self.precision, cfg, op)

@@ -126,6 +126,13 @@ int vgh_net_forward_graph(vgh_net* net, void* stream);
 void* vgh_net_buffer(vgh_net* net, int buf_id);         /* device pointer of an activation buffer   */
 int64_t vgh_net_buffer_bytes(vgh_net* net, int buf_id); /* bytes for max_batch                       */
 int vgh_net_set_cfg(vgh_net* net, int op_index, int cfg);
+/* Read-only: the tile configuration SELECTED for op `op_index` for the arena batch -- the one vgh_net_set_cfg left in place, else the automatic choice resolved at
+ * vgh_net_create.  An index into vgh_conv_cfg_name, or into vgh_conv_split_cfg_name for a split-precision / fp16 net; -1 for an op that is not a conv on a tile table
+ * (stem, pools, forks, the convs of an fp32 net) and for a bad index.  The selection is what launches, with three exceptions: (a) vgh_net_set_cfg validates nothing for
+ * a split-precision / fp16 net -- a forced tile that the split launcher refuses for the launch at hand runs the automatic tile instead, silently; (b) a pipelined
+ * halo-patch ("q") tile that cannot store the op's channel layout launches its "p" twin; (c) the ops of a back-to-back pair launch together on the pair's tile
+ * (vgh_net_set_b2b): the index is that of their own launches. */
+int vgh_net_op_cfg(vgh_net* net, int op_index);
 /* Batch split (1..4, default 1): vgh_net_forward runs the batch as `nsplit` independent sub-batches on net-owned lane streams
  * (forked from / joined into `stream`), so that the fixed cost of every launch -- dispatch, tile prologue and first-load
  * latency, epilogue store burst, tail -- of one sub-batch hides under the main loops of the others.  Results are identical

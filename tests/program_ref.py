@@ -121,12 +121,22 @@ def fp16_weights(P, w_all):
 # per-op checker of a whole forward (tests/test_gpu_tuned_ops.py on the GPU; tests/test_host_logic.py proves on the CPU that it discriminates)
 # ------------------------------------------------------------------------------------------------------
 # |fp32 evaluation - float64 evaluation| at the output of a fused chain, both with bf16 storage: two correct evaluations differ where an intermediate value (stem or
-# downsample output) lands on the other side of a bf16 rounding boundary.  MEASURED on the CPU alone (no kernel involved; `python tests/program_ref.py` prints it; x86-64,
+# downsample output) lands on the other side of a bf16 rounding boundary.  MEASURED on the CPU alone (no kernel involved; `python tests/program_ref.py [size ...]` prints it; x86-64,
 # torch CPU convolutions, seed-7 weights, two u8 images of seed 640): the chains of L @640 and M @640 (the l64 / m32 programs of tests/test_gpu_tuned_ops.py) below -- the
 # worst is one bf16 ulp of an output in [16, 32).  A chain is held to the single-op tolerance plus TWICE the worst value: either side of the comparison may flip.
 CHAIN_FLOOR_MEASURED = {"vgg_heads_l@640": {"backbone.stage1.blocks.conv1|conv2": 0.015625, "neck.neck2.blocks.conv1|conv2": 0.125},
-                        "vgg_heads_m@640": {"backbone.stage1.blocks.conv1|conv2": 0.015625, "neck.neck2.blocks.conv1|conv2": 0.125}}
-CHAIN_FLOOR = max(v for d in CHAIN_FLOOR_MEASURED.values() for v in d.values())  # 0.125
+                        "vgg_heads_m@640": {"backbone.stage1.blocks.conv1|conv2": 0.015625, "neck.neck2.blocks.conv1|conv2": 0.125},
+                        # the other bf16 programs of OFFPATH_CASES, measured the same way (two u8 images of seed = image size): each is held to ITS OWN worst value
+                        # (chain_floor_for); none of them moves CHAIN_FLOOR
+                        "vgg_heads_l@320": {"backbone.stage1.blocks.conv1|conv2": 0.015625, "neck.neck2.blocks.conv1|conv2": 0.125},
+                        "vgg_heads_m@320": {"backbone.stage1.blocks.conv1|conv2": 0.0078125, "neck.neck2.blocks.conv1|conv2": 0.125},
+                        "vgg_heads_m@352": {"backbone.stage1.blocks.conv1|conv2": 0.015625, "neck.neck2.blocks.conv1|conv2": 0.0625},
+                        "vgg_heads_l@416": {"backbone.stage1.blocks.conv1|conv2": 0.015625, "neck.neck2.blocks.conv1|conv2": 0.125},
+                        "vgg_heads_l@480": {"backbone.stage1.blocks.conv1|conv2": 0.015625, "neck.neck2.blocks.conv1|conv2": 0.125},
+                        "vgg_heads_m@736": {"backbone.stage1.blocks.conv1|conv2": 0.015625, "neck.neck2.blocks.conv1|conv2": 0.125},
+                        "vgg_heads_l@1280": {"backbone.stage1.blocks.conv1|conv2": 0.015625, "neck.neck2.blocks.conv1|conv2": 0.25},  # one bf16 ulp of an output in [32, 64)
+                        "vgg_heads_m@1280": {"backbone.stage1.blocks.conv1|conv2": 0.015625, "neck.neck2.blocks.conv1|conv2": 0.125}}
+CHAIN_FLOOR = max(v for k in ("vgg_heads_l@640", "vgg_heads_m@640") for v in CHAIN_FLOOR_MEASURED[k].values())  # 0.125: the 640 programs only, whatever the others measure
 
 # absolute + relative tolerance of one fp16x3 conv with O(1) values (tests/test_gpu_split.py TOL[FMT_F16X2]); scaled by max(1, max|e|) of the op's output
 F16X3_TOL = (2e-5, 1e-5)
@@ -173,11 +183,12 @@ def run_chain(P, chain, got, image, w_all, b_all, f64: bool = False):
     return exp[P.ops[chain[-1]]["out_buf"]]
 
 
-def op_tolerance(mode: str, is_f32: bool, e, chained: bool = False):
-    """The project's per-op tolerances (test_network_every_op, test_fp16_network_every_op, test_gpu_split.TOL) for an expected tensor `e` (the op's own channels)."""
+def op_tolerance(mode: str, is_f32: bool, e, chained: bool = False, floor: float = None):
+    """The project's per-op tolerances (test_network_every_op, test_fp16_network_every_op, test_gpu_split.TOL) for an expected tensor `e` (the op's own channels).
+    floor: the chain allowance of the program when it is not the global CHAIN_FLOOR (chain_floor_for)."""
     if mode == "bf16":
         tol = (2e-3 + 1e-4 * e.abs()) if is_f32 else (2e-2 + 1.0 / 64 * e.abs())  # bf16: 2 ulps (accumulation order can cross a rounding boundary)
-        return tol + 2.0 * CHAIN_FLOOR if chained else tol
+        return tol + 2.0 * (CHAIN_FLOOR if floor is None else floor) if chained else tol
     assert not chained, "only bf16 programs have fused chains"
     if mode == "fp16":
         return (2e-3 + 2e-4 * e.abs()) if is_f32 else (1e-3 + 1.0 / 1024 * e.abs())  # exact operands: one fp16 ulp + accumulation-order slack
@@ -187,12 +198,12 @@ def op_tolerance(mode: str, is_f32: bool, e, chained: bool = False):
     raise ValueError(mode)
 
 
-def check_ops(P, got, image, probes, mode: str = "bf16", chains=(), tiles=None, w_all=None, b_all=None):
+def check_ops(P, got, image, probes, mode: str = "bf16", chains=(), tiles=None, w_all=None, b_all=None, floor: float = None):
     """Every op of kind 0 / 1 / 2 of a forward against run_op on the forward's OWN inputs of that op (no error accumulates across layers).
     got[b]: float32 CPU tensor [len(probes), h, w, pitch] of buffer b for the probe images; image: the probe images (u8 NHWC / f32 NCHW); probes: their indices in the
     batch (for the messages).  mode: "bf16" (bf16-emulating fp32 reference), "fp16" (float64 reference on the prescaled fp16 weights: pass fp16_weights as w_all),
     "fp16x3" (float64 reference).  chains (fused_chains): the ops of a chain are checked as one reference chain at the last op's output, and the tensors between them must
-    be all zero (never written).  tiles {op index: tile name}: for the messages.
+    be all zero (never written).  tiles {op index: tile name}: for the messages.  floor: op_tolerance's.
     Returns dict(single=ops checked singly, chained=ops inside chains, failures=[(op name, message)]); nothing is raised for a mismatch."""
     if w_all is None:
         w_all, b_all = P.arrays()
@@ -205,7 +216,7 @@ def check_ops(P, got, image, probes, mode: str = "bf16", chains=(), tiles=None, 
         op = P.ops[op_idx]
         ob, _ = own_channels(P, op)
         a, e = seg(P, op, a_buf), seg(P, op, e_buf)
-        tol = op_tolerance(mode, P.bufs[ob]["is_f32"] == 1, e, chained=len(names) > 1)
+        tol = op_tolerance(mode, P.bufs[ob]["is_f32"] == 1, e, chained=len(names) > 1, floor=floor)
         err = (a - e).abs()
         bad = ~(err <= tol)  # (a NaN is a mismatch)
         if not bool(bad.any()):
@@ -272,22 +283,102 @@ TUNED_CASES = {
 }
 
 
+# selections the benchmark never runs, checked op by op by tests/test_gpu_offpath_ops.py: id -> (variant, image size, max_batch, lanes, precision[, images forwarded]).
+# tests/test_host_logic.py::test_every_table_pair_of_the_sweep_has_a_reference_checked_case holds TUNED_CASES + OFFPATH_CASES to every (GEMM shape, tile) pair the table
+# can select over M / L x {320, 640, 1280} x max_batch {1, 2, 3, 8, 16, 17, 32, 33, 64} x lanes {1, 2} x {bf16, fp16, fp16x3}: a table entry added without a case fails there.
+OFFPATH_CASES = {
+    # sizes the table has no entry for: the class heuristic (bf16) / the split pick rules (fp16, fp16x3) choose every tile, on ragged pyramids
+    "m5_352x2": ("vgg_heads_m", 352, 5, 2, "bf16"),  # uneven lanes (3 + 2), final maps 11 x 11
+    "l3_416x1": ("vgg_heads_l", 416, 3, 1, "bf16"),
+    "l2_480": ("vgg_heads_l", 480, 2, 1, "bf16"),  # the latency-lane schedule on 15 x 15 maps
+    "m20_736x2": ("vgg_heads_m", 736, 20, 2, "bf16"),  # the two largest pixel buckets of the heuristic with ragged maps
+    "m3_352_fp16x3": ("vgg_heads_m", 352, 3, 1, "fp16x3"),
+    "l3_416_fp16": ("vgg_heads_l", 416, 3, 1, "fp16"),
+    "l32_fp16x1": ("vgg_heads_l", 640, 32, 1, "fp16"),  # no table entry applies
+    # table pairs no benchmarked program selects: mostly the single-lane buckets (what an engine uses unless set_split is called)
+    "l32x1": ("vgg_heads_l", 640, 32, 1, "bf16"),
+    "m32x1": ("vgg_heads_m", 640, 32, 1, "bf16"),
+    "m16x1": ("vgg_heads_m", 640, 16, 1, "bf16"),
+    "l8x1": ("vgg_heads_l", 640, 8, 1, "bf16"),
+    "l17x2": ("vgg_heads_l", 640, 17, 2, "bf16"),  # the bucket edge, lanes of 9 and 8
+    "l4_1280x1": ("vgg_heads_l", 1280, 4, 1, "bf16"),
+    "m4_1280x1": ("vgg_heads_m", 1280, 4, 1, "bf16"),
+    "l8_320x1": ("vgg_heads_l", 320, 8, 1, "bf16"),
+    "m8_320x1": ("vgg_heads_m", 320, 8, 1, "bf16"),
+    "l1_320": ("vgg_heads_l", 320, 1, 1, "bf16"),
+    # what the completeness sweep demanded beyond the above (17 is the smallest batch of the b32 bucket, 33 of the b64 bucket)
+    "m17_fp16x2": ("vgg_heads_m", 640, 17, 2, "fp16"),
+    "m33_320x1": ("vgg_heads_m", 320, 33, 1, "bf16"),
+    "l17_fp16x3x1": ("vgg_heads_l", 640, 17, 1, "fp16x3"),
+    "l17_320_fp16x2": ("vgg_heads_l", 320, 17, 2, "fp16"),
+    "l17_320x2": ("vgg_heads_l", 320, 17, 2, "bf16"),
+    "m17_1280_fp16x3x1": ("vgg_heads_m", 1280, 17, 1, "fp16x3"),
+    "m17_1280x1": ("vgg_heads_m", 1280, 17, 1, "bf16"),
+    "m33_1280_fp16x2": ("vgg_heads_m", 1280, 33, 2, "fp16", 2),  # 2 images forwarded (one per lane): a float64 reference of two 1280 probes took 16 s, of one 4.5 s
+    "l1_1280": ("vgg_heads_l", 1280, 1, 1, "bf16"),
+    "l17_320_fp16x3x1": ("vgg_heads_l", 320, 17, 1, "fp16x3"),
+    "m33_320_fp16x2": ("vgg_heads_m", 320, 33, 2, "fp16"),
+    "l33x1": ("vgg_heads_l", 640, 33, 1, "bf16"),
+    "l17_320x1": ("vgg_heads_l", 320, 17, 1, "bf16"),
+    "l33_320x2": ("vgg_heads_l", 320, 33, 2, "bf16"),
+    "l33_320_fp16x2": ("vgg_heads_l", 320, 33, 2, "fp16"),
+    "l17_1280_fp16x2": ("vgg_heads_l", 1280, 17, 2, "fp16", 2),  # 2 images forwarded, as above (two probes: 22 s, one: 6.4 s)
+    # fewer images than max_batch on a tuned engine: the tiles-per-workgroup loops of the persistent tiles depend on the image count
+    # (the two 1280 fp16 cases above are of this kind too: their max_batch picks the table bucket, their batch is cut for the reference's sake)
+    "l64_fwd37": ("vgg_heads_l", 640, 64, 2, "bf16", 37),  # lanes of 19 and 18
+    "m32_fwd1x2": ("vgg_heads_m", 640, 32, 2, "bf16", 1),  # the second lane is empty
+}
+OFF_TABLE = ("m5_352x2", "l3_416x1", "l2_480", "m20_736x2", "m3_352_fp16x3", "l3_416_fp16", "l32_fp16x1")  # no table entry applies to any of their convs
+PARTIAL_BATCH = tuple(c for c, t in OFFPATH_CASES.items() if len(t) > 5)
+
+
+def case_tuple(cid: str):
+    """(variant, image size, max_batch, lanes, precision, images forwarded or None) of a TUNED_CASES / OFFPATH_CASES id."""
+    t = TUNED_CASES[cid] if cid in TUNED_CASES else OFFPATH_CASES[cid]
+    return (*t[:5], t[5] if len(t) > 5 else None)
+
+
+def chain_floor_for(P) -> float:
+    """The chain allowance of a bf16 OFFPATH_CASES program: the worst of ITS OWN measured |fp32 - float64| chain values (CHAIN_FLOOR_MEASURED).  The nine benchmarked cases
+    keep the global CHAIN_FLOOR whatever any other program measures."""
+    return max(CHAIN_FLOOR_MEASURED[f"{P.variant}@{P.image_size}"].values())
+
+
+def table_pair(P, op, tile: str):
+    """What the completeness sweep counts as one selection of the table: (precision, GEMM shape, ksize, stride, residual, epilogue class, tile name)."""
+    from head_detector_amd.engine import _epilogue_class
+
+    return (P.precision, tuple(op["gemm"]), op["ksize"], op["stride"], op.get("res_buf", -1) >= 0, _epilogue_class(op), tile)
+
+
+@functools.lru_cache(maxsize=None)
+def _state_dict(variant, seed):
+    from head_detector_amd import arch
+
+    return arch.random_state_dict(variant, seed)  # (build_program folds it into arrays of its own and leaves it as it is)
+
+
 @functools.lru_cache(maxsize=None)
 def _built_program(variant, S, precision, seed):
     from head_detector_amd import arch
 
-    return arch.build_program(variant, arch.random_state_dict(variant, seed), S, precision)
+    return arch.build_program(variant, _state_dict(variant, seed), S, precision)
 
 
-def case_program(cid: str, seed: int = 7):
-    """The op program VGHeadsEngine(variant, image_size=S, max_batch=MB, seed=seed, precision=prec) runs for a TUNED_CASES id, built on the host (no GPU, no library)."""
+def program_for(variant, S, MB, prec, seed: int = 7):
+    """The op program VGHeadsEngine(variant, image_size=S, max_batch=MB, seed=seed, precision=prec) runs, built on the host (no GPU, no library)."""
     from head_detector_amd import arch
     from head_detector_amd.engine import LATENCY_MAX_BATCH
 
-    variant, S, MB, _, prec = TUNED_CASES[cid]
     P = copy.copy(_built_program(variant, S, prec, seed))
     P.ops = [dict(op) for op in P.ops]
     return arch.schedule_latency(P) if MB <= LATENCY_MAX_BATCH else P
+
+
+def case_program(cid: str, seed: int = 7):
+    """program_for a TUNED_CASES / OFFPATH_CASES id."""
+    variant, S, MB, _, prec, _ = case_tuple(cid)
+    return program_for(variant, S, MB, prec, seed)
 
 
 def chain_floor(P, image):
@@ -310,7 +401,8 @@ if __name__ == "__main__":  # python tests/program_ref.py: re-measures CHAIN_FLO
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from head_detector_amd import arch
 
-    for variant in ("vgg_heads_l", "vgg_heads_m"):
-        Q = arch.build_program(variant, arch.random_state_dict(variant, 7), 640)
-        img = torch.randint(0, 256, (2, 640, 640, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(640))
-        print(variant, chain_floor(Q, img))
+    progs = sorted({(t[0], t[1]) for t in list(TUNED_CASES.values()) + list(OFFPATH_CASES.values()) if t[4] == "bf16"}, key=lambda p: (p[1], p[0]))
+    for variant, S in [p for p in progs if not sys.argv[1:] or str(p[1]) in sys.argv[1:]]:
+        Q = arch.build_program(variant, arch.random_state_dict(variant, 7), S)
+        img = torch.randint(0, 256, (2, S, S, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(S))
+        print(f'"{variant}@{S}": {chain_floor(Q, img)},', flush=True)

@@ -92,6 +92,11 @@ F16_CASES = [
     (3, 20, 20, 192, 192, 1, 1),
     (1, 33, 17, 64, 96, 3, 2),
     (1, 5, 5, 32, 13, 1, 1),
+    # ragged maps under every tile vgh_conv_split_cfg_ok admits (a forced tile that the launch itself refuses runs the launcher's own pick under that name: vgh_conv2d has no
+    # fallback tile to offer, the split launcher then picks -- as for every row of this list)
+    (2, 11, 13, 96, 96, 3, 1),    # odd map, 143 pixels per image: pixel tiles straddle images
+    (1, 22, 44, 128, 128, 3, 1),  # ragged against 8, 16, 32 and 40
+    (3, 9, 19, 192, 192, 3, 1),   # K = 1728
 ]
 
 

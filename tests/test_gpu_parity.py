@@ -377,7 +377,48 @@ CONV_CASES = [
     (2, 16, 48, 96, 96, 3, 1),
     (2, 32, 48, 96, 192, 3, 2),  # the r tile's shapes (csrc/ds_b2b.hip: 96 input channels, stride 2, whole 8 x 8 output tiles): two cout halves
     (3, 16, 32, 96, 96, 3, 2),
+    # where tiles break: ragged maps under 96- / 128-wide cout tiles and the K loops the network reaches (K = 1728, 2304, 4608: ring depth, stage wrap-around, an odd or
+    # even count of K steps)
+    (2, 11, 13, 96, 96, 3, 1),  # odd map, 96-wide cout tiles; 143 pixels per image: linear 128-pixel tiles straddle images
+    (1, 22, 44, 128, 128, 3, 1),  # 128-wide tiles; ragged against 8, 16, 32 and 40
+    (3, 9, 19, 192, 192, 3, 1),  # K = 1728; Ho 9 and Wo 19 keep the s tiles' 4 x 8 sub-patches legal and moved back
+    (1, 13, 13, 256, 256, 3, 1),  # K = 2304
+    (1, 8, 12, 512, 128, 3, 1),  # K = 4608, the longest K of the network
+    (2, 23, 45, 96, 192, 3, 2),  # odd input, 12 x 23 output: the r tile must refuse it, every other stride-2 tile must run it
+    (1, 44, 44, 192, 384, 3, 2),  # stride 2, K = 1728
+    (3, 11, 11, 384, 192, 1, 1),  # 1x1, 363 pixels
+    (2, 19, 19, 576, 192, 1, 1),  # 1x1, K = 576
 ]
+
+
+class _LaunchPredicate:
+    """The library's OWN launch-time predicate for one conv, asked without launching anything: a one-op network of exactly _run_conv's geometry (vgh_net_create), on which
+    vgh_net_set_cfg keeps a forced tile only if the launch-time check admits it for this very launch (it logs and drops it otherwise) and vgh_net_op_cfg reads the answer
+    back.  vgh_conv_cfg_ok knows the conv's class only; this one knows the map, the channels and the batch (s tiles: maps of at least 4 x 8; r / w tiles: their input
+    channels and whole 8 x 8 tiles; the ping-pong tiles' 2 GiB rule)."""
+
+    def __init__(self, lib, B, H, W, Cin, Cout, k, stride, out_coff=8, out_f32=False, split=None, res=False):
+        from head_detector_amd import _lib
+
+        self.lib, self._lib = lib, _lib
+        rp = (Cout + 31) // 32 * 32
+        Ho, Wo = (H + 2 * (k // 2) - k) // stride + 1, (W + 2 * (k // 2) - k) // stride + 1
+        bufs = [_lib.BufDesc(H, W, Cin, 0, 0.0), _lib.BufDesc(Ho, Wo, rp + 16, 1 if out_f32 else 0, 0.0)] + ([_lib.BufDesc(Ho, Wo, Cout, 0, 0.0)] if res else [])
+        op = _lib.OpDesc(kind=1, in_buf=0, in_coff=0, cin=Cin, out_buf=1, out_coff=out_coff if not split else split[1], cout_pad=rp, cout_store=Cout,
+                         out_split=rp if not split else split[0], out_coff2=0 if not split else split[2], res_buf=2 if res else -1, res_coff=0, alpha=0.7 if res else 0.0,
+                         ksize=k, stride=stride, act=1, shuffle=0, w_off=0, b_off=0, force_cfg=-1, lane=0, grp_cout=0, grp_in_stride=0)
+        w, b = np.zeros(rp * k * k * Cin, np.float32), np.zeros(rp, np.float32)
+        self.net = C.c_void_p()
+        _lib.check(lib.vgh_net_create(torch.cuda.current_device(), 32, B, (_lib.BufDesc * len(bufs))(*bufs), len(bufs), (_lib.OpDesc * 1)(op), 1, _lib.ptr(w), w.size, _lib.ptr(b), b.size,
+                                      C.byref(self.net)))
+        assert lib.vgh_net_op_cfg(self.net, 0) >= 0 and lib.vgh_net_op_cfg(self.net, 1) == -1
+
+    def __call__(self, cfg):
+        self._lib.check(self.lib.vgh_net_set_cfg(self.net, 0, cfg))
+        return self.lib.vgh_net_op_cfg(self.net, 0) == cfg  # (a refused tile: the automatic one, which `ok` is asked about too -- it then answers for itself)
+
+    def close(self):
+        self.lib.vgh_net_destroy(self.net)
 
 
 @pytest.mark.parametrize("case", CONV_CASES)
@@ -392,22 +433,34 @@ def test_conv_all_configs_vs_torch(gpu_lib, case):
     rp = (Cout + 31) // 32 * 32
     ncfg = gpu_lib.vgh_conv_num_cfgs()
     tested = 0
-    for cfg in [-1] + list(range(ncfg)):
-        out_f32 = Cout % 4 != 0
-        for oc0 in (8, 4):  # 8: LDS-transposed 16-byte epilogue (when Cout % 8 == 0); 4: general epilogue
-            fast = int(oc0 == 8 and Cout % 8 == 0 and not out_f32)
-            if cfg >= 0 and not gpu_lib.vgh_conv_cfg_ok(cfg, k, stride, rp, fast, 0):
-                continue
-            if cfg >= 0 and gpu_lib.vgh_conv_cfg_name(cfg).decode()[0] == "r" and not (Cin == 96 and H % 16 == 0 and W % 16 == 0):
-                continue  # (the r tile's conditions on the input: vgh_conv_cfg_ok sees the output side only)
-            if cfg >= 0 and gpu_lib.vgh_conv_cfg_name(cfg).decode()[0] == "w" and not (Cin == gpu_lib.vgh_conv_cfg_cout_tile(cfg) and H % 8 == 0 and W % 8 == 0):
-                continue  # (the w tiles: cin = the tile's 96 / 128, whole 8 x 8 tiles)
-            out, ref, st, o0 = _run_conv(gpu_lib, x, Wt, b, k, stride, cfg=cfg, out_f32=out_f32, out_coff=oc0)
-            _assert_close(out[..., o0 : o0 + st], ref[..., :st], out_f32, f"{case} cfg={cfg} out_coff={oc0}")
-            assert float((out[..., :o0] + 768.0).abs().max()) == 0.0, "wrote outside its channel range"
-            assert float((out[..., o0 + st :] + 768.0).abs().max()) < 1.0, "wrote past cout_store"
-            tested += 1
+    out_f32 = Cout % 4 != 0
+    launch_ok = {oc0: _LaunchPredicate(gpu_lib, B, H, W, Cin, Cout, k, stride, out_coff=oc0, out_f32=out_f32) for oc0 in (8, 4)}
+    refused, n_s = set(), 0
+    try:
+        for cfg in [-1] + list(range(ncfg)):
+            for oc0 in (8, 4):  # 8: LDS-transposed 16-byte epilogue (when Cout % 8 == 0); 4: general epilogue
+                fast = int(oc0 == 8 and Cout % 8 == 0 and not out_f32)
+                if cfg >= 0 and not gpu_lib.vgh_conv_cfg_ok(cfg, k, stride, rp, fast, 0):
+                    continue
+                if cfg >= 0 and not launch_ok[oc0](cfg):
+                    refused.add(gpu_lib.vgh_conv_cfg_name(cfg).decode())  # exactly what the library's launch-time predicate refuses for THIS launch (the r / w tiles' conditions on
+                    # the input channels and whole 8 x 8 tiles, the s tiles' smallest map: vgh_conv_cfg_ok sees the conv's class only); nothing is caught
+                    continue
+                out, ref, st, o0 = _run_conv(gpu_lib, x, Wt, b, k, stride, cfg=cfg, out_f32=out_f32, out_coff=oc0)
+                _assert_close(out[..., o0 : o0 + st], ref[..., :st], out_f32, f"{case} cfg={cfg} out_coff={oc0}")
+                assert float((out[..., :o0] + 768.0).abs().max()) == 0.0, "wrote outside its channel range"
+                assert float((out[..., o0 + st :] + 768.0).abs().max()) < 1.0, "wrote past cout_store"
+                tested += 1
+                n_s += cfg >= 0 and gpu_lib.vgh_conv_cfg_name(cfg).decode()[0] == "s"
+    finally:
+        for p_ in launch_ok.values():
+            p_.close()
     assert tested >= 2
+    assert all(n[0] in "rws" for n in refused), f"only the r / w / s tiles have launch-time conditions on the map: {sorted(refused)}"
+    if case == (2, 23, 45, 96, 192, 3, 2):
+        assert sorted(refused) == ["r8x8x96_n4"]
+    if case in ((3, 9, 19, 192, 192, 3, 1), (2, 11, 13, 96, 96, 3, 1)):
+        assert not [n for n in refused if n[0] == "s"] and n_s >= 1, (sorted(refused), n_s)  # the s tiles RAN here, their 4 x 8 sub-patches moved back inside the map
 
 
 @pytest.mark.parametrize("B,H,W,Cout,split", [(5, 48, 64, 96, None), (3, 32, 32, 192, None), (2, 32, 48, 192, (96, 104, 0)), (40, 16, 16, 96, None)])
@@ -567,6 +620,35 @@ def test_conv_epilogues(gpu_lib):
         out, ref, st, _ = _run_conv(gpu_lib, x, Wt, b, 3, 1, split=(64, 72, 0), cfg=cfg)
         _assert_close(out[..., 72:136], ref[..., :64], False, f"split seg0 cfg={cfg}")
         _assert_close(out[..., 0:64], ref[..., 64:128], False, f"split seg1 cfg={cfg}")
+    # the residual and the two-segment store again where tiles break: a (2, 11, 13) map (odd, 143 pixels per image), 96 and 128 couts, every tile the library admits for
+    # that launch; nothing written outside the channel ranges
+    xr_ = torch.randn(2, 11, 13, Cin, generator=g)
+    for co in (96, 128):
+        Wr_, br_ = torch.randn(co, 3, 3, Cin, generator=g) * 0.06, torch.randn(co, generator=g)
+        rr_ = torch.randn(2, 11, 13, co, generator=g)
+        h = co // 2
+        ok_res = _LaunchPredicate(gpu_lib, 2, 11, 13, Cin, co, 3, 1, res=True)
+        ok_seg = _LaunchPredicate(gpu_lib, 2, 11, 13, Cin, co, 3, 1, split=(h, h + 8, 0))
+        n_run = 0
+        try:
+            for cfg in range(-1, gpu_lib.vgh_conv_num_cfgs()):
+                if cfg >= 0 and not gpu_lib.vgh_conv_cfg_ok(cfg, 3, 1, co, 1, 0):
+                    continue
+                if cfg < 0 or ok_res(cfg):
+                    out, ref, st, o0 = _run_conv(gpu_lib, xr_, Wr_, br_, 3, 1, res=rr_, alpha=0.7, cfg=cfg)
+                    _assert_close(out[..., o0 : o0 + st], ref, False, f"ragged residual cout={co} cfg={cfg}")
+                    assert float((out[..., :o0] + 768.0).abs().max()) == 0.0 and float((out[..., o0 + st :] + 768.0).abs().max()) == 0.0, f"cout={co} cfg={cfg}: wrote outside its channel range"
+                    n_run += 1
+                if cfg < 0 or ok_seg(cfg):
+                    out, ref, st, _ = _run_conv(gpu_lib, xr_, Wr_, br_, 3, 1, split=(h, h + 8, 0), cfg=cfg)
+                    _assert_close(out[..., h + 8 : co + 8], ref[..., :h], False, f"ragged split seg0 cout={co} cfg={cfg}")
+                    _assert_close(out[..., 0 : co - h], ref[..., h:co], False, f"ragged split seg1 cout={co} cfg={cfg}")
+                    assert float((out[..., co - h : h + 8] + 768.0).abs().max()) == 0.0 and float((out[..., co + 8 :] + 768.0).abs().max()) == 0.0, f"cout={co} cfg={cfg}: wrote outside its two segments"
+                    n_run += 1
+        finally:
+            ok_res.close()
+            ok_seg.close()
+        assert n_run >= 40, n_run
     # fp32 output with a ragged channel count (prediction convs): 69 channels
     W69 = torch.randn(69, 1, 1, Cin, generator=g) * 0.1
     out, ref, st, o0 = _run_conv(gpu_lib, x, W69, torch.randn(69, generator=g), 1, 1, act=0, out_f32=True, out_coff=5)

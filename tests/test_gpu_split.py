@@ -130,6 +130,11 @@ SPLIT_CONV_CASES = [
     (2, 40, 40, 64, 128, 3, 1),     # 40-wide map: row-strip patch tile
     (1, 21, 37, 32, 64, 3, 1),      # ragged: implicit GEMM
     (2, 16, 16, 256, 32, 3, 1),     # patch tile 16x16x32, 8 channel blocks per segment
+    # ragged maps: this test runs the AUTOMATIC tile only, which on these maps is a 64-pixel implicit-GEMM tile (pick_split_cfg); the split halo-patch tiles meet ragged maps
+    # in the forced-tile loop of tests/test_gpu_fp16.py alone
+    (2, 11, 13, 96, 96, 3, 1),      # 143 pixels per image: pixel tiles straddle images
+    (1, 22, 44, 128, 128, 3, 1),
+    (3, 9, 19, 192, 192, 3, 1),     # K = 1728
 ]
 
 
@@ -357,11 +362,13 @@ def _assert_north_star(r):
     assert r["kept"] >= 4
 
 
-@pytest.mark.parametrize("variant,okey,S,B", [("vgg_heads_m", "m", 160, 2), ("vgg_heads_l", "l", 160, 2), ("vgg_heads_m", "m", 640, 2), ("vgg_heads_l", "l", 640, 1)],
-                         ids=["m160", "l160", "m640", "l640"])
+@pytest.mark.parametrize("variant,okey,S,B", [("vgg_heads_m", "m", 160, 2), ("vgg_heads_l", "l", 160, 2), ("vgg_heads_m", "m", 640, 2), ("vgg_heads_l", "l", 640, 1),
+                                              ("vgg_heads_m", "m", 352, 2), ("vgg_heads_l", "l", 416, 1)],
+                         ids=["m160", "l160", "m640", "l640", "m352", "l416"])
 def test_fp16x3_matrix_core_mode_meets_north_star_tolerances(gpu_lib, flame_model, variant, okey, S, B):
     """The MFMA parity mode at BASELINE.json's bar against the unfused fp32 oracle -- at the benchmark's 640 x 640 geometry, every op
-    also against the fp32 torch executor on the engine's own inputs."""
+    also against the fp32 torch executor on the engine's own inputs.  m352 / l416: sizes off every table, pyramids of 44 / 22 / 11 and 52 / 26 / 13 -- head decode, top-k
+    and the candidate gather over 2541 and 3549 anchors, with level starts that are multiples of nothing."""
     # per op against a float64 evaluation of the same op on the engine's own inputs: what remains is the engine's fp32 accumulation -- a chain of
     # 3 * K / 16 MFMAs per output (432 at K = 2304), each adding into the running sum: measured 2e-5 .. 6e-5 of (|ref| + 1) on the longest chains
     # (the fp32 FMA kernel: 1.6e-5 .. 2.1e-5); the END-TO-END deviation below is what north_star's bar is stated on

@@ -134,7 +134,8 @@ def test_c_abi_library_exports_every_declared_symbol():
     exported = {ln.split()[-1] for ln in subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout.splitlines()
                 if " T " in ln and ln.split()[-1].startswith("vgh_")}  # the C symbols (mangled C++ internals do not start with vgh_)
     assert exported == declared, (exported ^ declared)
-    assert len(declared) <= 85
+    assert len(declared) <= 86  # (+ vgh_net_op_cfg, the read-only getter of the tile an op launches with)
+    assert lib.vgh_net_op_cfg(None, 0) == -1  # no net: not a conv on a tile table
     assert lib.vgh_version().startswith(b"vgh")
     assert lib.vgh_conv_num_cfgs() >= 4 and lib.vgh_conv_cfg_name(0)
     # host-only entry point: weight packing is a pure permutation + bf16 rounding of the dense weights
@@ -855,6 +856,84 @@ def test_every_table_entry_a_benchmarked_program_looks_up_can_run_its_op(cid):
     assert not stale, f"{cid}: table entries whose tile cannot run the op they are looked up for (load_tuning would drop them silently): {stale}"
 
 
+def _table_pairs(P, MB, lanes, lib=None):
+    """{program_ref.table_pair: op name} of the table entries pack.tile_names_for finds for this program; lib: only those whose tile engine.tile_can_run admits (what load_tuning applies)."""
+    from head_detector_amd import pack
+    from head_detector_amd.engine import tile_can_run, tile_names
+
+    index = {n: i for i, n in enumerate(tile_names(lib, P.precision))} if lib is not None else None
+    out = {}
+    for i, n in pack.tile_names_for(P, MB, lanes).items():
+        if index is None or (n in index and tile_can_run(lib, P, P.precision, index[n], P.ops[i])):
+            out[pr.table_pair(P, P.ops[i], n)] = P.ops[i]["name"]
+    return out
+
+
+def test_every_table_pair_of_the_sweep_has_a_reference_checked_case():
+    """A condition, not a measurement: every (GEMM shape, ksize, stride, residual, epilogue class, tile) the measured table selects over M / L x {320, 640, 1280} x
+    max_batch {1, 2, 3, 8, 16, 17, 32, 33, 64} x lanes {1, 2} x {bf16, fp16, fp16x3} is selected by a case of program_ref.TUNED_CASES or OFFPATH_CASES, whose every op
+    tests/test_gpu_tuned_ops.py / tests/test_gpu_offpath_ops.py hold to the plain reference.  A pair may be missing only if engine.tile_can_run refuses it (load_tuning
+    then does not apply it).  A table entry added later without a case fails here, on the CPU."""
+    lib = _lib.load()
+    covered = set()
+    for cid in list(pr.TUNED_CASES) + list(pr.OFFPATH_CASES):
+        variant, S, MB, lanes, prec, _ = pr.case_tuple(cid)
+        covered |= set(_table_pairs(pr.case_program(cid), MB, lanes))
+    missing, n_pairs, refused = {}, set(), set()
+    for variant in ("vgg_heads_m", "vgg_heads_l"):
+        for S in (320, 640, 1280):
+            for prec in ("bf16", "fp16", "fp16x3"):
+                for MB in (1, 2, 3, 8, 16, 17, 32, 33, 64):
+                    P = pr.program_for(variant, S, MB, prec)
+                    for lanes in (1, 2):
+                        every, runnable = _table_pairs(P, MB, lanes), _table_pairs(P, MB, lanes, lib)
+                        n_pairs |= set(every)
+                        refused |= set(every) - set(runnable)
+                        for pair, name in runnable.items():
+                            if pair not in covered:
+                                missing.setdefault(pair, (variant, S, MB, lanes, prec, name))
+    print(f"[table pairs] {len(n_pairs)} pairs in the sweep, {len(n_pairs & covered)} selected by a case, {len(refused)} refused by tile_can_run")
+    assert len(n_pairs) > 500
+    assert not missing, f"{len(missing)} table selections no TUNED_CASES / OFFPATH_CASES program runs (pair: first program that selects it): " + "; ".join(f"{k}: {v}" for k, v in list(missing.items())[:8])
+
+
+@pytest.mark.parametrize("cid", list(pr.OFFPATH_CASES))
+def test_every_offpath_program_builds_with_its_chains_and_its_measured_floor(cid):
+    """Host side of tests/test_gpu_offpath_ops.py: the program of every case builds (vgh_net_create takes any multiple of 32), the chains the default mode fuses for u8
+    images are the stem triple and the neck pair (bf16) or none (fp16 / fp16x3: fused_chains is asked with stem_fused False there), a bf16 program has its own measured
+    chain floor, the off-table cases find no table entry and hold a 3x3 / stride-1 conv on a map ragged in both directions, the table cases find entries that can run."""
+    from head_detector_amd import pack
+    from head_detector_amd.engine import tile_can_run, tile_names
+
+    variant, S, MB, lanes, prec, fwd = pr.case_tuple(cid)
+    P = pr.case_program(cid)
+    assert S % 32 == 0 and P.image_size == S and P.precision == prec and (fwd is None or 1 <= fwd < MB)
+    assert (cid in pr.PARTIAL_BATCH) == (fwd is not None)
+    if prec == "bf16":
+        chains = pr.fused_chains(P, True)
+        assert [len(c) for c in chains] == [3, 2] and chains[0][0] == 0 and P.ops[0]["kind"] == 0
+        assert set(pr.CHAIN_FLOOR_MEASURED[f"{variant}@{S}"]) == {P.ops[c[-1]]["name"] for c in chains}
+        assert 0.0 < pr.chain_floor_for(P) <= 0.25  # one bf16 ulp of an output below 64
+    found = pack.tile_names_for(P, MB, lanes)
+    if cid in pr.OFF_TABLE:
+        assert not found
+        maps = {(P.bufs[o["out_buf"]]["h"], P.bufs[o["out_buf"]]["w"]) for o in P.ops if o["kind"] == 1 and o["ksize"] == 3 and o["stride"] == 1}
+        assert any(h % 8 and w % 8 for h, w in maps), maps
+    else:
+        lib = _lib.load()
+        index = {n: i for i, n in enumerate(tile_names(lib, prec))}
+        assert found and not [(P.ops[i]["name"], n) for i, n in found.items() if n not in index or not tile_can_run(lib, P, prec, index[n], P.ops[i])]
+
+
+def test_chain_floor_of_the_benchmarked_cases_stays_where_it_was():
+    """The per-program floors of the off-path cases (the L @1280 neck chain measures 0.25) never widen what the nine benchmarked cases are held to."""
+    assert pr.CHAIN_FLOOR == 0.125
+    e = torch.tensor([1.0, 40.0])
+    assert torch.equal(pr.op_tolerance("bf16", False, e, chained=True), 2e-2 + e / 64 + 0.25)
+    assert torch.equal(pr.op_tolerance("bf16", False, e, chained=True, floor=0.0625), 2e-2 + e / 64 + 0.125)
+    assert torch.equal(pr.op_tolerance("bf16", False, e, chained=False, floor=0.25), 2e-2 + e / 64)
+
+
 @pytest.fixture(scope="module")
 def small_forward():
     """The CPU reference's own forward of a small program (M @192, two images) and the chains the engine's default mode fuses for u8 images."""
@@ -874,7 +953,7 @@ def _as_the_engine_leaves_it(P, bufs, chains):
     return bufs
 
 
-def _planted(forward, op, edit):
+def _planted(forward, op, edit, floor=None):
     """(report of check_ops, max |planted - clean|) for a forward whose op `op` went wrong in the LAST image only: `edit(P, image, bufs, op)` rewrites the op's output in the
     one-image views `bufs`, every later op then runs on what it left behind -- as in an engine with one wrong kernel."""
     P, image, full, chains = forward
@@ -887,7 +966,7 @@ def _planted(forward, op, edit):
     ob = pr.own_channels(P, op)[0]
     dev = float((mine[ob] - full[ob]).abs().max())
     assert all(torch.equal(a[0], b[0]) for a, b in zip(mine, full)), "faults go into the last image only"
-    return pr.check_ops(P, _as_the_engine_leaves_it(P, mine, chains), image, (0, 1), "bf16", chains), dev
+    return pr.check_ops(P, _as_the_engine_leaves_it(P, mine, chains), image, (0, 1), "bf16", chains, floor=floor), dev
 
 
 def _names_only(rep, op):
@@ -908,25 +987,34 @@ def _first(P, chains, pred):
     return next(op for i, op in enumerate(P.ops) if i not in inside and op["kind"] == 1 and pred(op))
 
 
+def _edit_shift_row(P, image, bufs, op):
+    row = bufs[op["out_buf"]][0, 5, :, op["out_coff"] : op["out_coff"] + op["cout_store"]]
+    row.copy_(torch.roll(row, 1, 0))
+
+
+def _edit_zero_block(P, image, bufs, op):
+    bufs[op["out_buf"]][0, :, :, op["out_coff2"] + 8 : op["out_coff2"] + 16] = 0
+
+
+def _edit_res_before_act(P, image, bufs, op):
+    tmp = [t.clone() for t in bufs]
+    pr.run_op(P, dict(op, res_buf=-1, act=0), tmp, image, True)  # the conv alone, before activation and residual
+    c0, n = op["out_coff"], op["cout_store"]
+    r = bufs[op["res_buf"]][..., op["res_coff"] : op["res_coff"] + n]
+    bufs[op["out_buf"]][..., c0 : c0 + n] = pr.rb(torch.relu(tmp[op["out_buf"]][..., c0 : c0 + n] + np.float32(op["alpha"]) * r), True)
+
+
 def test_per_op_checker_names_a_shifted_row_of_a_3x3_conv(small_forward):
     P, _, _, chains = small_forward
     op = _first(P, chains, lambda o: o["ksize"] == 3 and o["stride"] == 1 and o["res_buf"] < 0)
-
-    def edit(P, image, bufs, op):
-        row = bufs[op["out_buf"]][0, 5, :, op["out_coff"] : op["out_coff"] + op["cout_store"]]
-        row.copy_(torch.roll(row, 1, 0))
-
-    rep, dev = _planted(small_forward, op, edit)
+    rep, dev = _planted(small_forward, op, _edit_shift_row)
     assert dev > 0.0 and _names_only(rep, op), rep["failures"]
 
 
 def test_per_op_checker_names_a_zeroed_channel_block_of_the_second_store_segment(small_forward):
     """Planted in a CSP conv1|conv2 that runs as its own launch AND in the one that ends the stage-1 chain (judged at the wider chain tolerance)."""
     P, _, _, chains = small_forward
-
-    def edit(P, image, bufs, op):
-        bufs[op["out_buf"]][0, :, :, op["out_coff2"] + 8 : op["out_coff2"] + 16] = 0
-
+    edit = _edit_zero_block
     for op in (_first(P, chains, lambda o: o["cout_store"] > o["out_split"]), P.ops[chains[0][-1]]):
         assert op["cout_store"] > op["out_split"]
         rep, dev = _planted(small_forward, op, edit)
@@ -959,15 +1047,7 @@ def test_per_op_checker_names_an_spp_plane_pooled_with_the_wrong_window(small_fo
 def test_per_op_checker_names_a_residual_added_before_the_activation(small_forward):
     P, _, _, chains = small_forward
     op = _first(P, chains, lambda o: o["res_buf"] >= 0 and o["act"] == 1)
-
-    def edit(P, image, bufs, op):
-        tmp = [t.clone() for t in bufs]
-        pr.run_op(P, dict(op, res_buf=-1, act=0), tmp, image, True)  # the conv alone, before activation and residual
-        c0, n = op["out_coff"], op["cout_store"]
-        r = bufs[op["res_buf"]][..., op["res_coff"] : op["res_coff"] + n]
-        bufs[op["out_buf"]][..., c0 : c0 + n] = pr.rb(torch.relu(tmp[op["out_buf"]][..., c0 : c0 + n] + np.float32(op["alpha"]) * r), True)
-
-    rep, dev = _planted(small_forward, op, edit)
+    rep, dev = _planted(small_forward, op, _edit_res_before_act)
     assert dev > 0.0 and _names_only(rep, op), rep["failures"]
 
 
@@ -1006,6 +1086,29 @@ def test_chain_tolerance_covers_two_correct_references(small_forward):
         d = (a - e).abs()
         print(f"[chain floor] {last['name']}: max |fp32 - f64| {float(d.max())}, {float((d > 0).float().mean()):.2e} of the outputs differ")
         assert bool((d <= pr.op_tolerance("bf16", False, e, chained=True)).all()) and float(d.max()) <= 2 * pr.CHAIN_FLOOR, (last["name"], float(d.max()))
+
+
+def test_per_op_checker_on_an_off_table_program():
+    """The planted-fault checks above on an off-table program of program_ref.OFFPATH_CASES: M @352 (the m5_352x2 program: maps 88 / 44 / 22 / 11, ragged against every tile
+    shape).  The clean forward passes with every op counted, at the program's OWN chain floor; a shifted row of the last 3x3 / stride-1 conv on the 11 x 11 map, a zeroed
+    channel block behind the end of the stage-1 chain, a residual added before the activation and an SPP plane pooled with an 11-wide window (the 11 x 11 map tells 11 from
+    13 at its borders) are each named, at the op they were planted in and at no other."""
+    P = pr.case_program("m5_352x2")
+    image = torch.randint(0, 256, (2, 352, 352, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(352))
+    chains = pr.fused_chains(P, True)
+    forward = (P, image, pr.run_program(P, image, True), chains)
+    floor = pr.chain_floor_for(P)
+    assert floor == 0.0625 < pr.CHAIN_FLOOR
+    rep = pr.check_ops(P, _as_the_engine_leaves_it(P, forward[2], chains), image, (0, 1), "bf16", chains, floor=floor)
+    assert rep["failures"] == [] and rep["chained"] == 5 and rep["single"] + rep["chained"] == len(P.ops)
+    inside = {i for ch in chains for i in ch}
+    on_11 = [op for i, op in enumerate(P.ops) if i not in inside and op["kind"] == 1 and op["ksize"] == 3 and op["stride"] == 1 and op["res_buf"] < 0
+             and (P.bufs[op["out_buf"]]["h"], P.bufs[op["out_buf"]]["w"]) == (11, 11)]
+    plants = [(on_11[-1], _edit_shift_row), (P.ops[chains[0][-1]], _edit_zero_block), (_first(P, chains, lambda o: o["res_buf"] >= 0 and o["act"] == 1), _edit_res_before_act),
+              (next(o for o in P.ops if o["kind"] == 2), _spp_window_11)]
+    for op, edit in plants:
+        rep, dev = _planted(forward, op, edit, floor)  # (judged at the program's own chain floor, as on the GPU)
+        assert dev > 0.0 and _names_only(rep, op), (op["name"], dev, rep["failures"])
 
 
 def test_tuning_keys_set_fp32_output_and_pixel_shuffle_convs_apart():

@@ -102,7 +102,7 @@ def test_mesh_entry_points_abi():
     want = {"vghv_version", "vghv_last_error", "vghv_warp_crops", "vghv_draw_heads", "vghv_vertex_normals", "vghv_render_meshes"}
     assert declared == want and set(_lib_view.SYMBOLS) == want and _exported(_lib_view.LIB_PATH) == want  # exactly 6
     core = {s for s in _exported(_lib.LIB_PATH) if s.startswith("vgh")}
-    assert core == set(_lib.SYMBOLS) and len(core) == 85 and _lib.ABI_VERSION == 8 and not any(s.startswith("vghv_") for s in core)
+    assert core == set(_lib.SYMBOLS) and len(core) == 86 and _lib.ABI_VERSION == 8 and not any(s.startswith("vghv_") for s in core)
     fields = re.search(r"typedef struct vghv_mesh_job \{(.*?)\} vghv_mesh_job;", hdr, flags=re.S).group(1)
     names = [n for decl in fields.split(";") for n in re.findall(r"(\w+)\s*(?:\[\d+\])?\s*(?:,|$)", decl.strip().replace("*", " "))]
     J = _lib_view.MeshJob
