@@ -24,14 +24,14 @@ class Companion(NamedTuple):
     objdir: str
 
 
-RASTER_HEADERS = ["tile_fold.h"]  # the tile-major triangle fold: header-only, compiled into each of the three libraries that rasterise
+HOST_HEADERS = ["companion_host.h"]  # the host plumbing of every companion (codes, message, check macros, staging, queue-then-record): header-only
+RASTER_HEADERS = HOST_HEADERS + ["tile_fold.h"]  # the tile-major triangle fold: header-only, compiled into each of the three libraries that rasterise
 COMPANIONS = [  # built in this order, before the core
     # mesh benchmark metrics (Z_n, chamfer): float64 distances in a stated operation order, so no contraction into fused multiply-adds anywhere in this library
-    Companion("libvgheval.so", ["mesh_metrics.hip"], [], "vgh_eval.h", ["-ffp-contract=off"], "build_eval"),
+    Companion("libvgheval.so", ["mesh_metrics.hip"], HOST_HEADERS, "vgh_eval.h", ["-ffp-contract=off"], "build_eval"),
     Companion("libvghtex.so", ["texture.hip"], RASTER_HEADERS, "vgh_tex.h", [], "build_tex"),  # head textures (Sim3DR's render_texture)
     Companion("libvghvis.so", ["visibility.hip"], RASTER_HEADERS, "vgh_vis.h", [], "build_vis"),  # head visibility buffers
-    # result-side image helpers; vghv_internal.h is what its three sources share
-    Companion("libvghview.so", ["aligned.hip", "draw.hip", "mesh_render.hip"], ["vghv_internal.h"] + RASTER_HEADERS, "vgh_view.h", [], "build_view"),
+    Companion("libvghview.so", ["aligned.hip", "draw.hip", "mesh_render.hip"], RASTER_HEADERS, "vgh_view.h", [], "build_view"),  # result-side image helpers
 ]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]
 

@@ -7,54 +7,19 @@
 //   X = (X0[y] + adelta[x]) >> 5, Y likewise; source pixel (X >> 5, Y >> 5), fractions X & 31, Y & 31; weights 32 * {(32-fx)(32-fy), fx(32-fy),
 //   (32-fx)fy, fx fy} (sum 2^15); taps outside the source read 0; (sum + 2^14) >> 15.
 // PARITY UNPINNED against cv2 itself (absent from this image); bit-exact against tests/warp_affine_ref.py.
-// Self-contained on purpose: no csrc/vgh_internal.h, no object of libvgh.so (csrc/vghv_internal.h is what the view library's sources share); built with -fvisibility=hidden, only the vghv_* functions are exported.
-#include <stdarg.h>
-#include <stdio.h>
+// Self-contained on purpose: no csrc/vgh_internal.h, no object of libvgh.so (csrc/companion_host.h is what the companion libraries' sources share); built with -fvisibility=hidden, only the vghv_* functions are exported.
 #include <string.h>
 
 #include <map>
 #include <mutex>
 
-#include "vghv_internal.h"
-
-namespace vghv {
-
-thread_local char g_error[512] = "";
-
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-}
-
-const char* last_error() { return g_error; }
-
-int staging_reserve(Staging& s, size_t need, const char* who) {
-    if (s.recorded) VGHV_HIP(hipEventSynchronize(s.ev));
-    s.recorded = false;
-    if (!s.ev) VGHV_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    if (need <= s.bytes) return VGHV_OK;
-    hipHostFree(s.host);
-    hipFree(s.dev);
-    s.host = s.dev = nullptr;
-    s.bytes = 0;
-    const size_t cap = align16(need + need / 2);
-    if (hipHostMalloc((void**)&s.host, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&s.dev, cap) != hipSuccess) {
-        hipHostFree(s.host);
-        s.host = nullptr;
-        set_error("%s: allocating %zu bytes of staging failed", who, cap);
-        return VGHV_ERR_NOMEM;
-    }
-    s.bytes = cap;
-    return VGHV_OK;
-}
-
-}  // namespace vghv
+#include "../../include/vgh_view.h"
+#include "companion_host.h"
 
 namespace {
 
-using namespace vghv;
+using namespace companion;
+static_assert(VGHV_OK == OK && VGHV_ERR_INVALID == ERR_INVALID && VGHV_ERR_HIP == ERR_HIP && VGHV_ERR_NOMEM == ERR_NOMEM, "companion_host.h returns these codes");
 
 // device-side descriptor of one crop
 struct Crop {
@@ -109,7 +74,7 @@ __global__ __launch_bounds__(256) void warp_crops_kernel(const Crop* __restrict_
     }
 }
 
-// ---- staging: descriptors + tile list + tables of one call (vghv_internal.h) -----------------------------------------------------------
+// ---- staging: descriptors + tile list + tables of one call (companion_host.h) ----------------------------------------------------------
 std::mutex g_mutex;
 std::map<int, Staging> g_staging;
 
@@ -117,41 +82,41 @@ std::map<int, Staging> g_staging;
 
 extern "C" VGHV_API const char* vghv_version(void) { return "vghview 2 (gfx950)"; }
 
-extern "C" VGHV_API const char* vghv_last_error(void) { return vghv::last_error(); }
+extern "C" VGHV_API const char* vghv_last_error(void) { return last_error(); }
 
 extern "C" VGHV_API int vghv_warp_crops(const vghv_crop* crops, int n, const int32_t* tables, int64_t n_tables, uint8_t* dst_dev, int64_t dst_bytes, void* stream) {
-    VGHV_REQUIRE(n >= 0 && n_tables >= 0 && dst_bytes >= 0, "warp_crops: negative count");
-    if (n == 0) return VGHV_OK;
-    VGHV_REQUIRE(crops && tables, "warp_crops: null argument");
-    VGHV_REQUIRE(n_tables <= INT32_MAX, "warp_crops: %lld table entries exceed 2^31 - 1", (long long)n_tables);
+    CH_REQUIRE(n >= 0 && n_tables >= 0 && dst_bytes >= 0, "warp_crops: negative count");
+    if (n == 0) return OK;
+    CH_REQUIRE(crops && tables, "warp_crops: null argument");
+    CH_REQUIRE(n_tables <= INT32_MAX, "warp_crops: %lld table entries exceed 2^31 - 1", (long long)n_tables);
     int64_t n_tiles = 0;
     for (int i = 0; i < n; ++i) {  // everything is checked before anything is allocated, written or queued
         const vghv_crop& c = crops[i];
-        VGHV_REQUIRE(c.src_dev, "warp_crops: crop %d: null src_dev", i);
-        VGHV_REQUIRE(c.src_channels == 3, "warp_crops: crop %d: %d channels (needs 3: u8 RGB)", i, c.src_channels);
-        VGHV_REQUIRE(c.src_h >= 1 && c.src_w >= 1 && c.src_h <= VGHV_MAX_SIDE && c.src_w <= VGHV_MAX_SIDE, "warp_crops: crop %d: source %d x %d outside 1 .. %d", i, c.src_h,
-                     c.src_w, VGHV_MAX_SIDE);
-        VGHV_REQUIRE(c.src_pitch_bytes >= (int64_t)c.src_w * 3, "warp_crops: crop %d: src_pitch_bytes %lld < src_w * 3 = %lld", i, (long long)c.src_pitch_bytes,
-                     (long long)c.src_w * 3);
-        VGHV_REQUIRE(c.crop_w >= 0 && c.crop_h >= 0 && c.crop_w <= 65535 * TILE_W && c.crop_h <= 65535 * TILE_H, "warp_crops: crop %d: bad size %d x %d", i, c.crop_w, c.crop_h);
+        CH_REQUIRE(c.src_dev, "warp_crops: crop %d: null src_dev", i);
+        CH_REQUIRE(c.src_channels == 3, "warp_crops: crop %d: %d channels (needs 3: u8 RGB)", i, c.src_channels);
+        CH_REQUIRE(c.src_h >= 1 && c.src_w >= 1 && c.src_h <= VGHV_MAX_SIDE && c.src_w <= VGHV_MAX_SIDE, "warp_crops: crop %d: source %d x %d outside 1 .. %d", i, c.src_h,
+                   c.src_w, VGHV_MAX_SIDE);
+        CH_REQUIRE(c.src_pitch_bytes >= (int64_t)c.src_w * 3, "warp_crops: crop %d: src_pitch_bytes %lld < src_w * 3 = %lld", i, (long long)c.src_pitch_bytes,
+                   (long long)c.src_w * 3);
+        CH_REQUIRE(c.crop_w >= 0 && c.crop_h >= 0 && c.crop_w <= 65535 * TILE_W && c.crop_h <= 65535 * TILE_H, "warp_crops: crop %d: bad size %d x %d", i, c.crop_w, c.crop_h);
         if (c.crop_w == 0 || c.crop_h == 0) continue;
         const int64_t need_tab = 2 * (int64_t)c.crop_w + 2 * (int64_t)c.crop_h, need_dst = (int64_t)c.crop_w * c.crop_h * 3;
-        VGHV_REQUIRE(c.table_offset >= 0 && c.table_offset <= n_tables - need_tab, "warp_crops: crop %d: tables [%lld, +%lld) outside the %lld supplied", i,
-                     (long long)c.table_offset, (long long)need_tab, (long long)n_tables);
-        VGHV_REQUIRE(dst_dev && c.dst_offset >= 0 && c.dst_offset <= dst_bytes - need_dst, "warp_crops: crop %d: result [%lld, +%lld) outside the %lld destination bytes", i,
-                     (long long)c.dst_offset, (long long)need_dst, (long long)dst_bytes);
+        CH_REQUIRE(c.table_offset >= 0 && c.table_offset <= n_tables - need_tab, "warp_crops: crop %d: tables [%lld, +%lld) outside the %lld supplied", i,
+                   (long long)c.table_offset, (long long)need_tab, (long long)n_tables);
+        CH_REQUIRE(dst_dev && c.dst_offset >= 0 && c.dst_offset <= dst_bytes - need_dst, "warp_crops: crop %d: result [%lld, +%lld) outside the %lld destination bytes", i,
+                   (long long)c.dst_offset, (long long)need_dst, (long long)dst_bytes);
         n_tiles += (int64_t)((c.crop_w + TILE_W - 1) / TILE_W) * ((c.crop_h + TILE_H - 1) / TILE_H);
     }
-    if (n_tiles == 0) return VGHV_OK;
-    VGHV_REQUIRE(n_tiles <= INT32_MAX, "warp_crops: %lld tiles exceed one launch", (long long)n_tiles);
+    if (n_tiles == 0) return OK;
+    CH_REQUIRE(n_tiles <= INT32_MAX, "warp_crops: %lld tiles exceed one launch", (long long)n_tiles);
 
     int device = 0;
-    VGHV_HIP(hipGetDevice(&device));
+    CH_HIP(hipGetDevice(&device));
     std::lock_guard<std::mutex> lock(g_mutex);
     Staging& s = g_staging[device];
     const size_t at_tiles = align16((size_t)n * sizeof(Crop)), at_tab = align16(at_tiles + (size_t)n_tiles * sizeof(Tile));
     const size_t total = at_tab + (size_t)n_tables * sizeof(int32_t);
-    if (int rc = staging_reserve(s, total, "warp_crops")) return rc;
+    if (int rc = reserve(s, total, "warp_crops")) return rc;
     Crop* hc = (Crop*)s.host;
     Tile* ht = (Tile*)(s.host + at_tiles);
     for (int i = 0; i < n; ++i) {
@@ -173,10 +138,9 @@ extern "C" VGHV_API int vghv_warp_crops(const vghv_crop* crops, int n, const int
     }
     memcpy(s.host + at_tab, tables, (size_t)n_tables * sizeof(int32_t));
     hipStream_t st = (hipStream_t)stream;
-    VGHV_HIP(hipMemcpyAsync(s.dev, s.host, total, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(warp_crops_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, (const Crop*)s.dev, (const Tile*)(s.dev + at_tiles), (const int32_t*)(s.dev + at_tab), dst_dev);
-    VGHV_HIP(hipGetLastError());
-    VGHV_HIP(hipEventRecord(s.ev, st));
-    s.recorded = true;
-    return VGHV_OK;
+    Queue q;  // from here on work is queued (companion_host.h, queue-then-record)
+    CH_QUEUE(q, hipMemcpyAsync(s.dev, s.host, total, hipMemcpyHostToDevice, st));
+    if (q.ok())
+        hipLaunchKernelGGL(warp_crops_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, (const Crop*)s.dev, (const Tile*)(s.dev + at_tiles), (const int32_t*)(s.dev + at_tab), dst_dev);
+    return finish(q, s, true, st, "warp_crops");
 }

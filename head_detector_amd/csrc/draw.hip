@@ -15,11 +15,13 @@
 #include <map>
 #include <mutex>
 
-#include "vghv_internal.h"
+#include "../../include/vgh_view.h"
+#include "companion_host.h"
 
 namespace {
 
-using namespace vghv;
+using namespace companion;
+static_assert(VGHV_OK == OK && VGHV_ERR_INVALID == ERR_INVALID && VGHV_ERR_HIP == ERR_HIP && VGHV_ERR_NOMEM == ERR_NOMEM, "companion_host.h returns these codes");
 
 enum DrawClass : uint32_t { CLASS_BOX = 0, CLASS_WIRE = 1, CLASS_DOTS = 2, NUM_CLASSES = 3 };  // in the order one head's classes are painted
 
@@ -224,11 +226,10 @@ __global__ __launch_bounds__(256) void resolve_kernel(const uint32_t* __restrict
     }
 }
 
-// ---- per-device state: the staging block of the uploads and the key plane (library scratch, grown on demand, cleared by every call) ----------
+// ---- per-device state: the staging block of the uploads and the key plane, cleared by every call and guarded by the block's event (companion_host.h) ----
 struct DrawState {
     Staging staging;
-    uint32_t* keys = nullptr;
-    size_t key_bytes = 0;
+    Scratch<uint32_t> keys;
 };
 
 std::mutex g_mutex;
@@ -239,64 +240,57 @@ bool coord_ok(int32_t v) { return v > -VGHV_MAX_COORD && v < VGHV_MAX_COORD; }
 }  // namespace
 
 extern "C" VGHV_API int vghv_draw_heads(const vghv_draw_job* job, void* stream) {
-    VGHV_REQUIRE(job, "draw_heads: null job");
+    CH_REQUIRE(job, "draw_heads: null job");
     const vghv_draw_job& j = *job;
     // everything is checked before anything is allocated, written or queued
-    VGHV_REQUIRE(j.src_dev && j.dst_dev, "draw_heads: null image (src_dev %p, dst_dev %p)", (const void*)j.src_dev, (void*)j.dst_dev);
-    VGHV_REQUIRE(j.channels == 3, "draw_heads: %d channels (needs 3: u8 RGB)", j.channels);
-    VGHV_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHV_MAX_SIDE && j.width <= VGHV_MAX_SIDE, "draw_heads: image %d x %d outside 1 .. %d", j.height, j.width,
-                 VGHV_MAX_SIDE);
-    VGHV_REQUIRE(j.src_pitch_bytes >= (int64_t)j.width * 3, "draw_heads: src_pitch_bytes %lld < width * 3 = %lld", (long long)j.src_pitch_bytes, (long long)j.width * 3);
-    VGHV_REQUIRE(((uintptr_t)j.dst_dev & 3) == 0, "draw_heads: dst_dev %p is not 4-byte aligned", (void*)j.dst_dev);
-    VGHV_REQUIRE(j.n_heads >= 0 && j.n_heads <= VGHV_MAX_DRAW_HEADS, "draw_heads: %d heads outside 0 .. %d", j.n_heads, VGHV_MAX_DRAW_HEADS);
-    VGHV_REQUIRE(j.n_triangles >= 0 && j.n_indices >= 0 && j.n_vertices >= 0, "draw_heads: negative count");
+    CH_REQUIRE(j.src_dev && j.dst_dev, "draw_heads: null image (src_dev %p, dst_dev %p)", (const void*)j.src_dev, (void*)j.dst_dev);
+    CH_REQUIRE(j.channels == 3, "draw_heads: %d channels (needs 3: u8 RGB)", j.channels);
+    CH_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHV_MAX_SIDE && j.width <= VGHV_MAX_SIDE, "draw_heads: image %d x %d outside 1 .. %d", j.height, j.width,
+               VGHV_MAX_SIDE);
+    CH_REQUIRE(j.src_pitch_bytes >= (int64_t)j.width * 3, "draw_heads: src_pitch_bytes %lld < width * 3 = %lld", (long long)j.src_pitch_bytes, (long long)j.width * 3);
+    CH_REQUIRE(((uintptr_t)j.dst_dev & 3) == 0, "draw_heads: dst_dev %p is not 4-byte aligned", (void*)j.dst_dev);
+    CH_REQUIRE(j.n_heads >= 0 && j.n_heads <= VGHV_MAX_DRAW_HEADS, "draw_heads: %d heads outside 0 .. %d", j.n_heads, VGHV_MAX_DRAW_HEADS);
+    CH_REQUIRE(j.n_triangles >= 0 && j.n_indices >= 0 && j.n_vertices >= 0, "draw_heads: negative count");
     const int n = j.n_heads, V = j.n_vertices, T = j.n_triangles, K = j.n_indices, R = j.radius;
     const bool boxes = n && j.boxes, wire = n && T, dots = n && K;
-    if (wire || dots) VGHV_REQUIRE(j.points && V >= 1, "draw_heads: wire and dots need points (points %p, n_vertices %d)", (const void*)j.points, V);
+    if (wire || dots) CH_REQUIRE(j.points && V >= 1, "draw_heads: wire and dots need points (points %p, n_vertices %d)", (const void*)j.points, V);
     if (wire) {
-        VGHV_REQUIRE(j.triangles, "draw_heads: null triangles");
-        VGHV_REQUIRE((int64_t)n * T * 3 <= INT32_MAX, "draw_heads: %lld segments exceed one launch", (long long)n * T * 3);
+        CH_REQUIRE(j.triangles, "draw_heads: null triangles");
+        CH_REQUIRE((int64_t)n * T * 3 <= INT32_MAX, "draw_heads: %lld segments exceed one launch", (long long)n * T * 3);
         for (int64_t i = 0; i < (int64_t)T * 3; ++i)
-            VGHV_REQUIRE(j.triangles[i] >= 0 && j.triangles[i] < V, "draw_heads: triangle %lld: index %d outside the %d vertices", (long long)(i / 3), j.triangles[i], V);
+            CH_REQUIRE(j.triangles[i] >= 0 && j.triangles[i] < V, "draw_heads: triangle %lld: index %d outside the %d vertices", (long long)(i / 3), j.triangles[i], V);
     }
     if (dots) {
-        VGHV_REQUIRE(j.indices && j.half_widths, "draw_heads: null indices or half_widths");
-        VGHV_REQUIRE(R >= 1 && R <= VGHV_MAX_RADIUS, "draw_heads: radius %d outside 1 .. %d", R, VGHV_MAX_RADIUS);
-        VGHV_REQUIRE((int64_t)n * K * (2 * R + 1) <= INT32_MAX, "draw_heads: %lld circle rows exceed one launch", (long long)n * K * (2 * R + 1));
-        for (int i = 0; i < K; ++i) VGHV_REQUIRE(j.indices[i] >= 0 && j.indices[i] < V, "draw_heads: indices[%d] = %d outside the %d vertices", i, j.indices[i], V);
-        for (int i = 0; i <= R; ++i) VGHV_REQUIRE(j.half_widths[i] >= 0 && j.half_widths[i] <= R, "draw_heads: half_widths[%d] = %d outside 0 .. radius", i, j.half_widths[i]);
+        CH_REQUIRE(j.indices && j.half_widths, "draw_heads: null indices or half_widths");
+        CH_REQUIRE(R >= 1 && R <= VGHV_MAX_RADIUS, "draw_heads: radius %d outside 1 .. %d", R, VGHV_MAX_RADIUS);
+        CH_REQUIRE((int64_t)n * K * (2 * R + 1) <= INT32_MAX, "draw_heads: %lld circle rows exceed one launch", (long long)n * K * (2 * R + 1));
+        for (int i = 0; i < K; ++i) CH_REQUIRE(j.indices[i] >= 0 && j.indices[i] < V, "draw_heads: indices[%d] = %d outside the %d vertices", i, j.indices[i], V);
+        for (int i = 0; i <= R; ++i) CH_REQUIRE(j.half_widths[i] >= 0 && j.half_widths[i] <= R, "draw_heads: half_widths[%d] = %d outside 0 .. radius", i, j.half_widths[i]);
     }
     const size_t n_points = (wire || dots) ? (size_t)n * V * 2 : 0;
     for (size_t i = 0; i < n_points; ++i)
-        VGHV_REQUIRE(coord_ok(j.points[i]), "draw_heads: head %zu: coordinate %d outside +-2^24", i / ((size_t)V * 2), j.points[i]);
+        CH_REQUIRE(coord_ok(j.points[i]), "draw_heads: head %zu: coordinate %d outside +-2^24", i / ((size_t)V * 2), j.points[i]);
     if (boxes)
         for (int i = 0; i < n; ++i) {
             const int32_t* b = j.boxes + 4 * i;
-            VGHV_REQUIRE(coord_ok(b[0]) && coord_ok(b[1]) && b[2] >= 0 && b[3] >= 0 && b[2] < VGHV_MAX_COORD && b[3] < VGHV_MAX_COORD, "draw_heads: head %d: bad box (%d, %d, %d, %d)", i,
-                         b[0], b[1], b[2], b[3]);
+            CH_REQUIRE(coord_ok(b[0]) && coord_ok(b[1]) && b[2] >= 0 && b[3] >= 0 && b[2] < VGHV_MAX_COORD && b[3] < VGHV_MAX_COORD, "draw_heads: head %d: bad box (%d, %d, %d, %d)", i,
+                       b[0], b[1], b[2], b[3]);
         }
 
     const int W = j.width, H = j.height;
     const uint32_t n_pixels = (uint32_t)W * (uint32_t)H;  // < 2^30
     hipStream_t st = (hipStream_t)stream;
     int device = 0;
-    VGHV_HIP(hipGetDevice(&device));
+    CH_HIP(hipGetDevice(&device));
     std::lock_guard<std::mutex> lock(g_mutex);
     DrawState& s = g_state[device];
     // one upload: [points | boxes | triangles | indices | half_widths], each from a 16-byte boundary
     const size_t at_boxes = align16(n_points * 4), at_tri = align16(at_boxes + (boxes ? (size_t)n * 16 : 0)), at_idx = align16(at_tri + (wire ? (size_t)T * 12 : 0));
     const size_t at_hw = align16(at_idx + (dots ? (size_t)K * 4 : 0)), total = align16(at_hw + (dots ? (size_t)(R + 1) * 4 : 0));
-    if (int rc = staging_reserve(s.staging, total ? total : 16, "draw_heads")) return rc;  // also waits for this device's previous draw
-    if ((size_t)n_pixels * 4 > s.key_bytes) {  // nothing is using the old plane: the wait above covered the previous call's kernels
-        hipFree(s.keys);
-        s.keys = nullptr;
-        s.key_bytes = 0;
-        const size_t cap = (size_t)n_pixels * 4;
-        if (hipMalloc((void**)&s.keys, cap) != hipSuccess) {
-            set_error("draw_heads: allocating the %zu-byte key plane failed", cap);
-            return VGHV_ERR_NOMEM;
-        }
-        s.key_bytes = cap;
+    if (int rc = reserve(s.staging, total ? total : 16, "draw_heads")) return rc;  // also waits for this device's previous draw
+    if (!grow(s.keys, (size_t)n_pixels * 4)) {
+        set_error("draw_heads: allocating the %zu-byte key plane failed", (size_t)n_pixels * 4);
+        return ERR_NOMEM;
     }
     uint8_t* h = s.staging.host;
     if (n_points) memcpy(h, j.points, n_points * 4);
@@ -306,26 +300,26 @@ extern "C" VGHV_API int vghv_draw_heads(const vghv_draw_job* job, void* stream) 
         memcpy(h + at_idx, j.indices, (size_t)K * 4);
         memcpy(h + at_hw, j.half_widths, (size_t)(R + 1) * 4);
     }
+    // from here on work is queued (companion_host.h, queue-then-record); the event also guards the key plane, so it is recorded by every call that gets here
     const uint8_t* d = s.staging.dev;
-    if (total) VGHV_HIP(hipMemcpyAsync(s.staging.dev, h, total, hipMemcpyHostToDevice, st));
-    VGHV_HIP(hipMemsetAsync(s.keys, 0, (size_t)n_pixels * 4, st));  // every call clears what it resolves: no stale keys from another image size
+    uint32_t* keys = s.keys.ptr;
+    Queue q;
+    if (total) CH_QUEUE(q, hipMemcpyAsync(s.staging.dev, h, total, hipMemcpyHostToDevice, st));
+    CH_QUEUE(q, hipMemsetAsync(keys, 0, (size_t)n_pixels * 4, st));  // every call clears what it resolves: no stale keys from another image size
     const int32_t* d_points = (const int32_t*)d;
-    if (boxes) {
+    if (boxes && q.ok()) {
         const int longest = W > H ? W : H;
-        hipLaunchKernelGGL(stamp_boxes_kernel, dim3((unsigned)n * 4, (unsigned)(longest + 255) / 256), dim3(256), 0, st, (const int32_t*)(d + at_boxes), s.keys, W, H);
+        hipLaunchKernelGGL(stamp_boxes_kernel, dim3((unsigned)n * 4, (unsigned)(longest + 255) / 256), dim3(256), 0, st, (const int32_t*)(d + at_boxes), keys, W, H);
     }
-    if (wire) {
+    if (wire && q.ok()) {
         const int n_segments = n * T * 3;
-        hipLaunchKernelGGL(stamp_wire_kernel, dim3((unsigned)(n_segments + 255) / 256), dim3(256), 0, st, d_points, (const int32_t*)(d + at_tri), s.keys, n_segments, V, T, W, H);
+        hipLaunchKernelGGL(stamp_wire_kernel, dim3((unsigned)(n_segments + 255) / 256), dim3(256), 0, st, d_points, (const int32_t*)(d + at_tri), keys, n_segments, V, T, W, H);
     }
-    if (dots) {
+    if (dots && q.ok()) {
         const int n_rows = n * K * (2 * R + 1);
-        hipLaunchKernelGGL(stamp_dots_kernel, dim3((unsigned)(n_rows + 255) / 256), dim3(256), 0, st, d_points, (const int32_t*)(d + at_idx), (const int32_t*)(d + at_hw), s.keys,
-                           n_rows, V, K, R, W, H);
+        hipLaunchKernelGGL(stamp_dots_kernel, dim3((unsigned)(n_rows + 255) / 256), dim3(256), 0, st, d_points, (const int32_t*)(d + at_idx), (const int32_t*)(d + at_hw), keys, n_rows,
+                           V, K, R, W, H);
     }
-    hipLaunchKernelGGL(resolve_kernel, dim3((n_pixels / 4 + 256) / 256), dim3(256), 0, st, (const uint32_t*)s.keys, j.src_dev, j.src_pitch_bytes, j.dst_dev, W, n_pixels);
-    VGHV_HIP(hipGetLastError());
-    VGHV_HIP(hipEventRecord(s.staging.ev, st));
-    s.staging.recorded = true;
-    return VGHV_OK;
+    if (q.ok()) hipLaunchKernelGGL(resolve_kernel, dim3((n_pixels / 4 + 256) / 256), dim3(256), 0, st, (const uint32_t*)keys, j.src_dev, j.src_pitch_bytes, j.dst_dev, W, n_pixels);
+    return finish(q, s.staging, true, st, "draw_heads");
 }

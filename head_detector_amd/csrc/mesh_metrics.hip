@@ -13,46 +13,17 @@
 // Agreement counts are integers: a workgroup adds its lanes' counts in LDS and issues one integer atomic per workgroup.  There is no float atomic; every
 // distance is float64 in the stated operation order with contraction off, so every output is bitwise reproducible and equal to a float64 restatement on
 // the host (tests/mesh_metrics_ref.py).
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stddef.h>
-#include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/vgh_eval.h"
+#include "companion_host.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-// ---- error plumbing: never throw across the C ABI ---------------------------------------------------------------------------------------------
-thread_local char g_error[512] = "";
-
-void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-}
-
-#define EV_HIP(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) {                                                             \
-            set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-            return VGHEV_ERR_HIP;                                                           \
-        }                                                                                   \
-    } while (0)
-
-#define EV_REQUIRE(cond, ...)         \
-    do {                              \
-        if (!(cond)) {                \
-            set_error(__VA_ARGS__);   \
-            return VGHEV_ERR_INVALID; \
-        }                             \
-    } while (0)
+using namespace companion;
+static_assert(VGHEV_OK == OK && VGHEV_ERR_INVALID == ERR_INVALID && VGHEV_ERR_HIP == ERR_HIP, "companion_host.h returns these codes");  // this library allocates nothing: its header has no NOMEM
 
 constexpr int RANK_LANES = 256;   // points of one workgroup of rank_kernel
 constexpr int RANK_TILE = 1024;   // column distances held in LDS at a time: 8 KB
@@ -248,25 +219,25 @@ void launch_z_nearest(unsigned grid, hipStream_t st, const vghev_z_order_job& j,
 
 extern "C" VGHEV_API const char* vghev_version(void) { return "vgheval 1 (gfx950)"; }
 
-extern "C" VGHEV_API const char* vghev_last_error(void) { return g_error; }
+extern "C" VGHEV_API const char* vghev_last_error(void) { return last_error(); }
 
 extern "C" VGHEV_API int vghev_z_order(const vghev_z_order_job* job, void* stream) {
-    EV_REQUIRE(job != nullptr, "z_order: job is NULL");
+    CH_REQUIRE(job != nullptr, "z_order: job is NULL");
     const vghev_z_order_job& j = *job;
-    EV_REQUIRE(j.n_heads >= 0 && j.n_heads <= VGHEV_MAX_HEADS, "z_order: n_heads = %d outside 0 .. %d", j.n_heads, VGHEV_MAX_HEADS);
-    EV_REQUIRE(j.top_k >= 1 && j.top_k <= VGHEV_MAX_TOP_K, "z_order: top_k = %d outside 1 .. %d", j.top_k, VGHEV_MAX_TOP_K);
-    EV_REQUIRE(j.n_points >= j.top_k + 1 && j.n_points <= VGHEV_MAX_POINTS, "z_order: n_points = %d outside top_k + 1 = %d .. %d", j.n_points, j.top_k + 1,
+    CH_REQUIRE(j.n_heads >= 0 && j.n_heads <= VGHEV_MAX_HEADS, "z_order: n_heads = %d outside 0 .. %d", j.n_heads, VGHEV_MAX_HEADS);
+    CH_REQUIRE(j.top_k >= 1 && j.top_k <= VGHEV_MAX_TOP_K, "z_order: top_k = %d outside 1 .. %d", j.top_k, VGHEV_MAX_TOP_K);
+    CH_REQUIRE(j.n_points >= j.top_k + 1 && j.n_points <= VGHEV_MAX_POINTS, "z_order: n_points = %d outside top_k + 1 = %d .. %d", j.n_points, j.top_k + 1,
                VGHEV_MAX_POINTS);
-    EV_REQUIRE(j.mode == VGHEV_NEIGHBOURS_REFERENCE || j.mode == VGHEV_NEIGHBOURS_NEAREST, "z_order: unknown mode %d", j.mode);
-    if (j.n_heads == 0) return VGHEV_OK;
-    EV_REQUIRE(j.pred_dev && j.gt_dev && j.agree_dev, "z_order: pred_dev, gt_dev and agree_dev must not be NULL");
+    CH_REQUIRE(j.mode == VGHEV_NEIGHBOURS_REFERENCE || j.mode == VGHEV_NEIGHBOURS_NEAREST, "z_order: unknown mode %d", j.mode);
+    if (j.n_heads == 0) return OK;
+    CH_REQUIRE(j.pred_dev && j.gt_dev && j.agree_dev, "z_order: pred_dev, gt_dev and agree_dev must not be NULL");
     const bool reference = j.mode == VGHEV_NEIGHBOURS_REFERENCE;
     const int tiles = (j.n_points + (reference ? RANK_LANES : NEAR_LANES) - 1) / (reference ? RANK_LANES : NEAR_LANES);
     const uint64_t groups = (uint64_t)j.n_heads * (uint64_t)tiles * (uint64_t)(reference ? j.top_k : 1);
-    EV_REQUIRE(groups <= 0x7fffffffull, "z_order: %d heads of %d points need %llu workgroups, more than one launch holds", j.n_heads, j.n_points,
+    CH_REQUIRE(groups <= 0x7fffffffull, "z_order: %d heads of %d points need %llu workgroups, more than one launch holds", j.n_heads, j.n_points,
                (unsigned long long)groups);
     hipStream_t st = (hipStream_t)stream;
-    EV_HIP(hipMemsetAsync(j.agree_dev, 0, (size_t)j.n_heads * sizeof(int32_t), st));
+    CH_HIP(hipMemsetAsync(j.agree_dev, 0, (size_t)j.n_heads * sizeof(int32_t), st));
     if (reference) {
         hipLaunchKernelGGL(rank_kernel, dim3((unsigned)groups), dim3(RANK_LANES), 0, st, j.pred_dev, j.gt_dev, j.n_points, j.top_k, tiles, j.agree_dev);
     } else {
@@ -280,28 +251,28 @@ extern "C" VGHEV_API int vghev_z_order(const vghev_z_order_job* job, void* strea
 #undef EV_CASE
         }
     }
-    EV_HIP(hipGetLastError());
-    return VGHEV_OK;
+    CH_HIP(hipGetLastError());
+    return OK;
 }
 
 extern "C" VGHEV_API int vghev_nearest(const vghev_nearest_job* job, void* stream) {
-    EV_REQUIRE(job != nullptr, "nearest: job is NULL");
+    CH_REQUIRE(job != nullptr, "nearest: job is NULL");
     const vghev_nearest_job& j = *job;
-    EV_REQUIRE(j.n_heads >= 0 && j.n_heads <= VGHEV_MAX_HEADS, "nearest: n_heads = %d outside 0 .. %d", j.n_heads, VGHEV_MAX_HEADS);
-    EV_REQUIRE(j.n_queries >= 1 && j.n_queries <= VGHEV_MAX_POINTS, "nearest: n_queries = %d outside 1 .. %d", j.n_queries, VGHEV_MAX_POINTS);
-    EV_REQUIRE(j.n_points >= 1 && j.n_points <= VGHEV_MAX_POINTS, "nearest: n_points = %d outside 1 .. %d", j.n_points, VGHEV_MAX_POINTS);
-    EV_REQUIRE(j.reserved == 0, "nearest: reserved must be 0");
-    EV_REQUIRE(j.transform_dev || !j.point_scale_dev, "nearest: point_scale_dev needs transform_dev");
-    if (j.n_heads == 0) return VGHEV_OK;
-    EV_REQUIRE(j.query_dev && j.points_dev && j.sqdist_dev && j.index_dev, "nearest: query_dev, points_dev, sqdist_dev and index_dev must not be NULL");
+    CH_REQUIRE(j.n_heads >= 0 && j.n_heads <= VGHEV_MAX_HEADS, "nearest: n_heads = %d outside 0 .. %d", j.n_heads, VGHEV_MAX_HEADS);
+    CH_REQUIRE(j.n_queries >= 1 && j.n_queries <= VGHEV_MAX_POINTS, "nearest: n_queries = %d outside 1 .. %d", j.n_queries, VGHEV_MAX_POINTS);
+    CH_REQUIRE(j.n_points >= 1 && j.n_points <= VGHEV_MAX_POINTS, "nearest: n_points = %d outside 1 .. %d", j.n_points, VGHEV_MAX_POINTS);
+    CH_REQUIRE(j.reserved == 0, "nearest: reserved must be 0");
+    CH_REQUIRE(j.transform_dev || !j.point_scale_dev, "nearest: point_scale_dev needs transform_dev");
+    if (j.n_heads == 0) return OK;
+    CH_REQUIRE(j.query_dev && j.points_dev && j.sqdist_dev && j.index_dev, "nearest: query_dev, points_dev, sqdist_dev and index_dev must not be NULL");
     const int tiles = (j.n_queries + NEAR_LANES - 1) / NEAR_LANES;
     const uint64_t groups = (uint64_t)j.n_heads * (uint64_t)tiles;
-    EV_REQUIRE(groups <= 0x7fffffffull, "nearest: %d heads of %d queries need %llu workgroups, more than one launch holds", j.n_heads, j.n_queries,
+    CH_REQUIRE(groups <= 0x7fffffffull, "nearest: %d heads of %d queries need %llu workgroups, more than one launch holds", j.n_heads, j.n_queries,
                (unsigned long long)groups);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(nearest_kernel, dim3((unsigned)groups), dim3(NEAR_LANES), 0, st, j.query_dev, j.query_scale_dev, j.points_dev, j.transform_dev,
                        j.point_scale_dev, j.n_queries, j.n_points, tiles, j.sqdist_dev, j.index_dev);
     if (j.mean_dev) hipLaunchKernelGGL(mean_kernel, dim3((unsigned)j.n_heads), dim3(MEAN_LANES), 0, st, (const double*)j.sqdist_dev, j.n_queries, j.mean_dev);
-    EV_HIP(hipGetLastError());
-    return VGHEV_OK;
+    CH_HIP(hipGetLastError());
+    return OK;
 }

@@ -19,8 +19,7 @@
 #include <mutex>
 #include <vector>
 
-#include "vghv_internal.h"
-#define TILE_FOLD_SET_ERROR vghv::set_error  // one message for all of libvghview.so (csrc/aligned.hip)
+#include "../../include/vgh_view.h"
 #include "tile_fold.h"
 
 #pragma clang fp contract(off)
@@ -28,7 +27,7 @@
 namespace {
 
 using namespace tile_fold;
-static_assert(VGHV_OK == OK && VGHV_ERR_INVALID == ERR_INVALID && VGHV_ERR_HIP == ERR_HIP && VGHV_ERR_NOMEM == ERR_NOMEM, "tile_fold.h returns these codes");
+static_assert(VGHV_OK == OK && VGHV_ERR_INVALID == ERR_INVALID && VGHV_ERR_HIP == ERR_HIP && VGHV_ERR_NOMEM == ERR_NOMEM, "companion_host.h returns these codes");
 
 // ---- normals, and the colours of the shaded mesh ----------------------------------------------------------------------------------------
 struct Shade {
@@ -177,7 +176,7 @@ std::map<int, State> g_state;
 // every triangle index against V
 int check_triangles(const char* who, const int32_t* triangles, int T, int V) {
     const int64_t bad = first_bad_index(triangles, (int64_t)T * 3, V);
-    TF_REQUIRE(bad < 0, "%s: triangle %lld: index %d outside the %d vertices", who, (long long)(bad / 3), triangles[bad], V);
+    CH_REQUIRE(bad < 0, "%s: triangle %lld: index %d outside the %d vertices", who, (long long)(bad / 3), triangles[bad], V);
     return OK;
 }
 
@@ -201,16 +200,16 @@ void launch_normals(const float* verts, const uint8_t* d_tri, const uint8_t* d_i
 }  // namespace
 
 extern "C" VGHV_API int vghv_vertex_normals(const float* verts_dev, int n, int V, const int32_t* triangles, int T, float* normals_dev, void* stream) {
-    TF_REQUIRE(n >= 0 && V >= 1 && T >= 0, "vertex_normals: bad sizes (n %d, V %d, T %d)", n, V, T);
-    TF_REQUIRE((int64_t)n * V <= INT32_MAX / 4 && T <= INT32_MAX / 4, "vertex_normals: %lld vertices or %d triangles exceed one launch", (long long)n * V, T);
+    CH_REQUIRE(n >= 0 && V >= 1 && T >= 0, "vertex_normals: bad sizes (n %d, V %d, T %d)", n, V, T);
+    CH_REQUIRE((int64_t)n * V <= INT32_MAX / 4 && T <= INT32_MAX / 4, "vertex_normals: %lld vertices or %d triangles exceed one launch", (long long)n * V, T);
     if (n == 0) return OK;
-    TF_REQUIRE(verts_dev && normals_dev, "vertex_normals: null vertices or normals (verts_dev %p, normals_dev %p)", (const void*)verts_dev, (void*)normals_dev);
-    TF_REQUIRE(triangles || T == 0, "vertex_normals: null triangles");
-    TF_REQUIRE(verts_dev != normals_dev, "vertex_normals: normals_dev overlaps verts_dev");
+    CH_REQUIRE(verts_dev && normals_dev, "vertex_normals: null vertices or normals (verts_dev %p, normals_dev %p)", (const void*)verts_dev, (void*)normals_dev);
+    CH_REQUIRE(triangles || T == 0, "vertex_normals: null triangles");
+    CH_REQUIRE(verts_dev != normals_dev, "vertex_normals: normals_dev overlaps verts_dev");
     if (int rc = check_triangles("vertex_normals", triangles, T, V)) return rc;
     hipStream_t st = (hipStream_t)stream;
     int device = 0;
-    TF_HIP(hipGetDevice(&device));
+    CH_HIP(hipGetDevice(&device));
     std::lock_guard<std::mutex> lock(g_mutex);
     State& s = g_state[device];
     const size_t at_inc = align16((size_t)T * 12), total = at_inc + incidence_bytes(T, V);
@@ -218,59 +217,59 @@ extern "C" VGHV_API int vghv_vertex_normals(const float* verts_dev, int n, int V
     uint8_t* h = s.host;
     if (T) memcpy(h, triangles, (size_t)T * 12);
     build_incidence(triangles, T, V, (int32_t*)(h + at_inc), (int32_t*)(h + at_inc + align16(((size_t)V + 1) * 4)));
-    Queue q;  // from here on work is queued (tile_fold.h, queue-then-record)
-    TF_QUEUE(q, hipMemcpyAsync(s.dev, h, total, hipMemcpyHostToDevice, st));
+    Queue q;  // from here on work is queued (companion_host.h, queue-then-record)
+    CH_QUEUE(q, hipMemcpyAsync(s.dev, h, total, hipMemcpyHostToDevice, st));
     if (q.ok()) launch_normals(verts_dev, s.dev, s.dev + at_inc, n, V, 1.0f, 0, Shade{}, normals_dev, st);
     return finish(q, s, true, st, "vertex_normals");
 }
 
 extern "C" VGHV_API int vghv_render_meshes(const vghv_mesh_job* job, void* stream) {
-    TF_REQUIRE(job, "render_meshes: null job");
+    CH_REQUIRE(job, "render_meshes: null job");
     const vghv_mesh_job& j = *job;
     // everything is checked before anything is allocated, written or queued
-    TF_REQUIRE(j.src_dev && j.dst_dev, "render_meshes: null image (src_dev %p, dst_dev %p)", (const void*)j.src_dev, (void*)j.dst_dev);
-    TF_REQUIRE(j.channels == 3, "render_meshes: %d channels (needs 3: u8 RGB)", j.channels);
-    TF_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHV_MAX_SIDE && j.width <= VGHV_MAX_SIDE, "render_meshes: image %d x %d outside 1 .. %d", j.height, j.width,
+    CH_REQUIRE(j.src_dev && j.dst_dev, "render_meshes: null image (src_dev %p, dst_dev %p)", (const void*)j.src_dev, (void*)j.dst_dev);
+    CH_REQUIRE(j.channels == 3, "render_meshes: %d channels (needs 3: u8 RGB)", j.channels);
+    CH_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHV_MAX_SIDE && j.width <= VGHV_MAX_SIDE, "render_meshes: image %d x %d outside 1 .. %d", j.height, j.width,
                VGHV_MAX_SIDE);
-    TF_REQUIRE(j.src_pitch_bytes >= (int64_t)j.width * 3, "render_meshes: src_pitch_bytes %lld < width * 3 = %lld", (long long)j.src_pitch_bytes, (long long)j.width * 3);
+    CH_REQUIRE(j.src_pitch_bytes >= (int64_t)j.width * 3, "render_meshes: src_pitch_bytes %lld < width * 3 = %lld", (long long)j.src_pitch_bytes, (long long)j.width * 3);
     const int W = j.width, H = j.height, n = j.n_heads, V = j.n_vertices, T = j.n_triangles;
     {
         const uintptr_t s0 = (uintptr_t)j.src_dev, s1 = s0 + (size_t)(H - 1) * (size_t)j.src_pitch_bytes + (size_t)W * 3, d0 = (uintptr_t)j.dst_dev, d1 = d0 + (size_t)H * W * 3;
-        TF_REQUIRE(s1 <= d0 || d1 <= s0, "render_meshes: dst_dev overlaps src_dev");
+        CH_REQUIRE(s1 <= d0 || d1 <= s0, "render_meshes: dst_dev overlaps src_dev");
     }
-    TF_REQUIRE(n >= 0 && n <= VGHV_MAX_DRAW_HEADS, "render_meshes: %d heads outside 0 .. %d", n, VGHV_MAX_DRAW_HEADS);
-    TF_REQUIRE(V >= 0 && T >= 0, "render_meshes: negative count");
-    TF_REQUIRE(j.alpha >= 0.0f && j.alpha <= 1.0f, "render_meshes: alpha %g outside 0 .. 1", (double)j.alpha);
-    TF_REQUIRE(j.z_sign == 1.0f || j.z_sign == -1.0f, "render_meshes: z_sign %g is neither +1 nor -1", (double)j.z_sign);
-    TF_REQUIRE(j.shade == 0 || j.shade == 1, "render_meshes: shade %d is neither 0 nor 1", j.shade);
-    TF_REQUIRE(j.colors_per_head == 0 || j.colors_per_head == 1, "render_meshes: colors_per_head %d is neither 0 nor 1", j.colors_per_head);
+    CH_REQUIRE(n >= 0 && n <= VGHV_MAX_DRAW_HEADS, "render_meshes: %d heads outside 0 .. %d", n, VGHV_MAX_DRAW_HEADS);
+    CH_REQUIRE(V >= 0 && T >= 0, "render_meshes: negative count");
+    CH_REQUIRE(j.alpha >= 0.0f && j.alpha <= 1.0f, "render_meshes: alpha %g outside 0 .. 1", (double)j.alpha);
+    CH_REQUIRE(j.z_sign == 1.0f || j.z_sign == -1.0f, "render_meshes: z_sign %g is neither +1 nor -1", (double)j.z_sign);
+    CH_REQUIRE(j.shade == 0 || j.shade == 1, "render_meshes: shade %d is neither 0 nor 1", j.shade);
+    CH_REQUIRE(j.colors_per_head == 0 || j.colors_per_head == 1, "render_meshes: colors_per_head %d is neither 0 nor 1", j.colors_per_head);
     const bool paint = n > 0 && T > 0;
     if (paint) {
-        TF_REQUIRE(V >= 1 && j.verts_dev && j.triangles && j.bounds && j.colors_dev, "render_meshes: null vertices, triangles, bounds or colours (n_vertices %d)", V);
-        TF_REQUIRE((int64_t)n * T <= INT32_MAX / 4 && (int64_t)n * V <= INT32_MAX / 4, "render_meshes: %lld triangles or %lld vertices exceed one launch", (long long)n * T,
+        CH_REQUIRE(V >= 1 && j.verts_dev && j.triangles && j.bounds && j.colors_dev, "render_meshes: null vertices, triangles, bounds or colours (n_vertices %d)", V);
+        CH_REQUIRE((int64_t)n * T <= INT32_MAX / 4 && (int64_t)n * V <= INT32_MAX / 4, "render_meshes: %lld triangles or %lld vertices exceed one launch", (long long)n * T,
                    (long long)n * V);
-        TF_REQUIRE(!j.shade || j.colors_per_head, "render_meshes: shading writes one colour table per head (colors_per_head must be 1)");
+        CH_REQUIRE(!j.shade || j.colors_per_head, "render_meshes: shading writes one colour table per head (colors_per_head must be 1)");
         if (j.shade) {
             const float c[8] = {j.color[0], j.color[1], j.color[2], j.ambient, j.diffuse, j.light[0], j.light[1], j.light[2]};
-            for (int i = 0; i < 8; ++i) TF_REQUIRE(c[i] == c[i] && c[i] - c[i] == 0.0f, "render_meshes: a shading constant is not finite");
-            TF_REQUIRE(j.color[0] >= 0 && j.color[0] <= 1 && j.color[1] >= 0 && j.color[1] <= 1 && j.color[2] >= 0 && j.color[2] <= 1 && j.ambient >= 0 && j.diffuse >= 0,
+            for (int i = 0; i < 8; ++i) CH_REQUIRE(c[i] == c[i] && c[i] - c[i] == 0.0f, "render_meshes: a shading constant is not finite");
+            CH_REQUIRE(j.color[0] >= 0 && j.color[0] <= 1 && j.color[1] >= 0 && j.color[1] <= 1 && j.color[2] >= 0 && j.color[2] <= 1 && j.ambient >= 0 && j.diffuse >= 0,
                        "render_meshes: colour outside 0 .. 1 or negative ambient / diffuse");
         }
         if (int rc = check_triangles("render_meshes", j.triangles, T, V)) return rc;
         if (const int i = first_bad_bound(j.bounds, n, W, H); i >= 0) {
             const int32_t* b = j.bounds + 4 * i;
-            TF_REQUIRE(false, "render_meshes: head %d: bounds (%d, %d, %d, %d) outside the image", i, b[0], b[1], b[2], b[3]);
+            CH_REQUIRE(false, "render_meshes: head %d: bounds (%d, %d, %d, %d) outside the image", i, b[0], b[1], b[2], b[3]);
         }
     }
     hipStream_t st = (hipStream_t)stream;
     int device = 0;
-    TF_HIP(hipGetDevice(&device));
+    CH_HIP(hipGetDevice(&device));
     std::lock_guard<std::mutex> lock(g_mutex);
     State& s = g_state[device];
     TileLists lists;
     if (paint) lists.count(j.bounds, n, W, H);
     const size_t n_tiles = lists.n_tiles, n_pairs = lists.n_pairs;
-    TF_REQUIRE(n_pairs <= (size_t)INT32_MAX, "render_meshes: %zu (tile, head) pairs exceed one launch", n_pairs);
+    CH_REQUIRE(n_pairs <= (size_t)INT32_MAX, "render_meshes: %zu (tile, head) pairs exceed one launch", n_pairs);
     const bool tiles = n_tiles > 0, work = tiles || (paint && j.shade);  // with shade the colours are written even when no head touches the image
     // one upload: [triangles | first, incident (shading only) | tile_xy | tile_first | tile_heads], each from a 16-byte boundary
     const size_t at_inc = align16((size_t)T * 12), at_xy = at_inc + (work && j.shade ? incidence_bytes(T, V) : 0), at_first = at_xy + align16(n_tiles * 4);
@@ -282,19 +281,19 @@ extern "C" VGHV_API int vghv_render_meshes(const vghv_mesh_job* job, void* strea
         if (j.shade) build_incidence(j.triangles, T, V, (int32_t*)(h + at_inc), (int32_t*)(h + at_inc + align16(((size_t)V + 1) * 4)));
         lists.fill((uint32_t*)(h + at_xy), (int32_t*)(h + at_first), (int32_t*)(h + at_heads));
     }
-    // from here on work is queued (tile_fold.h, queue-then-record).  dst = src everywhere; the tiles that some head touches are then rewritten from src
+    // from here on work is queued (companion_host.h, queue-then-record).  dst = src everywhere; the tiles that some head touches are then rewritten from src
     Queue q;
-    TF_QUEUE(q, hipMemcpy2DAsync(j.dst_dev, (size_t)W * 3, j.src_dev, (size_t)j.src_pitch_bytes, (size_t)W * 3, (size_t)H, hipMemcpyDeviceToDevice, st));
+    CH_QUEUE(q, hipMemcpy2DAsync(j.dst_dev, (size_t)W * 3, j.src_dev, (size_t)j.src_pitch_bytes, (size_t)W * 3, (size_t)H, hipMemcpyDeviceToDevice, st));
     const uint8_t* d = s.dev;
-    if (work) TF_QUEUE(q, hipMemcpyAsync(s.dev, s.host, total, hipMemcpyHostToDevice, st));
+    if (work) CH_QUEUE(q, hipMemcpyAsync(s.dev, s.host, total, hipMemcpyHostToDevice, st));
     if (work && j.shade && q.ok()) {
         const Shade sh = {j.color[0], j.color[1], j.color[2], j.ambient, j.diffuse, j.light[0], j.light[1], j.light[2]};
         launch_normals(j.verts_dev, d, d + at_inc, n, V, j.z_sign, 1, sh, j.colors_dev, st);
     }
     if (tiles && q.ok()) {
-        hipLaunchKernelGGL(boxes_kernel, dim3((unsigned)(n * T + 255) / 256), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, n * T, V, T, H, W, s.boxes);
+        hipLaunchKernelGGL(boxes_kernel, dim3((unsigned)(n * T + 255) / 256), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, n * T, V, T, H, W, s.boxes.ptr);
         hipLaunchKernelGGL(tiles_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, (const float*)j.colors_dev,
-                           j.colors_per_head ? (size_t)V * 3 : (size_t)0, (const Box*)s.boxes, (const uint32_t*)(d + at_xy), (const int32_t*)(d + at_first),
+                           j.colors_per_head ? (size_t)V * 3 : (size_t)0, (const Box*)s.boxes.ptr, (const uint32_t*)(d + at_xy), (const int32_t*)(d + at_first),
                            (const int32_t*)(d + at_heads), V, T, H, W, j.reverse ? 1 : 0, j.z_sign, j.alpha, j.src_dev, j.src_pitch_bytes, j.dst_dev);
     }
     return finish(q, s, work, st, "render_meshes");

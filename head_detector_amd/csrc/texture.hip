@@ -23,7 +23,7 @@
 namespace {
 
 using namespace tile_fold;
-static_assert(VGHTEX_OK == OK && VGHTEX_ERR_INVALID == ERR_INVALID && VGHTEX_ERR_HIP == ERR_HIP && VGHTEX_ERR_NOMEM == ERR_NOMEM, "tile_fold.h returns these codes");
+static_assert(VGHTEX_OK == OK && VGHTEX_ERR_INVALID == ERR_INVALID && VGHTEX_ERR_HIP == ERR_HIP && VGHTEX_ERR_NOMEM == ERR_NOMEM, "companion_host.h returns these codes");
 
 // ---- the background of depth, triangle and head ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void fill_kernel(size_t n_px, float* __restrict__ depth, int32_t* __restrict__ tri, int32_t* __restrict__ head) {
@@ -174,48 +174,48 @@ inline bool is_flag(int32_t v) { return v == 0 || v == 1; }
 
 extern "C" VGHTEX_API const char* vghtex_version(void) { return "vghtex 1 (gfx950)"; }
 
-extern "C" VGHTEX_API const char* vghtex_last_error(void) { return tile_fold::g_error; }
+extern "C" VGHTEX_API const char* vghtex_last_error(void) { return last_error(); }
 
 extern "C" VGHTEX_API int vghtex_render_texture(const vghtex_job* job, void* stream) {
-    TF_REQUIRE(job, "render_texture: null job");
+    CH_REQUIRE(job, "render_texture: null job");
     const vghtex_job& j = *job;
     // everything is checked before anything is allocated, written or queued
-    TF_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHTEX_MAX_SIDE && j.width <= VGHTEX_MAX_SIDE, "render_texture: height x width %d x %d outside 1 .. %d", j.height,
+    CH_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHTEX_MAX_SIDE && j.width <= VGHTEX_MAX_SIDE, "render_texture: height x width %d x %d outside 1 .. %d", j.height,
                j.width, VGHTEX_MAX_SIDE);
     const int W = j.width, H = j.height, n = j.n_heads, V = j.n_vertices, T = j.n_triangles, Vt = j.n_tex_vertices, c = j.channels;
-    TF_REQUIRE(c >= 1 && c <= VGHTEX_MAX_CHANNELS, "render_texture: channels %d outside 1 .. %d", c, VGHTEX_MAX_CHANNELS);
-    TF_REQUIRE(n >= 0 && n <= VGHTEX_MAX_HEADS, "render_texture: n_heads %d outside 0 .. %d", n, VGHTEX_MAX_HEADS);
-    TF_REQUIRE(V >= 0, "render_texture: n_vertices %d is negative", V);
-    TF_REQUIRE(T >= 0, "render_texture: n_triangles %d is negative", T);
-    TF_REQUIRE(Vt >= 0, "render_texture: n_tex_vertices %d is negative", Vt);
-    TF_REQUIRE(j.tex_height >= 1 && j.tex_width >= 1 && j.tex_height <= VGHTEX_MAX_SIDE && j.tex_width <= VGHTEX_MAX_SIDE,
+    CH_REQUIRE(c >= 1 && c <= VGHTEX_MAX_CHANNELS, "render_texture: channels %d outside 1 .. %d", c, VGHTEX_MAX_CHANNELS);
+    CH_REQUIRE(n >= 0 && n <= VGHTEX_MAX_HEADS, "render_texture: n_heads %d outside 0 .. %d", n, VGHTEX_MAX_HEADS);
+    CH_REQUIRE(V >= 0, "render_texture: n_vertices %d is negative", V);
+    CH_REQUIRE(T >= 0, "render_texture: n_triangles %d is negative", T);
+    CH_REQUIRE(Vt >= 0, "render_texture: n_tex_vertices %d is negative", Vt);
+    CH_REQUIRE(j.tex_height >= 1 && j.tex_width >= 1 && j.tex_height <= VGHTEX_MAX_SIDE && j.tex_width <= VGHTEX_MAX_SIDE,
                "render_texture: tex_height x tex_width %d x %d outside 1 .. %d", j.tex_height, j.tex_width, VGHTEX_MAX_SIDE);
-    TF_REQUIRE(j.tex_channels >= c, "render_texture: tex_channels %d below channels %d", j.tex_channels, c);
-    TF_REQUIRE(j.tex_dtype == VGHTEX_TEX_F32 || j.tex_dtype == VGHTEX_TEX_U8, "render_texture: tex_dtype %d is neither 0 (f32) nor 1 (u8)", j.tex_dtype);
-    TF_REQUIRE(is_flag(j.tex_per_head), "render_texture: tex_per_head %d is neither 0 nor 1", j.tex_per_head);
-    TF_REQUIRE(is_flag(j.tex_coords_per_head), "render_texture: tex_coords_per_head %d is neither 0 nor 1", j.tex_coords_per_head);
-    TF_REQUIRE(is_flag(j.dst_per_head), "render_texture: dst_per_head %d is neither 0 nor 1", j.dst_per_head);
-    TF_REQUIRE(j.mapping == VGHTEX_MAP_NEAREST || j.mapping == VGHTEX_MAP_BILINEAR, "render_texture: mapping %d is neither 0 (nearest) nor 1 (bilinear)", j.mapping);
-    TF_REQUIRE(j.mode == VGHTEX_MODE_ORDER || j.mode == VGHTEX_MODE_DEPTH, "render_texture: mode %d is neither 0 (order) nor 1 (depth)", j.mode);
-    TF_REQUIRE(j.z_sign == 1.0f || j.z_sign == -1.0f, "render_texture: z_sign %g is neither +1 nor -1", (double)j.z_sign);
+    CH_REQUIRE(j.tex_channels >= c, "render_texture: tex_channels %d below channels %d", j.tex_channels, c);
+    CH_REQUIRE(j.tex_dtype == VGHTEX_TEX_F32 || j.tex_dtype == VGHTEX_TEX_U8, "render_texture: tex_dtype %d is neither 0 (f32) nor 1 (u8)", j.tex_dtype);
+    CH_REQUIRE(is_flag(j.tex_per_head), "render_texture: tex_per_head %d is neither 0 nor 1", j.tex_per_head);
+    CH_REQUIRE(is_flag(j.tex_coords_per_head), "render_texture: tex_coords_per_head %d is neither 0 nor 1", j.tex_coords_per_head);
+    CH_REQUIRE(is_flag(j.dst_per_head), "render_texture: dst_per_head %d is neither 0 nor 1", j.dst_per_head);
+    CH_REQUIRE(j.mapping == VGHTEX_MAP_NEAREST || j.mapping == VGHTEX_MAP_BILINEAR, "render_texture: mapping %d is neither 0 (nearest) nor 1 (bilinear)", j.mapping);
+    CH_REQUIRE(j.mode == VGHTEX_MODE_ORDER || j.mode == VGHTEX_MODE_DEPTH, "render_texture: mode %d is neither 0 (order) nor 1 (depth)", j.mode);
+    CH_REQUIRE(j.z_sign == 1.0f || j.z_sign == -1.0f, "render_texture: z_sign %g is neither +1 nor -1", (double)j.z_sign);
     const size_t slices = j.dst_per_head ? (size_t)n : 1;
     const size_t n_px = slices * (size_t)H * (size_t)W;
-    TF_REQUIRE(n_px / 256 < (size_t)INT32_MAX, "render_texture: %zu destination pixels exceed one launch", n_px);
+    CH_REQUIRE(n_px / 256 < (size_t)INT32_MAX, "render_texture: %zu destination pixels exceed one launch", n_px);
     if (n_px) {
-        TF_REQUIRE(j.dst_dev, "render_texture: null dst_dev");
-        TF_REQUIRE(j.depth_dev, "render_texture: null depth_dev");
+        CH_REQUIRE(j.dst_dev, "render_texture: null dst_dev");
+        CH_REQUIRE(j.depth_dev, "render_texture: null depth_dev");
     }
     const bool raster = n > 0 && T > 0;
     if (raster) {
-        TF_REQUIRE(V >= 1, "render_texture: n_vertices %d with %d triangles", V, T);
-        TF_REQUIRE(Vt >= 1, "render_texture: n_tex_vertices %d with %d triangles", Vt, T);
-        TF_REQUIRE(j.verts_dev, "render_texture: null verts_dev");
-        TF_REQUIRE(j.triangles, "render_texture: null triangles");
-        TF_REQUIRE(j.tex_coords_dev, "render_texture: null tex_coords_dev");
-        TF_REQUIRE(j.tex_triangles, "render_texture: null tex_triangles");
-        TF_REQUIRE(j.texture_dev, "render_texture: null texture_dev");
-        TF_REQUIRE(j.bounds, "render_texture: null bounds");
-        TF_REQUIRE((int64_t)n * T <= INT32_MAX / 4 && (int64_t)n * V <= INT32_MAX / 4 && (int64_t)n * Vt <= INT32_MAX / 4,
+        CH_REQUIRE(V >= 1, "render_texture: n_vertices %d with %d triangles", V, T);
+        CH_REQUIRE(Vt >= 1, "render_texture: n_tex_vertices %d with %d triangles", Vt, T);
+        CH_REQUIRE(j.verts_dev, "render_texture: null verts_dev");
+        CH_REQUIRE(j.triangles, "render_texture: null triangles");
+        CH_REQUIRE(j.tex_coords_dev, "render_texture: null tex_coords_dev");
+        CH_REQUIRE(j.tex_triangles, "render_texture: null tex_triangles");
+        CH_REQUIRE(j.texture_dev, "render_texture: null texture_dev");
+        CH_REQUIRE(j.bounds, "render_texture: null bounds");
+        CH_REQUIRE((int64_t)n * T <= INT32_MAX / 4 && (int64_t)n * V <= INT32_MAX / 4 && (int64_t)n * Vt <= INT32_MAX / 4,
                    "render_texture: n_heads * n_triangles = %lld, n_heads * n_vertices = %lld or n_heads * n_tex_vertices = %lld exceed one launch", (long long)n * T,
                    (long long)n * V, (long long)n * Vt);
         // a mesh index reads a vertex and, for the corner's texture y, a texture coordinate
@@ -223,22 +223,22 @@ extern "C" VGHTEX_API int vghtex_render_texture(const vghtex_job* job, void* str
         // what is reported is what one pass over the corners, looking at triangles[i] before tex_triangles[i], meets first: the earlier corner, the mesh's on a tie
         if (bad >= 0 && (bad_tex < 0 || bad <= bad_tex)) {
             const int32_t v = j.triangles[bad];
-            TF_REQUIRE(v >= 0 && v < V, "render_texture: triangles: triangle %lld: index %d outside the %d vertices", (long long)(bad / 3), v, V);
-            TF_REQUIRE(false, "render_texture: triangles: triangle %lld: index %d outside the %d texture coordinates (a corner's texture y is read through it)", (long long)(bad / 3), v, Vt);
+            CH_REQUIRE(v >= 0 && v < V, "render_texture: triangles: triangle %lld: index %d outside the %d vertices", (long long)(bad / 3), v, V);
+            CH_REQUIRE(false, "render_texture: triangles: triangle %lld: index %d outside the %d texture coordinates (a corner's texture y is read through it)", (long long)(bad / 3), v, Vt);
         }
-        TF_REQUIRE(bad_tex < 0, "render_texture: tex_triangles: triangle %lld: index %d outside the %d texture coordinates", (long long)(bad_tex / 3), j.tex_triangles[bad_tex], Vt);
+        CH_REQUIRE(bad_tex < 0, "render_texture: tex_triangles: triangle %lld: index %d outside the %d texture coordinates", (long long)(bad_tex / 3), j.tex_triangles[bad_tex], Vt);
         if (const int i = first_bad_bound(j.bounds, n, W, H); i >= 0) {
             const int32_t* b = j.bounds + 4 * i;
-            TF_REQUIRE(false, "render_texture: bounds: head %d: (%d, %d, %d, %d) outside the image", i, b[0], b[1], b[2], b[3]);
+            CH_REQUIRE(false, "render_texture: bounds: head %d: (%d, %d, %d, %d) outside the image", i, b[0], b[1], b[2], b[3]);
         }
     }
     TileLists lists;
     if (raster) lists.count(j.bounds, n, W, H, j.dst_per_head != 0);
     const size_t n_tiles = lists.n_tiles, n_pairs = lists.n_pairs;
-    TF_REQUIRE(n_pairs <= (size_t)INT32_MAX, "render_texture: %zu (tile, head) pairs exceed one launch", n_pairs);
+    CH_REQUIRE(n_pairs <= (size_t)INT32_MAX, "render_texture: %zu (tile, head) pairs exceed one launch", n_pairs);
     hipStream_t st = (hipStream_t)stream;
     int device = 0;
-    TF_HIP(hipGetDevice(&device));
+    CH_HIP(hipGetDevice(&device));
     std::lock_guard<std::mutex> lock(g_mutex);
     State& s = g_state[device];
     // one upload: [triangles | tex_triangles | tile_xy | tile_first | tile_heads], each from a 16-byte boundary
@@ -251,9 +251,9 @@ extern "C" VGHTEX_API int vghtex_render_texture(const vghtex_job* job, void* str
         memcpy(h + at_tt, j.tex_triangles, (size_t)T * 12);
         lists.fill((uint32_t*)(h + at_xy), (int32_t*)(h + at_first), (int32_t*)(h + at_heads));
     }
-    // from here on work is queued (tile_fold.h, queue-then-record)
+    // from here on work is queued (companion_host.h, queue-then-record)
     Queue q;
-    if (n_tiles) TF_QUEUE(q, hipMemcpyAsync(s.dev, s.host, total, hipMemcpyHostToDevice, st));  // first: whatever follows, the event covers the staging block
+    if (n_tiles) CH_QUEUE(q, hipMemcpyAsync(s.dev, s.host, total, hipMemcpyHostToDevice, st));  // first: whatever follows, the event covers the staging block
     if (n_px && q.ok()) hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, st, n_px, j.depth_dev, j.triangle_dev, j.head_dev);
     if (n_tiles && q.ok()) {
         const uint8_t* d = s.dev;
@@ -268,8 +268,8 @@ extern "C" VGHTEX_API int vghtex_render_texture(const vghtex_job* job, void* str
         ta.tex_per_head = j.tex_per_head;
         ta.is_u8 = j.tex_dtype == VGHTEX_TEX_U8;
         ta.bilinear = j.mapping != VGHTEX_MAP_NEAREST;
-        hipLaunchKernelGGL(boxes_kernel, dim3((unsigned)(n * T + 255) / 256), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, n * T, V, T, H, W, s.boxes);
-        hipLaunchKernelGGL(tiles_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, (const int32_t*)(d + at_tt), (const Box*)s.boxes,
+        hipLaunchKernelGGL(boxes_kernel, dim3((unsigned)(n * T + 255) / 256), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, n * T, V, T, H, W, s.boxes.ptr);
+        hipLaunchKernelGGL(tiles_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, (const int32_t*)(d + at_tt), (const Box*)s.boxes.ptr,
                            (const uint32_t*)(d + at_xy), (const int32_t*)(d + at_first), (const int32_t*)(d + at_heads), ta, V, T, H, W, c, j.mode == VGHTEX_MODE_DEPTH ? 1 : 0,
                            j.dst_per_head, j.z_sign, j.dst_dev, j.depth_dev, j.triangle_dev, j.head_dev);
     }

@@ -1,5 +1,6 @@
 // The tile-major triangle fold that csrc/mesh_render.hip (libvghview.so), csrc/visibility.hip (libvghvis.so) and csrc/texture.hip (libvghtex.so) share,
-// and the host plumbing around it.  Header-only and internal: every definition has internal linkage or is inline, so each library compiles its own copy
+// and the host half of it (argument scans, TileLists, the per-device State); the plumbing every companion library needs is csrc/companion_host.h.
+// Header-only and internal: every definition has internal linkage or is inline, so each library compiles its own copy
 // and stays a library of its own (no shared object, no exported symbol, no link dependency).
 //
 // A pixel of Sim3DR's rasterisers is a serial fold over heads (in order) and over the head's triangles (in index order).  Tile-major:
@@ -12,72 +13,18 @@
 // What a library does with a triangle (its Hit payload, its inside rule, what a win changes, the write-back) is the library's; so is its fold loop.
 // All arithmetic is IEEE float32 in the reference's operation order: contraction is off here and in every includer.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stddef.h>
-#include <stdint.h>
-#include <stdio.h>
-
 #include <vector>
+
+#include "companion_host.h"
 
 #pragma clang fp contract(off)
 
 namespace tile_fold {
+using namespace companion;
 namespace {
 
 constexpr int TILE = 16;             // 16 x 16 pixels = the 256 lanes of a workgroup
 constexpr float BACKGROUND = -1e8f;  // what Sim3DR's callers initialise the depth buffer with (Sim3DR.py:31)
-
-// ---- error plumbing: never throw across the C ABI -------------------------------------------------------------------------------------------------
-// The codes of the four public headers are the same numbers; every includer static_asserts its own against these.
-constexpr int OK = 0, ERR_INVALID = -1, ERR_HIP = -2, ERR_NOMEM = -3;
-
-#ifndef TILE_FOLD_SET_ERROR  // a library whose sources already share a message (vghv_internal.h) names its own function before including this
-#define TILE_FOLD_SET_ERROR tile_fold::set_error
-thread_local char g_error[512] = "";
-
-void set_error(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-void set_error(const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_error, sizeof(g_error), fmt, ap);
-    va_end(ap);
-}
-#endif
-
-// check: a HIP call that must succeed before anything is queued
-#define TF_HIP(expr)                                                                                  \
-    do {                                                                                              \
-        hipError_t _e = (expr);                                                                       \
-        if (_e != hipSuccess) {                                                                       \
-            TILE_FOLD_SET_ERROR("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e)); \
-            return tile_fold::ERR_HIP;                                                                \
-        }                                                                                             \
-    } while (0)
-
-// require: an argument check
-#define TF_REQUIRE(cond, ...)                 \
-    do {                                      \
-        if (!(cond)) {                        \
-            TILE_FOLD_SET_ERROR(__VA_ARGS__); \
-            return tile_fold::ERR_INVALID;    \
-        }                                     \
-    } while (0)
-
-// queue-then-record: from the staging copy on, the first failure is kept and nothing more is queued after it (TF_QUEUE; launches ask q.ok()), and
-// finish() records the event on every path, so that the next call never rewrites the staging block or the boxes under work that is still queued.
-struct Queue {
-    hipError_t err = hipSuccess;
-    const char* failed = "";
-    bool ok() const { return err == hipSuccess; }
-};
-#define TF_QUEUE(q, expr)                                  \
-    do {                                                   \
-        if ((q).ok()) {                                    \
-            (q).err = (expr);                              \
-            if (!(q).ok()) (q).failed = #expr;             \
-        }                                                  \
-    } while (0)
 
 // ---- the triangle's integer box (rasterize_kernel.cpp:245-253, :321-329, :406-415) -----------------------------------------------------------------
 struct alignas(8) Box {
@@ -229,67 +176,19 @@ struct TileLists {
     }
 };
 
-// ---- host: per-device state: what one call uploads (one pinned and one device block, guarded by an event) and the boxes --------------------------------
-// A block is rewritten only after the previous call's copy and kernels have run (the event), whatever stream they were queued on.
-struct State {
-    uint8_t* host = nullptr;
-    uint8_t* dev = nullptr;
-    size_t bytes = 0;
-    hipEvent_t ev = nullptr;
-    bool recorded = false;
-    Box* boxes = nullptr;  // library scratch [n, T], grown on demand
-    size_t box_bytes = 0;
+// ---- host: per-device state: the staging block of what one call uploads and the boxes, both guarded by the block's event (companion_host.h) ----------
+struct State : Staging {
+    Scratch<Box> boxes;  // library scratch [n, T]
 };
-
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // waits for the blocks' previous user, then makes room for `need` staging bytes and `need_boxes` bytes of boxes; `who` names the caller in the message
 inline int reserve(State& s, size_t need, size_t need_boxes, const char* who) {
-    if (s.recorded) TF_HIP(hipEventSynchronize(s.ev));
-    s.recorded = false;
-    if (!s.ev) TF_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    if (need > s.bytes) {
-        hipHostFree(s.host);
-        hipFree(s.dev);
-        s.host = s.dev = nullptr;
-        s.bytes = 0;
-        const size_t cap = align16(need + need / 2);
-        if (hipHostMalloc((void**)&s.host, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&s.dev, cap) != hipSuccess) {
-            hipHostFree(s.host);
-            s.host = nullptr;
-            TILE_FOLD_SET_ERROR("%s: allocating %zu bytes of staging failed", who, cap);
-            return ERR_NOMEM;
-        }
-        s.bytes = cap;
-    }
-    if (need_boxes > s.box_bytes) {  // nothing is using the old boxes: the wait above covered the previous call's kernels
-        hipFree(s.boxes);
-        s.boxes = nullptr;
-        s.box_bytes = 0;
-        if (hipMalloc((void**)&s.boxes, need_boxes) != hipSuccess) {
-            TILE_FOLD_SET_ERROR("%s: allocating %zu bytes of triangle boxes failed", who, need_boxes);
-            return ERR_NOMEM;
-        }
-        s.box_bytes = need_boxes;
+    if (int rc = companion::reserve(s, need, who)) return rc;
+    if (!grow(s.boxes, need_boxes)) {
+        set_error("%s: allocating %zu bytes of triangle boxes failed", who, need_boxes);
+        return ERR_NOMEM;
     }
     return OK;
-}
-
-// The end of queue-then-record.  `staged`: the call queued the staging copy, so the event has to cover it; if it cannot be recorded the stream is
-// waited for instead.  Returns the call's code and words the first failure as "<who>: <call> -> <HIP's message>".
-inline int finish(Queue& q, State& s, bool staged, hipStream_t st, const char* who) {
-    TF_QUEUE(q, hipGetLastError());
-    if (staged) {
-        if (hipEventRecord(s.ev, st) == hipSuccess) {
-            s.recorded = true;
-        } else {
-            hipStreamSynchronize(st);  // no event to wait for next time: wait now
-            TF_QUEUE(q, hipErrorUnknown);
-        }
-    }
-    if (q.ok()) return OK;
-    TILE_FOLD_SET_ERROR("%s: %s -> %s", who, q.failed, hipGetErrorString(q.err));
-    return ERR_HIP;
 }
 
 }  // namespace

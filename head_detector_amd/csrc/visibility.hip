@@ -23,7 +23,7 @@
 namespace {
 
 using namespace tile_fold;
-static_assert(VGHVIS_OK == OK && VGHVIS_ERR_INVALID == ERR_INVALID && VGHVIS_ERR_HIP == ERR_HIP && VGHVIS_ERR_NOMEM == ERR_NOMEM, "tile_fold.h returns these codes");
+static_assert(VGHVIS_OK == OK && VGHVIS_ERR_INVALID == ERR_INVALID && VGHVIS_ERR_HIP == ERR_HIP && VGHVIS_ERR_NOMEM == ERR_NOMEM, "companion_host.h returns these codes");
 
 // ---- the background of every output ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void fill_kernel(size_t n_px, float* __restrict__ depth, int32_t* __restrict__ tri, int32_t* __restrict__ head, float* __restrict__ bary) {
@@ -152,46 +152,46 @@ std::map<int, State> g_state;
 
 extern "C" VGHVIS_API const char* vghvis_version(void) { return "vghvis 1 (gfx950)"; }
 
-extern "C" VGHVIS_API const char* vghvis_last_error(void) { return tile_fold::g_error; }
+extern "C" VGHVIS_API const char* vghvis_last_error(void) { return last_error(); }
 
 extern "C" VGHVIS_API int vghvis_rasterize_triangles(const vghvis_job* job, void* stream) {
-    TF_REQUIRE(job, "rasterize_triangles: null job");
+    CH_REQUIRE(job, "rasterize_triangles: null job");
     const vghvis_job& j = *job;
     // everything is checked before anything is allocated, written or queued
-    TF_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHVIS_MAX_SIDE && j.width <= VGHVIS_MAX_SIDE, "rasterize_triangles: height x width %d x %d outside 1 .. %d",
+    CH_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHVIS_MAX_SIDE && j.width <= VGHVIS_MAX_SIDE, "rasterize_triangles: height x width %d x %d outside 1 .. %d",
                j.height, j.width, VGHVIS_MAX_SIDE);
     const int W = j.width, H = j.height, n = j.n_heads, V = j.n_vertices, T = j.n_triangles;
-    TF_REQUIRE(n >= 0 && n <= VGHVIS_MAX_HEADS, "rasterize_triangles: n_heads %d outside 0 .. %d", n, VGHVIS_MAX_HEADS);
-    TF_REQUIRE(V >= 0, "rasterize_triangles: n_vertices %d is negative", V);
-    TF_REQUIRE(T >= 0, "rasterize_triangles: n_triangles %d is negative", T);
-    TF_REQUIRE(j.mode == VGHVIS_MODE_ORDER || j.mode == VGHVIS_MODE_DEPTH, "rasterize_triangles: mode %d is neither 0 (order) nor 1 (depth)", j.mode);
-    TF_REQUIRE(j.z_sign == 1.0f || j.z_sign == -1.0f, "rasterize_triangles: z_sign %g is neither +1 nor -1", (double)j.z_sign);
-    TF_REQUIRE(j.depth_dev, "rasterize_triangles: null depth_dev");
-    TF_REQUIRE(j.triangle_dev, "rasterize_triangles: null triangle_dev");
-    TF_REQUIRE(j.head_dev, "rasterize_triangles: null head_dev");
-    TF_REQUIRE(!j.vertex_visible_dev || n == 0 || V >= 1, "rasterize_triangles: vertex_visible_dev with n_vertices %d", V);
+    CH_REQUIRE(n >= 0 && n <= VGHVIS_MAX_HEADS, "rasterize_triangles: n_heads %d outside 0 .. %d", n, VGHVIS_MAX_HEADS);
+    CH_REQUIRE(V >= 0, "rasterize_triangles: n_vertices %d is negative", V);
+    CH_REQUIRE(T >= 0, "rasterize_triangles: n_triangles %d is negative", T);
+    CH_REQUIRE(j.mode == VGHVIS_MODE_ORDER || j.mode == VGHVIS_MODE_DEPTH, "rasterize_triangles: mode %d is neither 0 (order) nor 1 (depth)", j.mode);
+    CH_REQUIRE(j.z_sign == 1.0f || j.z_sign == -1.0f, "rasterize_triangles: z_sign %g is neither +1 nor -1", (double)j.z_sign);
+    CH_REQUIRE(j.depth_dev, "rasterize_triangles: null depth_dev");
+    CH_REQUIRE(j.triangle_dev, "rasterize_triangles: null triangle_dev");
+    CH_REQUIRE(j.head_dev, "rasterize_triangles: null head_dev");
+    CH_REQUIRE(!j.vertex_visible_dev || n == 0 || V >= 1, "rasterize_triangles: vertex_visible_dev with n_vertices %d", V);
     const bool raster = n > 0 && T > 0;
     if (raster) {
-        TF_REQUIRE(V >= 1, "rasterize_triangles: n_vertices %d with %d triangles", V, T);
-        TF_REQUIRE(j.verts_dev, "rasterize_triangles: null verts_dev");
-        TF_REQUIRE(j.triangles, "rasterize_triangles: null triangles");
-        TF_REQUIRE(j.bounds, "rasterize_triangles: null bounds");
-        TF_REQUIRE((int64_t)n * T <= INT32_MAX / 4 && (int64_t)n * V <= INT32_MAX / 4, "rasterize_triangles: n_heads * n_triangles = %lld or n_heads * n_vertices = %lld exceed one launch",
+        CH_REQUIRE(V >= 1, "rasterize_triangles: n_vertices %d with %d triangles", V, T);
+        CH_REQUIRE(j.verts_dev, "rasterize_triangles: null verts_dev");
+        CH_REQUIRE(j.triangles, "rasterize_triangles: null triangles");
+        CH_REQUIRE(j.bounds, "rasterize_triangles: null bounds");
+        CH_REQUIRE((int64_t)n * T <= INT32_MAX / 4 && (int64_t)n * V <= INT32_MAX / 4, "rasterize_triangles: n_heads * n_triangles = %lld or n_heads * n_vertices = %lld exceed one launch",
                    (long long)n * T, (long long)n * V);
         const int64_t bad = first_bad_index(j.triangles, (int64_t)T * 3, V);
-        TF_REQUIRE(bad < 0, "rasterize_triangles: triangles: triangle %lld: index %d outside the %d vertices", (long long)(bad / 3), j.triangles[bad], V);
+        CH_REQUIRE(bad < 0, "rasterize_triangles: triangles: triangle %lld: index %d outside the %d vertices", (long long)(bad / 3), j.triangles[bad], V);
         if (const int i = first_bad_bound(j.bounds, n, W, H); i >= 0) {
             const int32_t* b = j.bounds + 4 * i;
-            TF_REQUIRE(false, "rasterize_triangles: bounds: head %d: (%d, %d, %d, %d) outside the image", i, b[0], b[1], b[2], b[3]);
+            CH_REQUIRE(false, "rasterize_triangles: bounds: head %d: (%d, %d, %d, %d) outside the image", i, b[0], b[1], b[2], b[3]);
         }
     }
     TileLists lists;
     if (raster) lists.count(j.bounds, n, W, H);
     const size_t n_tiles = lists.n_tiles, n_pairs = lists.n_pairs;
-    TF_REQUIRE(n_pairs <= (size_t)INT32_MAX, "rasterize_triangles: %zu (tile, head) pairs exceed one launch", n_pairs);
+    CH_REQUIRE(n_pairs <= (size_t)INT32_MAX, "rasterize_triangles: %zu (tile, head) pairs exceed one launch", n_pairs);
     hipStream_t st = (hipStream_t)stream;
     int device = 0;
-    TF_HIP(hipGetDevice(&device));
+    CH_HIP(hipGetDevice(&device));
     std::lock_guard<std::mutex> lock(g_mutex);
     State& s = g_state[device];
     // one upload: [triangles | tile_xy | tile_first | tile_heads], each from a 16-byte boundary
@@ -203,20 +203,20 @@ extern "C" VGHVIS_API int vghvis_rasterize_triangles(const vghvis_job* job, void
         memcpy(h, j.triangles, (size_t)T * 12);
         lists.fill((uint32_t*)(h + at_xy), (int32_t*)(h + at_first), (int32_t*)(h + at_heads));
     }
-    // from here on work is queued (tile_fold.h, queue-then-record)
+    // from here on work is queued (companion_host.h, queue-then-record)
     const size_t n_px = (size_t)H * W;
     Queue q;
-    if (n_tiles) TF_QUEUE(q, hipMemcpyAsync(s.dev, s.host, total, hipMemcpyHostToDevice, st));  // first: whatever follows, the event covers the staging block
+    if (n_tiles) CH_QUEUE(q, hipMemcpyAsync(s.dev, s.host, total, hipMemcpyHostToDevice, st));  // first: whatever follows, the event covers the staging block
     if (q.ok()) hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((n_px + 255) / 256)), dim3(256), 0, st, n_px, j.depth_dev, j.triangle_dev, j.head_dev, j.bary_dev);
     if (n) {
-        if (j.visible_px_dev) TF_QUEUE(q, hipMemsetAsync(j.visible_px_dev, 0, (size_t)n * 4, st));
-        if (j.covered_px_dev) TF_QUEUE(q, hipMemsetAsync(j.covered_px_dev, 0, (size_t)n * 4, st));
-        if (j.vertex_visible_dev) TF_QUEUE(q, hipMemsetAsync(j.vertex_visible_dev, 0, (size_t)n * V, st));
+        if (j.visible_px_dev) CH_QUEUE(q, hipMemsetAsync(j.visible_px_dev, 0, (size_t)n * 4, st));
+        if (j.covered_px_dev) CH_QUEUE(q, hipMemsetAsync(j.covered_px_dev, 0, (size_t)n * 4, st));
+        if (j.vertex_visible_dev) CH_QUEUE(q, hipMemsetAsync(j.vertex_visible_dev, 0, (size_t)n * V, st));
     }
     if (n_tiles && q.ok()) {
         const uint8_t* d = s.dev;
-        hipLaunchKernelGGL(boxes_kernel, dim3((unsigned)(n * T + 255) / 256), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, n * T, V, T, H, W, s.boxes);
-        hipLaunchKernelGGL(tiles_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, (const Box*)s.boxes, (const uint32_t*)(d + at_xy),
+        hipLaunchKernelGGL(boxes_kernel, dim3((unsigned)(n * T + 255) / 256), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, n * T, V, T, H, W, s.boxes.ptr);
+        hipLaunchKernelGGL(tiles_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, j.verts_dev, (const int32_t*)d, (const Box*)s.boxes.ptr, (const uint32_t*)(d + at_xy),
                            (const int32_t*)(d + at_first), (const int32_t*)(d + at_heads), V, T, H, W, j.mode == VGHVIS_MODE_DEPTH ? 1 : 0, j.z_sign, j.depth_dev, j.triangle_dev,
                            j.head_dev, j.bary_dev, j.visible_px_dev, j.covered_px_dev, j.vertex_visible_dev);
     }

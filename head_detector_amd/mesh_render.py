@@ -26,7 +26,7 @@ import torch
 
 from . import _lib_view
 from .aligned import _device_image
-from .mesh_geometry import check_triangles as _triangles, pixel_bounds  # noqa: F401  (pixel_bounds is part of this module's surface)
+from .mesh_geometry import check_triangles as _triangles, device_of, head_vertices, pixel_bounds, require_faces, to_device  # noqa: F401  (pixel_bounds is part of this module's surface)
 
 
 def check_shading(alpha, color, ambient, diffuse, light) -> Tuple[float, Tuple[float, float, float], float, float, Tuple[float, float, float]]:
@@ -51,12 +51,6 @@ def check_shading(alpha, color, ambient, diffuse, light) -> Tuple[float, Tuple[f
     return alpha, color, ambient, diffuse, tuple(c / length for c in scaled)
 
 
-def _need_gpu(what: str) -> torch.device:
-    if not torch.cuda.is_available():
-        raise _lib_view.VghError(f"{what} needs a GPU: the HIP kernels of libvghview.so are the only implementation")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def vertex_normals(vertices, triangles):
     """``Sim3DR.get_normal``: NumPy [V, 3] + [T, 3] -> float32 [V, 3]; a GPU tensor [n, V, 3] (n meshes, one topology) -> a GPU tensor [n, V, 3]
     without a visit to the host."""
@@ -67,14 +61,10 @@ def vertex_normals(vertices, triangles):
     V = shape[-2]
     tri = _triangles(triangles, V, "get_normal")
     lib = _lib_view.load()
-    if on_device:
-        if not vertices.is_cuda:
-            raise ValueError("a torch tensor of vertices must live on the GPU (pass NumPy for host data)")
-        v = vertices.detach().to(torch.float32).contiguous()
-        dev = v.device
-    else:
-        dev = _need_gpu("get_normal")
-        v = torch.from_numpy(np.ascontiguousarray(vertices, dtype=np.float32)).to(dev).unsqueeze(0)
+    dev = device_of(vertices, what="get_normal", lib="libvghview.so")
+    v = to_device(vertices, dev, torch.float32)
+    if not on_device:
+        v = v.unsqueeze(0)
     out = torch.empty_like(v)
     with torch.cuda.device(dev):
         _lib_view.check(lib.vghv_vertex_normals(v.data_ptr(), v.shape[0], V, tri.ctypes.data, tri.shape[0], out.data_ptr(), torch.cuda.current_stream().cuda_stream))
@@ -118,12 +108,9 @@ def render_mesh(image, heads, faces, alpha=0.7, color=(0.75, 0.75, 0.8), ambient
     """A NEW uint8 [H, W, 3] image: every head's mesh, lit and blended with ``alpha``, over a copy of ``image`` (NumPy, or a GPU uint8 tensor whose rows may
     be pitched; never modified), in the order of ``heads``.  ``to_host=False`` returns a GPU tensor.  Arguments are validated before a GPU is looked for."""
     alpha, color, ambient, diffuse, light = check_shading(alpha, color, ambient, diffuse, light)
-    if faces is None:
-        raise ValueError("no triangle list available (FLAME model without faces)")
+    require_faces(faces)
     n = len(heads)
-    verts = np.stack([np.asarray(h.vertices_3d, dtype=np.float32) for h in heads]) if n else np.zeros((0, 1, 3), dtype=np.float32)
-    if verts.ndim != 3 or verts.shape[2] != 3:
-        raise ValueError(f"heads must carry vertices_3d [V, 3], got {verts.shape[1:]}")
+    verts = head_vertices(heads) if n else np.zeros((0, 1, 3), dtype=np.float32)
     tri = _triangles(faces, verts.shape[1], "render_mesh") if n else np.zeros((0, 3), dtype=np.int32)
     src = _device_image(image, "mesh renders")  # ValueError for a bad image, then VghError for a missing GPU
     f32 = lambda q: float(np.float32(q))  # noqa: E731

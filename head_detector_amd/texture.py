@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib_tex
-from .mesh_geometry import check_triangles, pixel_bounds
+from .mesh_geometry import check_raster_arguments, check_triangles, device_of, head_vertices, pixel_bounds, require_faces, shape_of, to_device
 
 
 class HeadTextures:
@@ -47,25 +47,7 @@ class HeadTextures:
 
 
 def _device_of(*candidates):
-    """The device of the first GPU tensor among the arguments; host data alone needs a GPU to be present."""
-    for c in candidates:
-        if isinstance(c, torch.Tensor):
-            if not c.is_cuda:
-                raise ValueError("a torch tensor must live on the GPU (pass NumPy for host data)")
-            return c.device
-    if not torch.cuda.is_available():
-        raise _lib_tex.VghError("render_texture needs a GPU: the HIP kernels of libvghtex.so are the only implementation")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _to_device(a, dev, dtype):
-    """A contiguous tensor of ``dtype`` on ``dev``; the caller's array or tensor is never written."""
-    if isinstance(a, torch.Tensor):
-        if not a.is_cuda:
-            raise ValueError("a torch tensor must live on the GPU (pass NumPy for host data)")
-        return a.detach().to(device=dev, dtype=dtype).contiguous()
-    np_dtype = {torch.float32: np.float32, torch.uint8: np.uint8}[dtype]
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np_dtype)).to(dev)
+    return device_of(*candidates, what="render_texture", lib="libvghtex.so")
 
 
 def _texture_dtype(texture) -> torch.dtype:
@@ -74,29 +56,12 @@ def _texture_dtype(texture) -> torch.dtype:
     return torch.uint8 if is_u8 else torch.float32
 
 
-def _shape(a):
-    return tuple(a.shape) if isinstance(a, torch.Tensor) else np.shape(a)
-
-
 def check_arguments(v_shape, height, width, mapping, occlusion, z_sign):
     """Validates what needs no GPU -> (n, V, height, width, mapping, mode, z_sign); ``v_shape`` is the vertices' shape."""
     if mapping not in _lib_tex.MAPPINGS:
         raise ValueError(f"mapping must be 'bilinear' or 'nearest', got {mapping!r}")
-    if occlusion not in _lib_tex.MODES:
-        raise ValueError(f"occlusion must be 'order' or 'depth', got {occlusion!r}")
-    z_sign = float(z_sign)
-    if z_sign not in (1.0, -1.0):
-        raise ValueError(f"z_sign must be +1 or -1, got {z_sign}")
-    v_shape = tuple(v_shape)
-    if len(v_shape) not in (2, 3) or v_shape[-1] != 3:
-        raise ValueError(f"vertices must be [V, 3] or [n, V, 3], got {v_shape}")
-    height, width = int(height), int(width)
-    if not (1 <= height <= _lib_tex.MAX_SIDE and 1 <= width <= _lib_tex.MAX_SIDE):
-        raise ValueError(f"height x width must lie in 1 .. {_lib_tex.MAX_SIDE}, got {height} x {width}")
-    n = v_shape[0] if len(v_shape) == 3 else 1
-    if n > _lib_tex.MAX_HEADS:
-        raise ValueError(f"{n} heads exceed {_lib_tex.MAX_HEADS}")
-    return n, v_shape[-2], height, width, _lib_tex.MAPPINGS[mapping], _lib_tex.MODES[occlusion], z_sign
+    n, V, height, width, mode, z_sign = check_raster_arguments(v_shape, height, width, occlusion, z_sign, _lib_tex)
+    return n, V, height, width, _lib_tex.MAPPINGS[mapping], mode, z_sign
 
 
 def _check_texture(t_shape, n, what="texture"):
@@ -141,9 +106,9 @@ def render_texture(vertices, triangles, texture, tex_coords, height, width, *, t
     image's, else the texture's) may be below the texture's.  NumPy or GPU tensors; float64 and int64 inputs are converted, nothing is modified.
     ``with_buffers`` returns (image, depth float32 [H, W], triangle int32 [H, W], head int32 [H, W]) instead: what the z-buffer ends with (-1e8 where
     nothing was painted) and the triangle and head every painted pixel shows (-1).  Arguments are validated before a GPU is looked for."""
-    n, V, H, W, mapping_id, mode, z_sign = check_arguments(_shape(vertices), height, width, mapping, occlusion, z_sign)
-    tex_per_head = _check_texture(_shape(texture), n)
-    c_shape = _shape(tex_coords)
+    n, V, H, W, mapping_id, mode, z_sign = check_arguments(shape_of(vertices), height, width, mapping, occlusion, z_sign)
+    tex_per_head = _check_texture(shape_of(texture), n)
+    c_shape = shape_of(tex_coords)
     if len(c_shape) not in (2, 3) or c_shape[-1] != 3:
         raise ValueError(f"tex_coords must be [Vt, 3] or [n, Vt, 3], got {c_shape}")
     if len(c_shape) == 3 and c_shape[0] != n:
@@ -153,9 +118,9 @@ def render_texture(vertices, triangles, texture, tex_coords, height, width, *, t
     tex_tri = tri if tex_triangles is None else check_triangles(tex_triangles, Vt, "render_texture: tex_triangles")
     if tex_tri.shape != tri.shape:
         raise ValueError(f"tex_triangles must have the shape of triangles {tri.shape}, got {tex_tri.shape}")
-    tc = _shape(texture)[-1]
+    tc = shape_of(texture)[-1]
     if image is not None:
-        i_shape = _shape(image)
+        i_shape = shape_of(image)
         if len(i_shape) != 3 or i_shape[:2] != (H, W):
             raise ValueError(f"image must be [{H}, {W}, c], got {i_shape}")
         if channels is not None and int(channels) != i_shape[2]:
@@ -165,11 +130,11 @@ def render_texture(vertices, triangles, texture, tex_coords, height, width, *, t
     if not 1 <= c <= min(tc, _lib_tex.MAX_CHANNELS):
         raise ValueError(f"channels must lie in 1 .. {min(tc, _lib_tex.MAX_CHANNELS)} (the texture has {tc}), got {c}")
     dev = _device_of(vertices, texture, tex_coords, image)
-    v = _to_device(vertices, dev, torch.float32).reshape(n, V, 3)
-    coords = _to_device(tex_coords, dev, torch.float32).reshape(-1, Vt, 3)
-    tex = _to_device(texture, dev, _texture_dtype(texture))
+    v = to_device(vertices, dev, torch.float32).reshape(n, V, 3)
+    coords = to_device(tex_coords, dev, torch.float32).reshape(-1, Vt, 3)
+    tex = to_device(texture, dev, _texture_dtype(texture))
     tex = tex.reshape((-1,) + tuple(tex.shape[-3:]))
-    dst = torch.zeros((H, W, c), dtype=torch.float32, device=dev) if image is None else _to_device(image, dev, torch.float32).clone()
+    dst = torch.zeros((H, W, c), dtype=torch.float32, device=dev) if image is None else to_device(image, dev, torch.float32).clone()
     depth = torch.empty((H, W), dtype=torch.float32, device=dev)
     tri_buf = torch.empty((H, W), dtype=torch.int32, device=dev) if with_buffers else None
     head_buf = torch.empty((H, W), dtype=torch.int32, device=dev) if with_buffers else None
@@ -204,8 +169,8 @@ def unwrap_heads(image, vertices, triangles, uv, size=256, *, mapping: str = "bi
     is, never expanded to floats).  ``vertices`` [V, 3] or [n, V, 3] in image coordinates, ``uv`` [V, 2] in [0, 1] per vertex, ``size`` the atlas side or
     (th, tw).  A texel shows the FIRST triangle of the list that holds it (all atlas depths are 0 and ties keep the earlier triangle)."""
     th, tw = _atlas_size(size)
-    n, V, th, tw, mapping_id, mode, z_sign = check_arguments(_shape(vertices), th, tw, mapping, "order", 1.0)
-    i_shape = _shape(image)
+    n, V, th, tw, mapping_id, mode, z_sign = check_arguments(shape_of(vertices), th, tw, mapping, "order", 1.0)
+    i_shape = shape_of(image)
     if len(i_shape) != 3:
         raise ValueError(f"image must be [H, W, C], got {i_shape}")
     _check_texture(i_shape, n, "image")
@@ -215,8 +180,8 @@ def unwrap_heads(image, vertices, triangles, uv, size=256, *, mapping: str = "bi
     tri = check_triangles(triangles, V, "unwrap_heads")
     atlas = atlas_vertices(uv, V, th, tw)
     dev = _device_of(vertices, image)
-    coords = _to_device(vertices, dev, torch.float32).reshape(n, V, 3)
-    tex = _to_device(image, dev, _texture_dtype(image)).reshape(1, i_shape[0], i_shape[1], C)
+    coords = to_device(vertices, dev, torch.float32).reshape(n, V, 3)
+    tex = to_device(image, dev, _texture_dtype(image)).reshape(1, i_shape[0], i_shape[1], C)
     v = torch.from_numpy(atlas).to(dev).unsqueeze(0).expand(n, V, 3).contiguous()
     dst = torch.zeros((n, th, tw, C), dtype=torch.float32, device=dev)
     depth = torch.empty((n, th, tw), dtype=torch.float32, device=dev)
@@ -248,19 +213,6 @@ def cylindrical_uv(template_vertices, triangles):
 
 
 # ---- what PredictionResult.get_textures and PredictionResult.render_texture do -------------------------------------------------------------------
-def _head_vertices(heads) -> np.ndarray:
-    verts = np.stack([np.asarray(h.vertices_3d, dtype=np.float32) for h in heads])
-    if verts.ndim != 3 or verts.shape[2] != 3:
-        raise ValueError(f"heads must carry vertices_3d [V, 3], got {verts.shape[1:]}")
-    return verts
-
-
-def _faces(faces):
-    if faces is None:
-        raise ValueError("no triangle list available (FLAME model without faces)")
-    return np.asarray(faces)
-
-
 def head_textures(image, heads, faces, uv, size=256, mapping: str = "bilinear", visible_only: bool = True, occlusion: str = "order", to_host: bool = True) -> HeadTextures:
     """``unwrap_heads`` over every head's ``vertices_3d``.  ``mask`` = ``written``; with ``visible_only`` the texel's triangle must also own at least one pixel of
     that head in ``visibility.head_visibility(heads, faces, occlusion)`` (depth = -z, like get_pncc and render_mesh)."""
@@ -268,9 +220,9 @@ def head_textures(image, heads, faces, uv, size=256, mapping: str = "bilinear", 
         raise ValueError(f"mapping must be 'bilinear' or 'nearest', got {mapping!r}")
     if occlusion not in _lib_tex.MODES:
         raise ValueError(f"occlusion must be 'order' or 'depth', got {occlusion!r}")
-    faces = _faces(faces)
+    faces = np.asarray(require_faces(faces))
     th, tw = _atlas_size(size)
-    i_shape = _shape(image)
+    i_shape = shape_of(image)
     if len(i_shape) != 3:
         raise ValueError(f"the image must be [H, W, C], got {i_shape}")
     n = len(heads)
@@ -279,7 +231,7 @@ def head_textures(image, heads, faces, uv, size=256, mapping: str = "bilinear", 
         tex = HeadTextures(torch.zeros((0, th, tw, i_shape[2]), dtype=torch.float32, device=dev), torch.zeros((0, th, tw), dtype=torch.int32, device=dev),
                            torch.zeros((0, th, tw), dtype=torch.bool, device=dev))
     else:
-        tex = unwrap_heads(image, _head_vertices(heads), faces, uv, (th, tw), mapping=mapping, to_host=False)
+        tex = unwrap_heads(image, head_vertices(heads), faces, uv, (th, tw), mapping=mapping, to_host=False)
         if visible_only:
             from .visibility import head_visibility
 
@@ -302,10 +254,10 @@ def paint_heads(image, heads, faces, textures, uv, mapping: str = "bilinear", oc
         raise ValueError(f"mapping must be 'bilinear' or 'nearest', got {mapping!r}")
     if occlusion not in _lib_tex.MODES:
         raise ValueError(f"occlusion must be 'order' or 'depth', got {occlusion!r}")
-    faces = _faces(faces)
+    faces = np.asarray(require_faces(faces))
     if isinstance(textures, HeadTextures):
         textures = textures.texture
-    i_shape, t_shape = _shape(image), _shape(textures)
+    i_shape, t_shape = shape_of(image), shape_of(textures)
     if len(i_shape) != 3 or i_shape[2] != 3:
         raise ValueError(f"the image must be [H, W, 3], got {i_shape}")
     n = len(heads)
@@ -313,9 +265,9 @@ def paint_heads(image, heads, faces, textures, uv, mapping: str = "bilinear", oc
     if t_shape[-1] < 3:
         raise ValueError(f"textures need at least 3 channels, got {t_shape[-1]}")
     dev = _device_of(image, textures)
-    base = _to_device(image, dev, torch.float32)  # a new tensor: uint8 -> float32 is exact
+    base = to_device(image, dev, torch.float32)  # a new tensor: uint8 -> float32 is exact
     if n:
-        verts = _head_vertices(heads)
+        verts = head_vertices(heads)
         atlas = atlas_vertices(uv, verts.shape[1], t_shape[-3], t_shape[-2])
         base = render_texture(verts, faces, textures, atlas, i_shape[0], i_shape[1], image=base, mapping=mapping, occlusion=occlusion, z_sign=-1.0, to_host=False)
     elif isinstance(image, torch.Tensor) and image.dtype == torch.float32:

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib_vis
-from .mesh_geometry import check_triangles, pixel_bounds
+from .mesh_geometry import check_raster_arguments, check_triangles, device_of, head_vertices, pixel_bounds, require_faces, shape_of, to_device
 
 
 class HeadVisibility:
@@ -61,40 +61,16 @@ class HeadVisibility:
 
 def check_arguments(shape, height, width, occlusion, z_sign):
     """Validates what needs no GPU -> (n, V, height, width, mode, z_sign); ``shape`` is the vertices' shape."""
-    if occlusion not in _lib_vis.MODES:
-        raise ValueError(f"occlusion must be 'order' or 'depth', got {occlusion!r}")
-    z_sign = float(z_sign)
-    if z_sign not in (1.0, -1.0):
-        raise ValueError(f"z_sign must be +1 or -1, got {z_sign}")
-    shape = tuple(shape)
-    if len(shape) not in (2, 3) or shape[-1] != 3:
-        raise ValueError(f"vertices must be [V, 3] or [n, V, 3], got {shape}")
-    height, width = int(height), int(width)
-    if not (1 <= height <= _lib_vis.MAX_SIDE and 1 <= width <= _lib_vis.MAX_SIDE):
-        raise ValueError(f"height x width must lie in 1 .. {_lib_vis.MAX_SIDE}, got {height} x {width}")
-    n = shape[0] if len(shape) == 3 else 1
-    if n > _lib_vis.MAX_HEADS:
-        raise ValueError(f"{n} heads exceed {_lib_vis.MAX_HEADS}")
-    return n, shape[-2], height, width, _lib_vis.MODES[occlusion], z_sign
+    return check_raster_arguments(shape, height, width, occlusion, z_sign, _lib_vis)
 
 
 def rasterize_heads(vertices, triangles, height, width, *, occlusion: str = "order", z_sign: float = 1.0, barycentric: bool = True, to_host: bool = True) -> HeadVisibility:
     """``vertices``: NumPy or a GPU tensor, [V, 3] (one head) or [n, V, 3]; other dtypes are converted, nothing is modified.  ``triangles`` [T, 3], shared by all
     heads.  Arguments are validated before a GPU is looked for."""
-    on_device = isinstance(vertices, torch.Tensor)
-    n, V, H, W, mode, z_sign = check_arguments(vertices.shape if on_device else np.shape(vertices), height, width, occlusion, z_sign)
+    n, V, H, W, mode, z_sign = check_arguments(shape_of(vertices), height, width, occlusion, z_sign)
     tri = check_triangles(triangles, V, "rasterize_heads")
-    if on_device:
-        if not vertices.is_cuda:
-            raise ValueError("a torch tensor of vertices must live on the GPU (pass NumPy for host data)")
-        dev = vertices.device
-        v = vertices.detach().to(torch.float32)
-    else:
-        if not torch.cuda.is_available():
-            raise _lib_vis.VghError("rasterize_heads needs a GPU: the HIP kernels of libvghvis.so are the only implementation")
-        dev = torch.device("cuda", torch.cuda.current_device())
-        v = torch.from_numpy(np.ascontiguousarray(vertices, dtype=np.float32)).to(dev)
-    v = v.reshape(n, V, 3).contiguous()
+    dev = device_of(vertices, what="rasterize_heads", lib="libvghvis.so")
+    v = to_device(vertices, dev, torch.float32).reshape(n, V, 3)
     lib = _lib_vis.load()
     depth = torch.empty((H, W), dtype=torch.float32, device=dev)
     tri_buf = torch.empty((H, W), dtype=torch.int32, device=dev)
@@ -126,14 +102,10 @@ def head_visibility(heads, faces, height, width, occlusion: str = "order", baryc
     ``z_sign = -1`` (the negation get_pncc and render_mesh apply; no head's array is touched)."""
     if occlusion not in _lib_vis.MODES:
         raise ValueError(f"occlusion must be 'order' or 'depth', got {occlusion!r}")
-    if faces is None:
-        raise ValueError("no triangle list available (FLAME model without faces)")
+    require_faces(faces)
     n = len(heads)
     if n:
-        verts = np.stack([np.asarray(h.vertices_3d, dtype=np.float32) for h in heads])
-        if verts.ndim != 3 or verts.shape[2] != 3:
-            raise ValueError(f"heads must carry vertices_3d [V, 3], got {verts.shape[1:]}")
-        tri = faces
+        verts, tri = head_vertices(heads), faces
     else:  # all-background buffers, empty per-head arrays
         verts, tri = np.zeros((0, 1, 3), dtype=np.float32), np.zeros((0, 3), dtype=np.int32)
     return rasterize_heads(verts, tri, height, width, occlusion=occlusion, z_sign=-1.0, barycentric=barycentric, to_host=to_host)

@@ -122,6 +122,39 @@ def test_vertically_align_device_results_and_no_heads(gpu_lib):
         PredictionResult(img, heads).get_aligned_heads()
 
 
+def test_consecutive_calls_of_different_sizes_on_one_stream(gpu_lib):
+    """Three calls queued on one non-default stream with nothing waited for in between: one head with a small crop, three heads (the staging block regrows
+    while the first call's work may still be queued: the library waits for its event before it frees it), the first call again (in the grown block).
+    A device image in, device crops out, one synchronisation at the end; every crop is the restatement's for its own inputs."""
+    rng = np.random.default_rng(29)
+    H, W = 200, 260
+    img = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
+    hidx = np.arange(0, 300, 3)
+
+    def head(cx, cy, r, roll):
+        ang, rad = rng.uniform(0, 2 * np.pi, 300), np.sqrt(rng.uniform(0, 1, 300))
+        v = np.stack([cx + r * rad * np.cos(ang), cy + r * rad * np.sin(ang), rng.normal(0, 5, 300)], axis=1).astype(np.float32)
+        s = 640 / max(H, W)
+        t = torch.tensor([[cx * s + (640 - int(W * s)), cy * s + (640 - int(H * s)), 0.0]], dtype=torch.float32)
+        return types.SimpleNamespace(vertices_3d=v, flame_params=types.SimpleNamespace(translation=t), head_pose=RPY(roll=roll, pitch=0.0, yaw=10.0))
+
+    one = [head(60.0, 50.0, 9.0, 25.0)]
+    three = [head(130.0, 100.0, 70.0, -40.0), head(200.0, 60.0, 45.0, 0.0), head(100.0, 110.0, 40.0, 90.0)]
+    calls = [one, three, one]
+    want = [_restated(img, aligned.aligned_head_plan(img.shape, heads, hidx)) for heads in calls]
+    assert all(c.size > 0 and c.any() for w in want for c in w) and sum(c.size for c in want[1]) > 20 * sum(c.size for c in want[0])
+    src = torch.from_numpy(img).to(_dev())
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        got = [PredictionResult(src, heads, head_indices=hidx).get_aligned_heads(to_host=False) for heads in calls]
+    stream.synchronize()
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert all(isinstance(c, torch.Tensor) and c.is_cuda for c in g)
+        _assert_same([c.cpu().numpy() for c in g], w, "ABC"[k])
+    _assert_same([c.cpu().numpy() for c in got[0]], [c.cpu().numpy() for c in got[2]], "A == C")
+
+
 def test_aligned_heads_through_the_facade(gpu_lib, flame_model):
     """HeadDetector(..., mesh_assets=...).detect_batch on two images of different sizes: one crop per head, equal to the restatement driven by the
     same heads.  With synthetic weights the meshes are meaningless and crops may be empty or clipped: the assertion is equality, not plausibility."""

@@ -167,6 +167,30 @@ def test_device_results_sizes_and_no_stale_keys(gpu_lib):
         _same(PredictionResult(tiny, hs, **assets).draw(), expected(tiny, hs, "full", **assets), shape)
 
 
+def test_consecutive_calls_of_different_sizes_on_one_stream(gpu_lib):
+    """Three draws queued on one non-default stream with nothing waited for in between: small (staging and key plane of a few bytes), larger (both regrow
+    while the first call's work may still be queued: the library waits for its event before it frees them), the small one again (in the grown blocks).
+    Device images in, device images out, one synchronisation at the end; every result is the restatement's for its own inputs."""
+    rng = np.random.default_rng(41)
+    tri, head_idx, face_idx = _topology(rng)
+    assets = dict(triangles=tri, head_indices=head_idx, face_indices=face_idx)
+    small, large = rng.integers(0, 256, (16, 16, 3), dtype=np.uint8), rng.integers(0, 256, (48, 64, 3), dtype=np.uint8)
+    one, three = _grid_heads(rng, 1, 16, 16, 4.0, 12.0), _grid_heads(rng, 3, 48, 64, 10.0, 60.0)
+    calls = [(small, one, "bbox"), (large, three, "full"), (small, one, "bbox")]
+    want = [expected(img, heads, m, **assets) for img, heads, m in calls]
+    assert all((w != img).any() for w, (img, _, _) in zip(want, calls))  # every call paints something
+    on_dev = [torch.from_numpy(img).to(_dev()) for img, _, _ in calls]
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        got = [PredictionResult(src, heads, **assets).draw(m, to_host=False) for src, (_, heads, m) in zip(on_dev, calls)]
+    stream.synchronize()
+    for k, (g, w) in enumerate(zip(got, want)):
+        assert isinstance(g, torch.Tensor) and g.is_cuda
+        _same(g.cpu().numpy(), w, "ABC"[k])
+    assert np.array_equal(got[0].cpu().numpy(), got[2].cpu().numpy())
+
+
 def test_draw_through_the_facade(gpu_lib, flame_model):
     """HeadDetector(..., mesh_assets=MeshAssets(..., triangles=, face_indices=)).detect_batch on two images of different sizes: every result's draw(m)
     equals the restatement driven by the same heads.  With synthetic weights the meshes are meaningless (they may lie mostly outside the image):

@@ -1,8 +1,11 @@
-// Stand-alone check of the host half of csrc/tile_fold.h: TileLists (shared and per-head), first_bad_bound and first_bad_index against brute force.
-// tests/test_tile_fold_host.py builds it with the host sanitizers (address, undefined) and runs it on its own.  It makes no HIP call.
+// Stand-alone check of the host half of csrc/tile_fold.h: TileLists (shared and per-head), first_bad_bound and first_bad_index against brute force; and of
+// what csrc/companion_host.h does without the runtime: align16, the require macro and the message, the queue macro (reserve and finish call the runtime:
+// tests/test_gpu_*.py).  tests/test_tile_fold_host.py builds it with the host sanitizers (address, undefined) and runs it on its own.  It makes no HIP call.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
+#include <string>
 #include <vector>
 
 #include "../head_detector_amd/csrc/tile_fold.h"
@@ -77,7 +80,47 @@ static void check_lists(const char* what, const std::vector<int32_t>& bounds, in
     EXPECT(sane && got == want, "%s %d x %d per_head %d: lists differ from brute force", what, W, H, (int)per_head);
 }
 
+// ---- csrc/companion_host.h ----------------------------------------------------------------------------------------------------------------------------
+static int needs_small(int v) {
+    CH_REQUIRE(v < 10, "needs_small: %d is not below %d (%s)", v, 10, "text");
+    return OK;
+}
+
+static int evaluated = 0;
+static hipError_t step(hipError_t e) {  // a plain value, no runtime call
+    ++evaluated;
+    return e;
+}
+
+static void check_plumbing() {
+    const size_t in[] = {0, 1, 15, 16, 17, 31, 32, 4097}, out[] = {0, 16, 16, 16, 32, 32, 32, 4112};
+    for (int i = 0; i < 8; ++i) EXPECT(align16(in[i]) == out[i], "align16(%zu) = %zu", in[i], align16(in[i]));
+    EXPECT(align16(SIZE_MAX - 15) == SIZE_MAX - 15, "align16 of the last multiple of 16");
+
+    EXPECT(strcmp(last_error(), "") == 0, "a thread starts with no message");
+    EXPECT(needs_small(9) == OK && strcmp(last_error(), "") == 0, "a check that holds writes nothing");
+    EXPECT(needs_small(12) == ERR_INVALID, "a check that fails returns ERR_INVALID");
+    EXPECT(strcmp(last_error(), "needs_small: 12 is not below 10 (text)") == 0, "message '%s'", last_error());
+    const std::string big(2000, 'x');  // longer than the buffer: truncated, terminated
+    set_error("%s", big.c_str());
+    EXPECT(strlen(last_error()) == 511 && last_error()[0] == 'x', "a long message is cut to %zu", strlen(last_error()));
+
+    Queue q;
+    EXPECT(q.ok() && q.err == hipSuccess && strcmp(q.failed, "") == 0, "a fresh queue");
+    CH_QUEUE(q, step(hipSuccess));
+    EXPECT(q.ok() && evaluated == 1, "a success keeps the queue going");
+    CH_QUEUE(q, step(hipErrorInvalidValue));
+    EXPECT(!q.ok() && q.err == hipErrorInvalidValue && evaluated == 2, "the first failure is kept");
+    EXPECT(strcmp(q.failed, "step(hipErrorInvalidValue)") == 0, "its text: '%s'", q.failed);
+    CH_QUEUE(q, step(hipErrorOutOfMemory));
+    CH_QUEUE(q, step(hipSuccess));
+    EXPECT(evaluated == 2, "nothing is evaluated after the first failure (%d evaluations)", evaluated);
+    EXPECT(q.err == hipErrorInvalidValue && strcmp(q.failed, "step(hipErrorInvalidValue)") == 0, "and it stays the first: '%s'", q.failed);
+    static_assert(OK == 0 && ERR_INVALID == -1 && ERR_HIP == -2 && ERR_NOMEM == -3, "the codes of the public headers");
+}
+
 int main() {
+    check_plumbing();
     const int sizes[4][2] = {{1, 1}, {16, 16}, {17, 33}, {4000, 3000}};
     for (const auto& wh : sizes) {
         const int W = wh[0], H = wh[1];
