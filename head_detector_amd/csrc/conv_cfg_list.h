@@ -2,6 +2,7 @@
 // alone was 80 s of a 90-s build.
 // ONE list for both translation units: conv_patch.hip defines a plain launcher per entry, conv_igemm.hip's table points at it (a tuple missing here fails at link time).
 #pragma once
+#include "per_device.h"
 #include "vgh_internal.h"
 
 #define VGH_PCFG_LIST(X) \
@@ -139,26 +140,3 @@ VGH_TCFG_LIST(VGH_DECL_T)
 #undef VGH_DECL_Q
 #undef VGH_DECL_T
 }  // namespace vghcfg
-
-// Per-device launch state: the >64 KiB dynamic-LDS opt-in and the occupancy query act on the CURRENT device, so they are cached
-// per device id (a second engine on another GPU of the same process needs its own opt-in).  Racing threads compute the same value.
-namespace {
-constexpr int kMaxDevices = 16;
-inline int current_device() {
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDevices) d = 0;
-    return d;
-}
-
-template <typename K>
-inline int patch_blocks_per_cu(K kernel, int threads, int lds, std::atomic<int> (&cache)[kMaxDevices]) {
-    const int dev = current_device();
-    int n = cache[dev].load(std::memory_order_acquire);
-    if (n == 0) {
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)kernel, threads, lds) != hipSuccess || n < 1) n = 1;
-        cache[dev].store(n, std::memory_order_release);
-    }
-    return n;
-}
-}  // namespace

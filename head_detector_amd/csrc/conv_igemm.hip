@@ -32,8 +32,6 @@ struct CfgEntry {
 static std::atomic<int> g_max_blocks_per_xcd{0};
 static std::atomic<int> g_nt_store{0};
 
-static int persistent_blocks_per_xcd(const ConvArgs& a, int chunk, int per_cu) { return vgh_conv_persistent_blocks_per_xcd(a, chunk, per_cu); }
-
 }  // namespace
 // persistent workgroups per XCD of a tile-loop kernel (also used by conv_split.hip): resident slots, shared between lanes, capped by the test knob
 int vgh_conv_persistent_blocks_per_xcd(const ConvArgs& a, int chunk, int per_cu) {
@@ -55,9 +53,9 @@ namespace {
 #ifdef VGH_EXPERIMENTS
 template <int TW, int TH, int BC, int NWP, int NWC>
 void launch_patch_s2_cfg(const ConvArgs& a, int ntc, int ntx, int nty, int total, int chunk, int lds, hipStream_t st) {
-    static std::atomic<int> per_cu[kMaxDevices];
+    static PerDevice per_cu;
     const int n = patch_blocks_per_cu(conv3x3_patch_kernel<TW, TH, BC, NWP, NWC, 0, 1>, NWP * NWC * 64, lds, per_cu);
-    const int gpx = persistent_blocks_per_xcd(a, chunk, n);
+    const int gpx = vgh_conv_persistent_blocks_per_xcd(a, chunk, n);
     hipLaunchKernelGGL((conv3x3_patch_kernel<TW, TH, BC, NWP, NWC, 0, 1>), dim3(gpx * 8), dim3(NWP * NWC * 64), lds, st, a, ntc, ntx, nty, total, chunk);
 }
 #endif

@@ -1,15 +1,8 @@
 // Host-side launchers of conv_igemm_kernel (included inside an anonymous namespace by conv_igemm.hip and conv_rings.hip, after conv_kernels.inc and conv_cfg_list.h).
 template <int BP, int BC, int WP, int WC, int KBS, int NST>
 void launch_cfg(const ConvArgs& a, int ntc, int total, int chunk, int lds, hipStream_t st) {
-    static std::atomic<int> attr_done[kMaxDevices];
-    if (lds > 64 * 1024) {
-        const int dev = current_device();
-        if (!attr_done[dev].load(std::memory_order_acquire)) {
-            (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            attr_done[dev].store(1, std::memory_order_release);
-        }
-    }
+    static PerDevice opted_in;
+    if (lds > 64 * 1024) (void)opt_in_dynamic_lds(opted_in, lds, conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST>, conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST>);
     const dim3 grid(chunk * 8), block((BP / WP) * (BC / WC) * 64);
     constexpr int nw = (BP / WP) * (BC / WC);
     constexpr int loop_lds = NST * KBS * (BP + BC) * 64 + (NST > 2 ? nw * 1024 : 0), epi_lds = nw * 32 * (WC + 4) * 4;
@@ -38,15 +31,8 @@ void launch_cfg(const ConvArgs& a, int ntc, int total, int chunk, int lds, hipSt
 // loader-wave tiles (conv_igemm_kernel<..., LF>): LF x the waves, the same LDS
 template <int BP, int BC, int WP, int WC, int KBS, int NST, int LF>
 void launch_cfg_lf(const ConvArgs& a, int ntc, int total, int chunk, int lds, hipStream_t st) {
-    static std::atomic<int> attr_done[kMaxDevices];
-    if (lds > 64 * 1024) {
-        const int dev = current_device();
-        if (!attr_done[dev].load(std::memory_order_acquire)) {
-            (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST, 0, 0, LF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, 0, 0, LF>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            attr_done[dev].store(1, std::memory_order_release);
-        }
-    }
+    static PerDevice opted_in;
+    if (lds > 64 * 1024) (void)opt_in_dynamic_lds(opted_in, lds, conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST, 0, 0, LF>, conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, 0, 0, LF>);
     const dim3 grid(chunk * 8), block((BP / WP) * (BC / WC) * 64 * LF);
     if (a.fast_epi)
         hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, 0, 0, LF>), grid, block, lds, st, a, ntc, total, chunk);

@@ -6,7 +6,7 @@
 namespace {
 template <int TW, int TH, int BC, int NWP, int NWC>
 void launch_patch_cfg(const ConvArgs& a, int ntc, int ntx, int nty, int total, int chunk, int lds, hipStream_t st) {
-    static std::atomic<int> per_cu[kMaxDevices];
+    static PerDevice per_cu;
     const int n = patch_blocks_per_cu(conv3x3_patch_kernel<TW, TH, BC, NWP, NWC>, NWP * NWC * 64, lds, per_cu);
     const int gpx = vgh_conv_persistent_blocks_per_xcd(a, chunk, n);
     hipLaunchKernelGGL((conv3x3_patch_kernel<TW, TH, BC, NWP, NWC>), dim3(gpx * 8), dim3(NWP * NWC * 64), lds, st, a, ntc, ntx, nty, total, chunk);
@@ -14,7 +14,7 @@ void launch_patch_cfg(const ConvArgs& a, int ntc, int ntx, int nty, int total, i
 
 template <int TW, int TH, int BC, int NWP, int NWC>
 void launch_patch3_cfg(const ConvArgs& a, int ntc, int ntx, int nty, int total, int chunk, int lds, hipStream_t st) {
-    static std::atomic<int> per_cu[kMaxDevices];
+    static PerDevice per_cu;
     const int n = patch_blocks_per_cu(conv3x3_patch3_kernel<TW, TH, BC, NWP, NWC>, NWP * NWC * 64, lds, per_cu);
     const int gpx = vgh_conv_persistent_blocks_per_xcd(a, chunk, n);
     hipLaunchKernelGGL((conv3x3_patch3_kernel<TW, TH, BC, NWP, NWC>), dim3(gpx * 8), dim3(NWP * NWC * 64), lds, st, a, ntc, ntx, nty, total, chunk);
@@ -22,7 +22,7 @@ void launch_patch3_cfg(const ConvArgs& a, int ntc, int ntx, int nty, int total, 
 
 template <int BP, int BC, int WP, int WC, int KBS, int NST>
 void launch_stream_cfg(const ConvArgs& a, int ntc, int total, int chunk, int lds, hipStream_t st) {
-    static std::atomic<int> per_cu[kMaxDevices];
+    static PerDevice per_cu;
     constexpr int threads = (BP / WP) * (BC / WC) * 64;
     const int n = patch_blocks_per_cu(conv1x1_stream_kernel<BP, BC, WP, WC, KBS, NST>, threads, lds, per_cu);
     const int gpx = vgh_conv_persistent_blocks_per_xcd(a, chunk, n);

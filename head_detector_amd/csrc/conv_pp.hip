@@ -27,6 +27,7 @@
 #include <atomic>
 #include <type_traits>
 
+#include "per_device.h"
 #include "vgh_internal.h"
 
 #define AS3 __attribute__((address_space(3)))
@@ -966,17 +967,11 @@ __global__ __launch_bounds__(512, 2) void conv3x3_pp_kernel(const ConvArgs a, co
     }
 }
 
-constexpr int kMaxDev = 16;
 template <int TI, int V, int F8 = 0, int O8 = 0, int H16 = 0, int DG = 0, int GEO = 0>
 int launch_pp(const ConvArgs& a, int ntc, int nsx, int nsy, int nsp, int total, int chunk, int max_blocks_per_xcd, hipStream_t st) {
     using G = PPGeo<TI, V, (F8 || O8) ? 1 : 0, GEO>;
-    static std::atomic<int> done[kMaxDev];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
-    if (!done[dev].load(std::memory_order_acquire)) {
-        VGH_HIP(hipFuncSetAttribute((const void*)conv3x3_pp_kernel<TI, V, F8, O8, H16, DG, GEO>, hipFuncAttributeMaxDynamicSharedMemorySize, (G::LDS)));
-        done[dev].store(1, std::memory_order_release);
-    }
+    static PerDevice opted_in;
+    VGH_HIP(opt_in_dynamic_lds(opted_in, G::LDS, conv3x3_pp_kernel<TI, V, F8, O8, H16, DG, GEO>));
     int gpx = 32;  // one workgroup per CU, 32 CUs per XCD
     if (max_blocks_per_xcd > 0 && gpx > max_blocks_per_xcd) gpx = max_blocks_per_xcd;
     if (gpx > chunk) gpx = chunk;

@@ -20,15 +20,9 @@
 #include <vector>
 
 #include "conv_kernels.inc"
+#include "per_device.h"
 
 namespace {
-
-constexpr int kMaxDev = 16;
-int cur_dev() {
-    int d = 0;
-    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= kMaxDev) d = 0;
-    return d;
-}
 
 constexpr int igemm_lds(int BP, int BC, int WP, int WC, int KBS, int NST) {
     const int nw = (BP / WP) * (BC / WC);
@@ -44,15 +38,8 @@ struct SplitCfg {
 
 template <int BP, int BC, int WP, int WC, int KBS, int NST, int SP>
 void launch_igemm_sp(const ConvArgs& a, int ntc, int total, int chunk, int lds, hipStream_t st) {
-    static std::atomic<int> attr_done[kMaxDev];
-    if (lds > 64 * 1024) {
-        const int dev = cur_dev();
-        if (!attr_done[dev].load(std::memory_order_acquire)) {
-            (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            attr_done[dev].store(1, std::memory_order_release);
-        }
-    }
+    static PerDevice opted_in;
+    if (lds > 64 * 1024) (void)opt_in_dynamic_lds(opted_in, lds, conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST, SP>, conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, SP>);
     const dim3 grid(chunk * 8), block((BP / WP) * (BC / WC) * 64);
     if (a.fast_epi)
         hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, SP>), grid, block, lds, st, a, ntc, total, chunk);
@@ -69,14 +56,8 @@ void launch_igemm(const ConvArgs& a, int sp, int ntc, int, int, int total, int c
 
 template <int TW, int TH, int BC, int NWP, int NWC, int SP>
 void launch_patch_sp(const ConvArgs& a, int ntc, int ntx, int nty, int total, int chunk, int lds, hipStream_t st) {
-    static std::atomic<int> per_cu[kMaxDev];
-    const int dev = cur_dev();
-    int n = per_cu[dev].load(std::memory_order_acquire);
-    if (n == 0) {
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)conv3x3_patch_kernel<TW, TH, BC, NWP, NWC, SP>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)conv3x3_patch_kernel<TW, TH, BC, NWP, NWC, SP>, NWP * NWC * 64, lds) != hipSuccess || n < 1) n = 1;
-        per_cu[dev].store(n, std::memory_order_release);
-    }
+    static PerDevice per_cu;
+    const int n = patch_blocks_per_cu(conv3x3_patch_kernel<TW, TH, BC, NWP, NWC, SP>, NWP * NWC * 64, lds, per_cu);
     const int gpx = vgh_conv_persistent_blocks_per_xcd(a, chunk, n);  // as the bf16 patch tiles: lane share + vgh_conv_set_max_blocks_per_xcd (multi-tile tests)
     hipLaunchKernelGGL((conv3x3_patch_kernel<TW, TH, BC, NWP, NWC, SP>), dim3(gpx * 8), dim3(NWP * NWC * 64), lds, st, a, ntc, ntx, nty, total, chunk);
 }

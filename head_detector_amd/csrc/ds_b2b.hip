@@ -23,6 +23,7 @@
 #include <atomic>
 #include <type_traits>
 
+#include "per_device.h"
 #include "vgh_internal.h"
 
 #define AS3 __attribute__((address_space(3)))
@@ -941,26 +942,33 @@ __global__ __launch_bounds__(64 * NCG, 1) void w_conv_kernel(const ConvArgs a, c
     for (int blk = 0; blk < 4; ++blk) epi_block(blk >> 1, blk & 1);  // the last tile's epilogue
 }
 
-constexpr int kMaxDev = 16;
-template <int T2, int STEM = 0>
-int launch_dt(const ConvArgs& a, const StemArgs& sa, hipStream_t st) {
-    constexpr int LDS = STEM ? ST_LDS : DT_LDS;
-    static std::atomic<int> done[kMaxDev];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
-    if (!done[dev].load(std::memory_order_acquire)) {
-        VGH_HIP(hipFuncSetAttribute((const void*)ds_b2b_kernel<T2, STEM>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        done[dev].store(1, std::memory_order_release);
-    }
-    const int nsx = a.Wo / 8, nsy = a.Ho / 8, per = nsx * nsy;
-    const int64_t total = (int64_t)a.B * per;
-    VGH_REQUIRE(total < (1ll << 30), "conv b2b: too many tiles");
-    const int chunk = (int)((total + 7) / 8);
+// The persistent grid of the t / u, r and w tiles: `total` work items (pixel tile x cout part, nh parts, the part running fastest) are dealt to the 8 XCDs in
+// chunks of whole pixel tiles, and an XCD runs gpx workgroups that stride over its chunk.  chunk and gpx are multiples of nh, so item % nh -- the cout part --
+// is fixed per workgroup.
+struct PersistentGrid {
+    int chunk, gpx;
+};
+PersistentGrid persistent_grid(const ConvArgs& a, int64_t total, int nh) {
+    const int chunk = ((int)((total + 7) / 8) + nh - 1) / nh * nh;
     int gpx = DT_FULL_WIDTH ? 32 : 32 / (a.grid_share > 1 ? a.grid_share : 1);  // one workgroup per CU; the executor's lane streams take their share of the CUs each
     if (gpx < 8) gpx = 8;
     const int cap = vgh_conv_max_blocks_per_xcd();
     if (cap > 0 && gpx > cap) gpx = cap;
     if (gpx > chunk) gpx = chunk;
+    gpx = gpx / nh * nh;
+    if (gpx < nh) gpx = nh;
+    return {chunk, gpx};
+}
+
+template <int T2, int STEM = 0>
+int launch_dt(const ConvArgs& a, const StemArgs& sa, hipStream_t st) {
+    constexpr int LDS = STEM ? ST_LDS : DT_LDS;
+    static PerDevice opted_in;
+    VGH_HIP(opt_in_dynamic_lds(opted_in, LDS, ds_b2b_kernel<T2, STEM>));
+    const int nsx = a.Wo / 8, nsy = a.Ho / 8, per = nsx * nsy;
+    const int64_t total = (int64_t)a.B * per;
+    VGH_REQUIRE(total < (1ll << 30), "conv b2b: too many tiles");
+    const auto [chunk, gpx] = persistent_grid(a, total, 1);
     DtDiv dv;
     vgh_fastdiv_magic((unsigned)per, &dv.m_per, &dv.s_per);
     vgh_fastdiv_magic((unsigned)nsx, &dv.m_nsx, &dv.s_nsx);
@@ -989,25 +997,12 @@ int vgh_conv_ds_ok(const ConvArgs& a) {
 
 int vgh_launch_conv_ds(const ConvArgs& a, hipStream_t st) {
     VGH_REQUIRE(vgh_conv_ds_ok(a), "conv: not a 96-channel stride-2 conv on whole 8 x 8 tiles (the r tile)");
-    static std::atomic<int> done[kMaxDev];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
-    if (!done[dev].load(std::memory_order_acquire)) {
-        VGH_HIP(hipFuncSetAttribute((const void*)ds_conv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DR_LDS));
-        done[dev].store(1, std::memory_order_release);
-    }
+    static PerDevice opted_in;
+    VGH_HIP(opt_in_dynamic_lds(opted_in, DR_LDS, ds_conv_kernel));
     const int nsx = a.Wo / 8, nsy = a.Ho / 8, per = nsx * nsy, nh = a.cout_pad / 96;
     const int64_t total = (int64_t)a.B * per * nh;
     VGH_REQUIRE(total < (1ll << 30), "conv: too many tiles");
-    int chunk = (int)((total + 7) / 8);
-    if (nh > 1) chunk += chunk & 1;  // even chunks: item parity = cout half, fixed per workgroup
-    int gpx = DT_FULL_WIDTH ? 32 : 32 / (a.grid_share > 1 ? a.grid_share : 1);
-    if (gpx < 8) gpx = 8;
-    const int cap = vgh_conv_max_blocks_per_xcd();
-    if (cap > 0 && gpx > cap) gpx = cap;
-    if (gpx > chunk) gpx = chunk;
-    if (nh > 1) gpx -= gpx & 1;
-    if (gpx < nh) gpx = nh;
+    const auto [chunk, gpx] = persistent_grid(a, total, nh);  // nh = 1 or 2: even chunks, item parity = cout half
     DtDiv dv;
     vgh_fastdiv_magic((unsigned)per, &dv.m_per, &dv.s_per);
     vgh_fastdiv_magic((unsigned)nsx, &dv.m_nsx, &dv.s_nsx);
@@ -1028,25 +1023,12 @@ int vgh_conv_w_ok(const ConvArgs& a) {
 template <int CIN16, int NCG, int RES>
 static int launch_w(const ConvArgs& a, hipStream_t st) {
     using G = WGeo<CIN16>;
-    static std::atomic<int> done[kMaxDev];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDev) dev = 0;
-    if (!done[dev].load(std::memory_order_acquire)) {
-        VGH_HIP(hipFuncSetAttribute((const void*)w_conv_kernel<CIN16, NCG, RES>, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
-        done[dev].store(1, std::memory_order_release);
-    }
+    static PerDevice opted_in;
+    VGH_HIP(opt_in_dynamic_lds(opted_in, G::LDS, w_conv_kernel<CIN16, NCG, RES>));
     const int nsx = a.Wo / 8, nsy = a.Ho / 8, per = nsx * nsy, nh = a.cout_pad / (32 * NCG);
     const int64_t total = (int64_t)a.B * per * nh;
     VGH_REQUIRE(total < (1ll << 30), "conv: too many tiles");
-    int chunk = (int)((total + 7) / 8);
-    chunk = (chunk + nh - 1) / nh * nh;  // chunks of whole pixel tiles: item % nh = cout part, fixed per workgroup
-    int gpx = DT_FULL_WIDTH ? 32 : 32 / (a.grid_share > 1 ? a.grid_share : 1);
-    if (gpx < 8) gpx = 8;
-    const int cap = vgh_conv_max_blocks_per_xcd();
-    if (cap > 0 && gpx > cap) gpx = cap;
-    if (gpx > chunk) gpx = chunk;
-    gpx = gpx / nh * nh;
-    if (gpx < nh) gpx = nh;
+    const auto [chunk, gpx] = persistent_grid(a, total, nh);
     DtDiv dv;
     vgh_fastdiv_magic((unsigned)per, &dv.m_per, &dv.s_per);
     vgh_fastdiv_magic((unsigned)nsx, &dv.m_nsx, &dv.s_nsx);

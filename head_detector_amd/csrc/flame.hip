@@ -18,7 +18,7 @@
 //  * (r02 - r04) the blend is a [heads x K] . [K x 3V] contraction, and gfx950's fp32 matrix instructions are exact ascending fmaf chains over their k
 //    (tools/micro/mfma_f32_chain.hip): the matrix-core kernels below -- register-fed, LDS-staged 128-head tiles, and from r04 the component-split "c3" tiles
 //    that run 1 ... 2 048 heads (one coordinate plane per wave, coefficient tile in LDS, k-interleaved basis copy, prologue waves inside the block up to 8 heads)
-//    -- produce the VALU kernel's bits, so which one runs is a pure speed choice (run_decode_on; vgh_flame_set_matrix_path for tests and A/B).
+//    -- produce the VALU kernel's bits, so which one runs is a pure speed choice (flame_plan.h; vgh_flame_set_matrix_path for tests and A/B).
 #include <math.h>
 #include <stdlib.h>
 
@@ -27,6 +27,8 @@
 
 #define AS3 __attribute__((address_space(3)))
 
+#include "flame_plan.h"
+#include "per_device.h"
 #include "vgh_internal.h"
 
 typedef __attribute__((ext_vector_type(3))) float f32x3_t;
@@ -71,9 +73,6 @@ static std::atomic<int> g_flame_mode{1};
 #ifdef VGH_EXPERIMENTS
 static unsigned long long* g_prep_trace = nullptr;  // vgh_flame_set_trace
 #endif
-constexpr int kLdsMinHeads = 1024;  // from here on: LDS-staged tiles with 128-head blocks
-constexpr int kC3MaxHeads = 2048;   // ... component-split tiles up to here (r04; automatic mode, direct batches)
-constexpr int kLdsMidHeads = 256;   // ... 64-head blocks (r02: the register-fed kernel ran n = 256 .. 1024 at 0.22 - 0.35 of the fp32 roof)
 
 namespace {
 
@@ -952,13 +951,8 @@ template <int WPS, int LBH>
 int launch_mfma_lds(const VertArgs& va, hipStream_t st) {
     constexpr int LB_KS = lb_ks<LBH>(), LB_B = LB_KS * 3 * LB_V;
     const size_t lds = (size_t)2 * (LB_KS * LBH + LB_B) * sizeof(float) + 1024;  // two slabs + the pair table (<= 256 entries): two blocks per CU (one for LBH = 32)
-    static std::atomic<int> attr_done[16];
-    int dev = 0;
-    VGH_HIP(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 16 && !attr_done[dev].load(std::memory_order_acquire)) {
-        VGH_HIP(hipFuncSetAttribute((const void*)flame_mfma_lds_kernel<WPS, LBH>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done[dev].store(1, std::memory_order_release);
-    }
+    static PerDevice opted_in;
+    VGH_HIP(opt_in_dynamic_lds(opted_in, (int)lds, flame_mfma_lds_kernel<WPS, LBH>));
     hipLaunchKernelGGL((flame_mfma_lds_kernel<WPS, LBH>), dim3((va.n + LBH - 1) / LBH, (va.V + LB_V - 1) / LB_V), dim3((LBH >= 64 ? LBH / 64 : 1) * 256), lds, st, va);
     VGH_HIP(hipGetLastError());
     return VGH_OK;
@@ -1363,13 +1357,8 @@ int launch_c3(const VertArgs& va, const PrepArgs& pa, hipStream_t st) {
     const int tile = (std::max(nrows8 * MT * (NPW > 0 ? 33 : 32), VG > 1 && MT == 1 ? 0 : VG * MT * 3 * 16 * 64) + 3) & ~3;
     constexpr bool XOWN = VG > 1 && MT == 1;  // the exchange buffer has its own memory (+ a counter per vertex group)
     const size_t lds = ((size_t)tile + (size_t)NH * HP_SIZE + (XOWN ? VG * 3 * 16 * 64 + 16 : 0)) * sizeof(float) + (NPW > 0 ? NPW * sizeof(PrepScratch) : 0);
-    static std::atomic<int> attr_done[16];
-    int dev = 0;
-    VGH_HIP(hipGetDevice(&dev));
-    if (dev >= 0 && dev < 16 && !attr_done[dev].load(std::memory_order_acquire)) {
-        VGH_HIP(hipFuncSetAttribute((const void*)flame_c3_kernel<NPW, NHL, VG, MT, Q>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done[dev].store(1, std::memory_order_release);
-    }
+    static PerDevice opted_in;
+    VGH_HIP(opt_in_dynamic_lds(opted_in, 160 * 1024, flame_c3_kernel<NPW, NHL, VG, MT, Q>));
     if (lds > 160 * 1024) {
         vgh_set_error("flame c3 tiles: %zu bytes of LDS for %d coefficient rows", lds, nrows8);
         return VGH_ERR_INVALID;
@@ -1415,57 +1404,6 @@ int run_decode_on(vgh_flame* f, const PrepArgs& pa_in, int n, int shape_live, in
         if (pa.unpad) pa.unpad += (int64_t)done * 3;
         if (pa.rot_out) pa.rot_out += (int64_t)done * 9;
         if (pa.joints_out) pa.joints_out += (int64_t)done * f->NJ * 3;
-        // matrix-core path from a handful of heads on (or the live count is only known on the device) and the
-        // live ranges have even length; tiny direct batches keep the fused VALU kernel (one launch, the whole chip on one head's basis)
-        const bool even = ((shape_live | expr_live | f->NB | f->K) & 1) == 0;
-        // (measured, profiles/r02_flame_sweep.json: the matrix-core kernel wins from a handful of heads up to a few thousand; at crowd scale the
-        //  VALU kernel's 8-heads-per-basis-load reuse is ahead again; with a device-side count the launch is capacity-sized and mostly
-        //  exits at once, so the tile count that matters is the live one)
-        const int mode = g_flame_mode.load(std::memory_order_relaxed);
-        const int amode = (mode == 8 || mode == 9) ? 1 : mode;  // 8 / 9: the automatic choice with the quad tiles forced on / off
-        const int npairs = ((detector_mode ? shape_live + expr_live : f->NB) + f->NP + 1) / 2;
-        // crowd scale: operands staged through LDS (its k-pair table holds 256 entries: FLAME has 218; a model with more coefficients keeps the other kernels)
-        // r04: 32-head blocks of the LDS-staged kernel (mode 5 only).  Hypothesis: the register-fed kernel keeps at most 63 dword loads (8 KB) in flight per wave
-        // and runs 77 ns per k at n = 96, so 1-KiB LDS-DMA pieces should free it.  Measured (profiles/r04_flame_sweep.json): n = 96 / 192 with all 400
-        // coefficients 63.0 / 64.5 us against 59.4 / 60.2 for the register-fed kernel -- the mid range is bound by its ~30 us of K-independent work (prologue
-        // kernel, two launches, head-pack staging, per-head skinning epilogue), not by loads in flight.  Kept selectable (bit-identical), not automatic.
-        const bool lds32 = even && npairs <= 248 && mode == 5;
-        const bool lds = lds32 || (even && npairs <= 248 && (mode == 3 || mode == 4 || (amode == 1 && !pa.n_dev && m >= kLdsMidHeads)));
-        const bool mfma = lds || (even && (mode == 2 || (amode == 1 && (pa.n_dev ? m <= 16384 : (m >= 5 && m < 2048)))));
-        // c3 tiles (component-split waves, coefficient tile in LDS; K - NB pose features in one k-group run, NB a multiple of 8 so that the pose rows start a
-        // group): mode 6 always with the prologue kernel, mode 7 the same with the fused variant (prologue waves inside the block) up to 8 heads.  Automatic
-        // (measured, profiles/r04_flame_sweep.json; us per call, all 400 / L-live / M-live coefficients; old = the kernels above):
-        //   n = 1: 22.4 / 18.2 / 16.5 (old 33.4 / 19.2 / 16.2)    n = 8: 27.0 / 21.3 / 18.4 (52.7 / 36.6 / 30.9)    n = 32: 27.7 / 23.0 / 20.2 (58.0 / 42.0 / 36.4)
-        //   n = 96: 39.1 / 30.4 / 25.4 (59.0 / 43.3 / 37.3)       n = 128: 49.9 / 35.9 / 28.3 (59.8 / 43.8 / 37.9)  n = 192: 51.3 / 37.2 / 30.0 (60.5 / 44.9 / 38.9)
-        //   n = 256: 82.7 / 56.9 / 44.1 (100.4 / 71.9 / 58.9)     n = 512: 122.4 / 83.4 / 63.8 (146.4 / 101.5 / 80.2)  n = 1024: 193.3 / 127.8 / 95.0 (249.7 / 163.3 / 123.4)
-        //   n = 2048: 364 / 237 / 173 (387 / 245 / 180)   n = 3072: 536 / 348 / 253 (469 / 298 / 218: the 128-head LDS-staged blocks take over)   n = 8192: 1 400 / 900 / 653 (1 192 / 766 / 569)
-        // -> direct batches up to kC3MaxHeads; with a device-side count the launch is capacity-sized and the dead tile rows exit at once: any capacity the
-        //    register-fed kernel took (the live count of a detector batch is a few hundred at most: 4-wave blocks up to a capacity of 128, 128-vertex blocks beyond).
-        const bool c3_ok = even && f->K - f->NB <= 64 && (f->NB & 7) == 0 && f->basis8;
-        const bool c3_auto = amode == 1 && (pa.n_dev ? m <= 16384 : m <= kC3MaxHeads) && !(m <= 2 && npairs < 100);  // (1 - 2 heads of the M set: the VALU kernel)
-        const bool c3 = c3_ok && (mode == 6 || mode == 7 || c3_auto);
-        const bool c3_fused = c3 && mode != 6 && !pa.n_dev && m <= 8 && (verts || proj);
-        const bool fused = c3_fused || (!c3 && !mfma && !pa.n_dev && m <= 256);  // the vertex kernel computes its own heads' prologue
-        if (!fused || (!verts && !proj)) {
-            constexpr int HB = 16;
-            if (m >= (c3 ? 4096 : 512)) {  // (the c3 tiles fetch the rows by LDS-DMA either way: the one-wave-per-block prologue is ~5 us shorter below a few thousand heads)
-                            // coalesced coefficient rows (measured: 16 waves per block cost 17 us vs 9.5 us at n = 96, but 92 vs 112 us at n = 8192); the
-                            // padded heads of the last block stay inside the scratch (npad is a multiple of 128)
-                const size_t lds = (size_t)HB * sizeof(PrepScratch) + (size_t)HB * HP_SIZE * 4 + (size_t)f->Kp * HB * 4;
-                static std::atomic<int> attr_done[16];
-                int dev = 0;
-                VGH_HIP(hipGetDevice(&dev));
-                if (dev >= 0 && dev < 16 && !attr_done[dev].load(std::memory_order_acquire)) {
-                    VGH_HIP(hipFuncSetAttribute((const void*)flame_prep_multi_kernel<HB>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-                    attr_done[dev].store(1, std::memory_order_release);
-                }
-                hipLaunchKernelGGL(flame_prep_multi_kernel<HB>, dim3((m + HB - 1) / HB), dim3(HB * 64), lds, st, pa);
-            } else {
-                hipLaunchKernelGGL(flame_prep_kernel, dim3(m), dim3(64), 0, st, pa);
-            }
-            VGH_HIP(hipGetLastError());
-        }
-        if (!verts && !proj) continue;
         VertArgs va;
         va.basis = f->basis;
         va.basis8 = f->basis8;
@@ -1501,60 +1439,29 @@ int run_decode_on(vgh_flame* f, const PrepArgs& pa_in, int n, int shape_live, in
 #ifdef VGH_EXPERIMENTS
         if (getenv("VGH_FLAME_ABLATE")) va.ablate = atoi(getenv("VGH_FLAME_ABLATE"));
 #endif
-        int rc;
-        // quad tiles (16 x 16 x 4 MFMAs, r06): measured and NOT adopted -- bit-identical, but no faster at one head (14.8 vs 15.0 us, M set; 19.4 vs 19.7 with all 400
-        // coefficients) and 30 - 60 % slower from two heads on (profiles/r06_flame_quad_tiles.txt): a small decode is not its dependent MFMA chain long, it is the
-        // basis stream per wave.  Kept in the -DVGH_EXPERIMENTS build (mode 8 forces them up to 128 heads; mode 9 = mode 1 = without them).
-#ifdef VGH_EXPERIMENTS
-        const bool quad = c3 && mode == 8 && m <= 128;
-#else
-        const bool quad = false;
-#endif
-        if (false) {
-#ifdef VGH_EXPERIMENTS
-        } else if (c3_fused && quad) {
-            rc = m <= 1 ? launch_c3<1, 0, 1, 1, 1>(va, pa, st) : m <= 2 ? launch_c3<2, 0, 1, 1, 1>(va, pa, st) : m <= 4 ? launch_c3<4, 0, 1, 1, 1>(va, pa, st) : launch_c3<8, 0, 1, 1, 1>(va, pa, st);
-        } else if (c3 && quad && !c3_fused) {
-            rc = m <= 32 ? launch_c3<0, 5, 1, 1, 1>(va, pa, st) : launch_c3<0, 1, 1, 1, 1>(va, pa, st);
-#endif
-        } else if (c3_fused) {
-            rc = m <= 1 ? launch_c3<1, 0>(va, pa, st) : m <= 2 ? launch_c3<2, 0>(va, pa, st) : m <= 4 ? launch_c3<4, 0>(va, pa, st) : launch_c3<8, 0>(va, pa, st);
-        } else if (c3) {
-            // one head tile: 3 + 5 waves; up to 96 heads: 3 + 1 (two blocks per CU; n = 112: 51.1 vs 50.1 us for the 128-vertex blocks); beyond: 128-vertex blocks of 12 compute waves (64-vertex blocks of 6 measured
-            // slower than both everywhere)
-            if (pa.n_dev) rc = m <= 128 ? launch_c3<0, 1>(va, pa, st) : launch_c3<0, 0, 4>(va, pa, st);  // (capacity, not the live count)
-            else if (m <= 96) rc = m <= 32 ? launch_c3<0, 5>(va, pa, st) : launch_c3<0, 1>(va, pa, st);
-            else {
-                // one block per CU: 128 vertices x 32 heads (12 compute waves), 160 x 32 (15 waves) or 128 x 64 (12 waves, two head tiles' chains per wave on one
-                // basis operand) -- whichever needs the least time in ROUNDS of blocks over the CUs, a round costing 1.0 / 1.3 / 1.72 of the first's (measured,
-                // all 400 coefficients: n = 256 59.7 vs 82.9 us for 160- vs 128-vertex blocks, 384 100.8 vs 86.0, 512 103.2 vs 118.3 (64-head blocks 134.2),
-                // 1 024 189.4 vs 190.2 (196.8), 2 048 361.9 vs 364.3 (323.5))
-                const int vgroups = (f->V + 31) / 32, hg = (m + 31) / 32, ncu = f->ncu > 0 ? f->ncu : 256;
-                const int r4 = (hg * ((vgroups + 3) / 4) + ncu - 1) / ncu, r5 = (hg * ((vgroups + 4) / 5) + ncu - 1) / ncu, r2 = ((hg + 1) / 2 * ((vgroups + 3) / 4) + ncu - 1) / ncu;
-                const int c4 = 100 * r4, c5 = 130 * r5, c2 = 172 * r2;
-                rc = c2 < c4 && c2 < c5 ? launch_c3<0, 0, 4, 2>(va, pa, st) : c5 < c4 ? launch_c3<0, 0, 5>(va, pa, st) : launch_c3<0, 0, 4>(va, pa, st);
-            }
-        } else if (lds) {
-            // 128-head blocks at crowd scale; 64-head blocks (twice the blocks) below it and in mode 4
-            rc = lds32 ? launch_mfma_lds<1, 32>(va, st) : (mode == 4 || (mode == 1 && m < kLdsMinHeads)) ? launch_mfma_lds<2, 64>(va, st) : launch_mfma_lds<4, 128>(va, st);
-        } else if (mfma) {
-            if (pa.n_dev || m <= 512)
-                rc = launch_mfma<1>(va, st);  // one 32-head tile per wave: twice the waves, two resident per SIMD
-            else
-                rc = launch_mfma<2>(va, st);
-        } else if (fused) {
-            if (m <= 4)
-                rc = launch_vertex_cfg<1, 64, 1, true>(va, pa, st);   // 79 blocks per head: the whole chip pulls the basis of one head
-            else if (m <= 32)
-                rc = launch_vertex_cfg<4, 64, 1, true>(va, pa, st);   // 79 x ceil(m/4) blocks
-            else if (m <= 96)
-                rc = launch_vertex_cfg<4, 64, 4, true>(va, pa, st);   // 20 x ceil(m/4)
-            else
-                rc = launch_vertex_cfg<8, 256, 4, true>(va, pa, st);  // 5 x ceil(m/8)
-        } else if (m <= 24) {
-            rc = launch_vertex_cfg<4, 64, 4, false>(va, pa, st);
-        } else {
-            rc = launch_vertex_cfg<8, 256, 4, false>(va, pa, st);
+        const FlamePlan plan = flame_plan({g_flame_mode.load(std::memory_order_relaxed), m, pa.n_dev != nullptr, detector_mode, shape_live, expr_live, f->NB, f->K, f->NP, f->V,
+                                           f->basis8 != nullptr, f->ncu, verts || proj});
+        if (plan.prologue == FlamePrologue::Blocks16) {
+            // the padded heads of the last block stay inside the scratch (npad is a multiple of 128)
+            constexpr int HB = 16;
+            const size_t lds = (size_t)HB * sizeof(PrepScratch) + (size_t)HB * HP_SIZE * 4 + (size_t)f->Kp * HB * 4;
+            static PerDevice opted_in;
+            VGH_HIP(opt_in_dynamic_lds(opted_in, 128 * 1024, flame_prep_multi_kernel<HB>));
+            hipLaunchKernelGGL(flame_prep_multi_kernel<HB>, dim3((m + HB - 1) / HB), dim3(HB * 64), lds, st, pa);
+        } else if (plan.prologue == FlamePrologue::WavePerHead) {
+            hipLaunchKernelGGL(flame_prep_kernel, dim3(m), dim3(64), 0, st, pa);
+        }
+        if (plan.prologue != FlamePrologue::None) VGH_HIP(hipGetLastError());
+        if (!verts && !proj) continue;
+        int rc = VGH_OK;
+        switch (plan.kernel) {
+#define FLAME_PLAN_CASE(name, ...)  \
+    case FlameKernel::name:         \
+        rc = __VA_ARGS__;           \
+        break;
+            FLAME_QUAD_KERNELS(FLAME_PLAN_CASE) FLAME_VERTEX_KERNELS(FLAME_PLAN_CASE)
+#undef FLAME_PLAN_CASE
+            case FlameKernel::None: break;  // (not reached: a decode without outputs has left the loop body above)
         }
         if (rc) return rc;
     }

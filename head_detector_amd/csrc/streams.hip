@@ -17,6 +17,7 @@
 #include <mutex>
 #include <vector>
 
+#include "per_device.h"
 #include "vgh_internal.h"
 
 namespace {
@@ -37,7 +38,9 @@ __global__ void spin_grid_kernel(long long ticks) {
 }
 
 constexpr long long kSpinTicks = 15000;  // 150 us
-constexpr int kMaxDev = 16, kMaxTries = 10;
+constexpr int kSpinGridLds = 80 * 1024;
+PerDevice g_spin_grid_opted_in;
+constexpr int kMaxTries = 10;
 // Upper bound on the streams one (device, priority) park ever holds.  With H hardware queues at most H - n_avoid candidates can be
 // "perfect"; when none is (e.g. main + 3 lanes already occupy the 4 default queues) every further hipStreamCreate lands on one of the
 // same H queues, so a full park already contains a member of every queue class and creating more only leaks streams and lengthens the
@@ -53,7 +56,7 @@ struct DeviceGuard {  // restores the caller's current device on every exit path
 };
 
 std::mutex g_mu;
-std::vector<hipStream_t> g_park[2][kMaxDev];  // [normal | lowest priority]
+std::vector<hipStream_t> g_park[2][kMaxDevices];  // [normal | lowest priority]
 
 // true when kernels queued on a and b at the same time overlap
 bool runs_concurrently(hipStream_t a, hipStream_t b) {
@@ -89,25 +92,29 @@ bool runs_concurrently(hipStream_t a, hipStream_t b) {
 // pipe only when `a`'s dispatches have been placed.
 bool blocked_behind(hipStream_t a, hipStream_t b) {
     if (a == b) return true;
-    static bool attr = false;
-    const int lds = 80 * 1024;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)spin_grid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr = true;
-    }
+    const int lds = kSpinGridLds;
+    if (opt_in_dynamic_lds(g_spin_grid_opted_in, lds, spin_grid_kernel) != hipSuccess) return false;  // no probe, no verdict: not blocked
     int dev = 0, cus = 256;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    hipEvent_t e0, ea, eb;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&ea) != hipSuccess || hipEventCreate(&eb) != hipSuccess) return false;
+    hipEvent_t ev[3];
+    for (int i = 0; i < 3; ++i)
+        if (hipEventCreate(&ev[i]) != hipSuccess) {
+            while (i > 0) (void)hipEventDestroy(ev[--i]);
+            return false;
+        }
+    const hipEvent_t e0 = ev[0], ea = ev[1], eb = ev[2];
     const int grid = cus * 2 * 6;  // six rounds of the LDS-limited residency, 10 us each
     int votes = 0;
+    bool probed = true;  // both multi-round kernels of every pass were launched: a pass without them times nothing and would vote "blocked"
     for (int pass = 0; pass < 3; ++pass) {  // pass 0 warms both streams up; "blocked" is believed when seen in both timed passes
         (void)hipStreamSynchronize(a);
         (void)hipStreamSynchronize(b);
         (void)hipEventRecord(e0, a);
         hipLaunchKernelGGL(spin_grid_kernel, dim3(grid), dim3(64), lds, a, 1000);
+        probed = hipGetLastError() == hipSuccess && probed;
         hipLaunchKernelGGL(spin_grid_kernel, dim3(grid), dim3(64), lds, a, 1000);
+        probed = hipGetLastError() == hipSuccess && probed;
         (void)hipEventRecord(ea, a);
         (void)hipStreamWaitEvent(b, e0, 0);
         hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, b, 100);
@@ -123,7 +130,7 @@ bool blocked_behind(hipStream_t a, hipStream_t b) {
     (void)hipEventDestroy(ea);
     (void)hipEventDestroy(eb);
     (void)hipGetLastError();
-    return votes == 2;
+    return probed && votes == 2;
 }
 
 int overlap_score(hipStream_t c, const hipStream_t* avoid, int n_avoid, bool low_priority) {
@@ -138,7 +145,7 @@ int overlap_score(hipStream_t c, const hipStream_t* avoid, int n_avoid, bool low
 }  // namespace
 
 int vgh_stream_acquire_internal(int device, const hipStream_t* avoid, int n_avoid, hipStream_t* out, bool low_priority) {
-    VGH_REQUIRE(out && device >= 0 && device < kMaxDev && n_avoid >= 0 && n_avoid <= 8, "stream_acquire: bad argument");
+    VGH_REQUIRE(out && device >= 0 && device < kMaxDevices && n_avoid >= 0 && n_avoid <= 8, "stream_acquire: bad argument");
     std::lock_guard<std::mutex> lk(g_mu);
     DeviceGuard guard;
     VGH_HIP(hipGetDevice(&guard.prev));
@@ -175,7 +182,7 @@ int vgh_stream_acquire_internal(int device, const hipStream_t* avoid, int n_avoi
 }
 
 void vgh_stream_release_internal(int device, hipStream_t s, bool low_priority) {
-    if (!s || device < 0 || device >= kMaxDev) return;
+    if (!s || device < 0 || device >= kMaxDevices) return;
     std::lock_guard<std::mutex> lk(g_mu);
     g_park[low_priority ? 1 : 0][device].push_back(s);
 }
@@ -204,12 +211,8 @@ int vgh_stream_blocked_behind(void* a, void* b) { return blocked_behind((hipStre
 // first-kernel completion time / pair completion time for two multi-round kernels launched back to back on a and b:
 // ~1.0 = their workgroups interleave, ~0.5 = b's only start when a's are all dispatched.  *1000 (integer per-mille).
 int vgh_streams_interleave_permille(void* a, void* b) {
-    static bool attr = false;
-    const int lds = 80 * 1024;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)spin_grid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr = true;
-    }
+    const int lds = kSpinGridLds;
+    (void)opt_in_dynamic_lds(g_spin_grid_opted_in, lds, spin_grid_kernel);
     hipStream_t sa = (hipStream_t)a, sb = (hipStream_t)b;
     hipEvent_t e0, ea, eb;
     if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&ea) != hipSuccess || hipEventCreate(&eb) != hipSuccess) return -1;
