@@ -124,11 +124,11 @@
     X(128, 64, 32, 64, 2, 3, 3)
 
 namespace vghcfg {
-#define VGH_DECL_P(TW, TH, BC, NWP, NWC) __attribute__((visibility("hidden"))) void lp_##TW##_##TH##_##BC##_##NWP##_##NWC(const ConvArgs&, int, int, int, int, int, int, hipStream_t);
-#define VGH_DECL_Q(TW, TH, BC, NWP, NWC) __attribute__((visibility("hidden"))) void lq_##TW##_##TH##_##BC##_##NWP##_##NWC(const ConvArgs&, int, int, int, int, int, int, hipStream_t);
-#define VGH_DECL_T(BP, BC, WP, WC, KBS, NST) __attribute__((visibility("hidden"))) void lt_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST(const ConvArgs&, int, int, int, int, hipStream_t);
-#define VGH_DECL_R(BP, BC, WP, WC, KBS, NST) __attribute__((visibility("hidden"))) void lr_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST(const ConvArgs&, int, int, int, int, hipStream_t);
-#define VGH_DECL_L(BP, BC, WP, WC, KBS, NST, LF) __attribute__((visibility("hidden"))) void ll_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST##_##LF(const ConvArgs&, int, int, int, int, hipStream_t);
+#define VGH_DECL_P(TW, TH, BC, NWP, NWC) __attribute__((visibility("hidden"))) VGH_TILE_LAUNCHER(lp_##TW##_##TH##_##BC##_##NWP##_##NWC);
+#define VGH_DECL_Q(TW, TH, BC, NWP, NWC) __attribute__((visibility("hidden"))) VGH_TILE_LAUNCHER(lq_##TW##_##TH##_##BC##_##NWP##_##NWC);
+#define VGH_DECL_T(BP, BC, WP, WC, KBS, NST) __attribute__((visibility("hidden"))) VGH_TILE_LAUNCHER(lt_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST);
+#define VGH_DECL_R(BP, BC, WP, WC, KBS, NST) __attribute__((visibility("hidden"))) VGH_TILE_LAUNCHER(lr_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST);
+#define VGH_DECL_L(BP, BC, WP, WC, KBS, NST, LF) __attribute__((visibility("hidden"))) VGH_TILE_LAUNCHER(ll_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST##_##LF);
 VGH_RCFG_LIST(VGH_DECL_R)
 VGH_LCFG_LIST(VGH_DECL_L)
 #undef VGH_DECL_R

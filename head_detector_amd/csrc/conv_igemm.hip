@@ -23,10 +23,10 @@ namespace {
 
 struct CfgEntry {
     const char* name;
+    TileFamily family;  // which kernel, and which convs it admits (conv_tiles.h)
     int BP, BC, threads, lds;
-    void (*launch)(const ConvArgs&, int, int, int, int, hipStream_t);
-    int patch, TW, TH;  // 7: conv3x3_pp_kernel with two 4 x 8 sub-patches per wave; 5: conv3x3_pp_kernel (conv_pp.hip: 8-wave ping-pong, 8 x 8 sub-patch per wave); 1 / 2: conv3x3_patch_kernel / conv3x3_patch3_kernel (3x3, stride 1, tile TH x TW); 3: conv1x1_stream_kernel; 4: conv3x3_patch_kernel stride 2 (output tile TH x TW); fast epilogue only
-    void (*launch_patch)(const ConvArgs&, int, int, int, int, int, int, hipStream_t);
+    int TW, TH;  // output tile (ping-pong families: sub-patch) of the families that tile the map in 2-D, else 0
+    VGH_TILE_LAUNCHER((*launch));
 };
 
 static std::atomic<int> g_max_blocks_per_xcd{0};
@@ -52,47 +52,51 @@ namespace {
 
 #ifdef VGH_EXPERIMENTS
 template <int TW, int TH, int BC, int NWP, int NWC>
-void launch_patch_s2_cfg(const ConvArgs& a, int ntc, int ntx, int nty, int total, int chunk, int lds, hipStream_t st) {
+VGH_TILE_LAUNCHER(launch_patch_s2_cfg) {
     static PerDevice per_cu;
     const int n = patch_blocks_per_cu(conv3x3_patch_kernel<TW, TH, BC, NWP, NWC, 0, 1>, NWP * NWC * 64, lds, per_cu);
-    const int gpx = vgh_conv_persistent_blocks_per_xcd(a, chunk, n);
-    hipLaunchKernelGGL((conv3x3_patch_kernel<TW, TH, BC, NWP, NWC, 0, 1>), dim3(gpx * 8), dim3(NWP * NWC * 64), lds, st, a, ntc, ntx, nty, total, chunk);
+    const int gpx = vgh_conv_persistent_blocks_per_xcd(a, g.chunk, n);
+    hipLaunchKernelGGL((conv3x3_patch_kernel<TW, TH, BC, NWP, NWC, 0, 1>), dim3(gpx * 8), dim3(NWP * NWC * 64), lds, st, a, g.ntc, g.ntx, g.nty, g.total, g.chunk);
+    return VGH_OK;
 }
 #endif
 
 #include "conv_launch_igemm.inc"
 
-constexpr int lds_bytes(int BP, int BC, int WP, int WC, int KBS, int NST) {
-    const int nw = (BP / WP) * (BC / WC);
-    const int loop = NST * KBS * (BP + BC) * 64 + (NST > 2 ? nw * 1024 : 0), epi = nw * 32 * (WC + 4) * 4;
-    return loop > epi ? loop : epi;
+// the tiles of conv_pp.hip and ds_b2b.hip size their own LDS (table column 0) and check the launch themselves
+template <TileFamily F, int BC>
+VGH_TILE_LAUNCHER(launch_pp_tile) {
+    return vgh_launch_conv_pp(a, F, BC, g, g_max_blocks_per_xcd.load(std::memory_order_relaxed), st);
 }
+VGH_TILE_LAUNCHER(launch_r_tile) { return vgh_launch_conv_ds(a, g, st); }
+VGH_TILE_LAUNCHER(launch_w_tile) { return vgh_launch_conv_w(a, g, st); }
 #define CFG(BP, BC, WP, WC, KBS) \
-    { #BP "x" #BC "_w" #WP "x" #WC "_k" #KBS, BP, BC, (BP / WP) * (BC / WC) * 64, lds_bytes(BP, BC, WP, WC, KBS, 2), launch_cfg<BP, BC, WP, WC, KBS, 2>, 0, 0, 0, nullptr }
+    { #BP "x" #BC "_w" #WP "x" #WC "_k" #KBS, TileFamily::Igemm, BP, BC, (BP / WP) * (BC / WC) * 64, lds_bytes(BP, BC, WP, WC, KBS, 2), 0, 0, launch_cfg<BP, BC, WP, WC, KBS, 2> }
 #define CFGR(BP, BC, WP, WC, KBS, NST) \
-    { #BP "x" #BC "_w" #WP "x" #WC "_k" #KBS "_r" #NST, BP, BC, (BP / WP) * (BC / WC) * 64, lds_bytes(BP, BC, WP, WC, KBS, NST), vghcfg::lr_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST, 0, 0, 0, nullptr }
+    { #BP "x" #BC "_w" #WP "x" #WC "_k" #KBS "_r" #NST, TileFamily::Igemm, BP, BC, (BP / WP) * (BC / WC) * 64, lds_bytes(BP, BC, WP, WC, KBS, NST), 0, 0, vghcfg::lr_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST }
 #define LCFG(BP, BC, WP, WC, KBS, NST, LF) \
-    { #BP "x" #BC "_w" #WP "x" #WC "_k" #KBS "_r" #NST "_l" #LF, BP, BC, (BP / WP) * (BC / WC) * 64 * LF, lds_bytes(BP, BC, WP, WC, KBS, NST), vghcfg::ll_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST##_##LF, 0, 0, 0, nullptr }
+    { #BP "x" #BC "_w" #WP "x" #WC "_k" #KBS "_r" #NST "_l" #LF, TileFamily::Igemm, BP, BC, (BP / WP) * (BC / WC) * 64 * LF, lds_bytes(BP, BC, WP, WC, KBS, NST), 0, 0, vghcfg::ll_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST##_##LF }
 #define PCFG(TW, TH, BC, NWP, NWC) \
-    { "p" #TH "x" #TW "x" #BC "_n" #NWP "x" #NWC, (TW) * (TH), BC, (NWP) * (NWC) * 64, patch_lds<TW, TH, BC, NWP, NWC>(), nullptr, 1, TW, TH, vghcfg::lp_##TW##_##TH##_##BC##_##NWP##_##NWC }
+    { "p" #TH "x" #TW "x" #BC "_n" #NWP "x" #NWC, TileFamily::Patch, (TW) * (TH), BC, (NWP) * (NWC) * 64, patch_lds<TW, TH, BC, NWP, NWC>(), TW, TH, vghcfg::lp_##TW##_##TH##_##BC##_##NWP##_##NWC }
 
 #define QCFG(TW, TH, BC, NWP, NWC) \
-    { "q" #TH "x" #TW "x" #BC "_n" #NWP "x" #NWC, (TW) * (TH), BC, (NWP) * (NWC) * 64, Patch3<TW, TH, BC, NWP, NWC>::LDS, nullptr, 2, TW, TH, vghcfg::lq_##TW##_##TH##_##BC##_##NWP##_##NWC }
+    { "q" #TH "x" #TW "x" #BC "_n" #NWP "x" #NWC, TileFamily::PatchPipe, (TW) * (TH), BC, (NWP) * (NWC) * 64, Patch3<TW, TH, BC, NWP, NWC>::LDS, TW, TH, vghcfg::lq_##TW##_##TH##_##BC##_##NWP##_##NWC }
 
 #ifdef VGH_EXPERIMENTS
 #define DCFG(TW, TH, BC, NWP, NWC) \
-    { "d" #TH "x" #TW "x" #BC "_n" #NWP "x" #NWC, (TW) * (TH), BC, (NWP) * (NWC) * 64, patch_lds<TW, TH, BC, NWP, NWC, 1>(), nullptr, 4, TW, TH, launch_patch_s2_cfg<TW, TH, BC, NWP, NWC> }
+    { "d" #TH "x" #TW "x" #BC "_n" #NWP "x" #NWC, TileFamily::PatchS2, (TW) * (TH), BC, (NWP) * (NWC) * 64, patch_lds<TW, TH, BC, NWP, NWC, 1>(), TW, TH, launch_patch_s2_cfg<TW, TH, BC, NWP, NWC> }
 #endif
 #define TCFG(BP, BC, WP, WC, KBS, NST) \
-    { "t" #BP "x" #BC "_w" #WP "x" #WC "_k" #KBS "_r" #NST, BP, BC, (BP / WP) * (BC / WC) * 64, Stream1<BP, BC, WP, WC, KBS, NST>::LDS, vghcfg::lt_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST, 3, 0, 0, nullptr }
+    { "t" #BP "x" #BC "_w" #WP "x" #WC "_k" #KBS "_r" #NST, TileFamily::Stream, BP, BC, (BP / WP) * (BC / WC) * 64, Stream1<BP, BC, WP, WC, KBS, NST>::LDS, 0, 0, vghcfg::lt_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST }
 
 #define GCFG(BC) \
-    { "g8x8x" #BC "_n8", 512, BC, 512, 0, nullptr, 5, 8, 8, nullptr }
+    { "g8x8x" #BC "_n8", TileFamily::PingPongG, 512, BC, 512, 0, 8, 8, launch_pp_tile<TileFamily::PingPongG, BC> }
 #define HCFG(BC) \
-    { "h8x8x" #BC "_n8", 512, BC, 512, 0, nullptr, 6, 8, 8, nullptr }
+    { "h8x8x" #BC "_n8", TileFamily::PingPongH, 512, BC, 512, 0, 8, 8, launch_pp_tile<TileFamily::PingPongH, BC> }
 #define SCFG(BC) \
-    { "s4x8x" #BC "_n8", 512, BC, 512, 0, nullptr, 7, 8, 4, nullptr }
+    { "s4x8x" #BC "_n8", TileFamily::PingPongS, 512, BC, 512, 0, 8, 4, launch_pp_tile<TileFamily::PingPongS, BC> }
 
+// The ORDER of this table is frozen: tuning/conv_cfg.json and the tools name tiles, but pick_size_only below and recorded results hold indices.
 const CfgEntry g_cfgs[] = {
     CFG(128, 128, 64, 64, 1),  // 0
     CFG(256, 64, 64, 64, 1),   // 1
@@ -215,64 +219,64 @@ const CfgEntry g_cfgs[] = {
     // Measured (profiles/r03_tune_d_*.json): correct and conflict-free, but 10 - 60 % SLOWER than the implicit-GEMM rings on every stride-2 layer
     // (stage-1 downsample 439 vs 368 us): a 64-pixel tile has 0.3 us of MFMAs per (channel block, kernel row) step against a 1 us L2 round trip for
     // the next step's weights.  Kept as tuner candidates (the four best shapes; eight more were measured and dropped).
-    DCFG(16, 4, 96, 1, 3),    // 113  64 output px x 96: 3 waves x (64 px x 32)
-    DCFG(16, 4, 64, 2, 2),    // 114  4 waves x (32 px x 32)
-    DCFG(16, 8, 128, 4, 2),   // 115  128 output px: 8 waves x (32 px x 64)
-    DCFG(32, 4, 128, 4, 2),   // 116
+    DCFG(16, 4, 96, 1, 3),  // 64 output px x 96: 3 waves x (64 px x 32)
+    DCFG(16, 4, 64, 2, 2),  // 4 waves x (32 px x 32)
+    DCFG(16, 8, 128, 4, 2),  // 128 output px: 8 waves x (32 px x 64)
+    DCFG(32, 4, 128, 4, 2),
 #endif
     // 64-pixel halo-patch tiles for the 20^2 / 40^2 maps at small batch (M b32: 12 800 pixels = 100 tiles of 128 px per cout tile, i.e. one partial
     // round of the chip; twice the tiles of half the length fill it better)
-    PCFG(16, 4, 64, 2, 2),    // 117  4 waves x (32 px x 32)
-    PCFG(16, 4, 128, 2, 2),   // 118  4 waves x (32 px x 64)
-    PCFG(16, 4, 128, 2, 4),   // 119  8 waves x (32 px x 32)
-    PCFG(16, 4, 96, 2, 3),    // 120  6 waves x (32 px x 32)
-    PCFG(16, 4, 64, 2, 1),    // 121  2 waves x (32 px x 64)
+    PCFG(16, 4, 64, 2, 2),  // 4 waves x (32 px x 32)
+    PCFG(16, 4, 128, 2, 2),  // 4 waves x (32 px x 64)
+    PCFG(16, 4, 128, 2, 4),  // 8 waves x (32 px x 32)
+    PCFG(16, 4, 96, 2, 3),  // 6 waves x (32 px x 32)
+    PCFG(16, 4, 64, 2, 1),  // 2 waves x (32 px x 64)
     // 8-wave ping-pong tiles (conv_pp.hip, r04): 8 sub-patches of 8 x 8 pixels x BC couts per workgroup, one workgroup per CU
-    GCFG(128),  // 122
-    GCFG(96),   // 123
-    GCFG(64),   // 124
+    GCFG(128),
+    GCFG(96),
+    GCFG(64),
     // the same tiles with ONE barrier per tap (conv3x3_pp_kernel<TI, 2>: the groups run M -> L / L -> M inside a slot, 4-stage weight ring)
-    HCFG(128),  // 125
-    HCFG(96),   // 126
-    HCFG(64),   // 127
+    HCFG(128),
+    HCFG(96),
+    HCFG(64),
     // the g tiles with TWO 4 x 8 sub-patches per wave (conv3x3_pp_kernel<TI, 1, ..., GEO = 1>, r06): 20-wide maps tile as 8 + 8 + 8 (the last one overlapping four
     // columns) x five 4-row bands -- 1.2 x the pixels where the 8 x 8 patches cover 1.44 x -- and small maps split into twice as many independent sub-patches
-    SCFG(128),  // 128
-    SCFG(96),   // 129
-    SCFG(64),   // 130
+    SCFG(128),
+    SCFG(96),
+    SCFG(64),
     // 192-cout tiles (r06): the stride-2 3x3 layers with 192 couts ran two 96-cout tiles per pixel tile, i.e. loaded every activation k-block twice; what bounds the
     // implicit-GEMM family below the MFMA rate is the bytes a CU pulls through its LDS-DMA path (~12 - 16 B / clk / CU measured against 64 nominal), so flop per byte counts
-    CFG(256, 192, 64, 96, 1),      // 131  8 waves x (64 px x 96)
-    CFGR(256, 192, 64, 96, 1, 3),  // 132
-    CFG(128, 192, 32, 96, 1),      // 133  8 waves x (32 px x 96)
-    CFGR(128, 192, 32, 96, 1, 3),  // 134
+    CFG(256, 192, 64, 96, 1),  // 8 waves x (64 px x 96)
+    CFGR(256, 192, 64, 96, 1, 3),
+    CFG(128, 192, 32, 96, 1),  // 8 waves x (32 px x 96)
+    CFGR(128, 192, 32, 96, 1, 3),
     // deep rings on the small tiles (r06, single-image latency): at B = 1 a 20^2 / 40^2 layer is 56 - 150 blocks, each walking K = 1728 - 4608 alone; a step of the
     // 2-stage loop costs one L2 / HBM round trip (~0.85 us for 128 k: 31 us per stage-4 layer with 2 us of MFMAs in it) -- three stages of LDS-DMA in flight instead of one
-    CFGR(64, 64, 32, 32, 4, 3),    // 135
-    CFGR(64, 64, 32, 32, 4, 4),    // 136  128 KiB of stages: one block per CU (there are fewer blocks than CUs)
-    CFGR(64, 64, 32, 32, 2, 4),    // 137
-    CFGR(64, 32, 32, 32, 4, 4),    // 138  2 waves
-    CFGR(128, 32, 32, 32, 4, 3),   // 139
-    CFGR(128, 64, 32, 64, 2, 4),   // 140
+    CFGR(64, 64, 32, 32, 4, 3),
+    CFGR(64, 64, 32, 32, 4, 4),  // 128 KiB of stages: one block per CU (there are fewer blocks than CUs)
+    CFGR(64, 64, 32, 32, 2, 4),
+    CFGR(64, 32, 32, 32, 4, 4),  // 2 waves
+    CFGR(128, 32, 32, 32, 4, 3),
+    CFGR(128, 64, 32, 64, 2, 4),
     // loader waves (r06): the same small tiles with 2 - 6 x the waves, all of them staging tiles (one wave loads ~14 GB/s whatever it keeps in flight)
-    LCFG(64, 64, 32, 32, 4, 3, 2),   // 141  8 waves
-    LCFG(64, 64, 32, 32, 4, 3, 4),   // 142  16 waves
-    LCFG(64, 64, 32, 32, 4, 4, 4),   // 143
-    LCFG(64, 64, 32, 32, 2, 4, 4),   // 144
-    LCFG(64, 32, 32, 32, 4, 3, 3),   // 145  6 waves
-    LCFG(64, 32, 32, 32, 4, 3, 6),   // 146  12 waves
-    LCFG(32, 64, 32, 32, 4, 3, 3),   // 147  32-pixel tiles: 13 instead of 7 pixel tiles over a 20^2 map
-    LCFG(32, 64, 32, 32, 4, 3, 6),   // 148
-    LCFG(128, 64, 32, 64, 2, 3, 3),  // 149  12 waves
-    CFGR(128, 96, 32, 96, 1, 3),     // 150  three stages = 46 KiB < the 51 KiB of epilogue strips: still three blocks per CU, two stages in flight each
-    CFGR(128, 192, 32, 96, 1, 4),    // 151
+    LCFG(64, 64, 32, 32, 4, 3, 2),  // 8 waves
+    LCFG(64, 64, 32, 32, 4, 3, 4),  // 16 waves
+    LCFG(64, 64, 32, 32, 4, 4, 4),
+    LCFG(64, 64, 32, 32, 2, 4, 4),
+    LCFG(64, 32, 32, 32, 4, 3, 3),  // 6 waves
+    LCFG(64, 32, 32, 32, 4, 3, 6),  // 12 waves
+    LCFG(32, 64, 32, 32, 4, 3, 3),  // 32-pixel tiles: 13 instead of 7 pixel tiles over a 20^2 map
+    LCFG(32, 64, 32, 32, 4, 3, 6),
+    LCFG(128, 64, 32, 64, 2, 3, 3),  // 12 waves
+    CFGR(128, 96, 32, 96, 1, 3),  // three stages = 46 KiB < the 51 KiB of epilogue strips: still three blocks per CU, two stages in flight each
+    CFGR(128, 192, 32, 96, 1, 4),
     // "r" tile (r06, ds_b2b.hip): 3x3 / stride-2 convs with 96 input channels on the persistent 4-wave structure of the stage-1 pair's tile -- the input patch fetched once
     // into parity planes, the wave's 32-cout slice of the weights (K = 864: 54 fragments) resident in registers
-    { "r8x8x96_n4", 64, 96, 256, 0, nullptr, 8, 8, 8, nullptr },  // 152
+    { "r8x8x96_n4", TileFamily::R, 64, 96, 256, 0, 8, 8, launch_r_tile },
     // "w" tiles (r06, ds_b2b.hip): 3x3 / stride-1 convs with 96 / 128 input channels, the weights resident in registers (K = 864 / 1 152: 54 / 72 fragments per wave), one
     // wave per cout group and SIMD, no barrier inside a tile
-    { "w8x8x96_n3", 64, 96, 192, 0, nullptr, 9, 8, 8, nullptr },   // 153
-    { "w8x8x128_n4", 64, 128, 256, 0, nullptr, 9, 8, 8, nullptr },  // 154
+    { "w8x8x96_n3", TileFamily::W, 64, 96, 192, 0, 8, 8, launch_w_tile },
+    { "w8x8x128_n4", TileFamily::W, 64, 128, 256, 0, 8, 8, launch_w_tile },
     // (measured and dropped: one-block 16-wave shapes p8x32x128_n8x2 / p16x16x128_n8x2 700 / 650 TFLOP/s where two 8-wave blocks reach 840-880;
     //  p8x16x96_n4x1 654 vs 781 for p8x32x96)
 };
@@ -303,31 +307,12 @@ int vgh_conv_set_max_blocks_per_xcd(int blocks) {
 }
 int vgh_conv_cfg_ok(int cfg, int ksize, int stride, int cout_pad, int fast_epilogue, int shuffle) {
     if (cfg < 0 || cfg >= kNumCfgs) return 0;
-    const CfgEntry& e = g_cfgs[cfg];
-    if (cout_pad % e.BC) return 0;
-    if ((e.patch == 1 || e.patch == 2 || e.patch == 5 || e.patch == 6 || e.patch == 7) && !(ksize == 3 && stride == 1 && fast_epilogue && !shuffle)) return 0;
-    if (e.patch == 7 && cout_pad > 1024) return 0;
-    if (e.patch == 3 && !(ksize == 1 && stride == 1 && fast_epilogue && !shuffle)) return 0;
-    if (e.patch == 4 && !(ksize == 3 && stride == 2 && fast_epilogue && !shuffle)) return 0;
-    if (e.patch == 8 && !(ksize == 3 && stride == 2 && fast_epilogue && !shuffle && cout_pad <= 192)) return 0;
-    if (e.patch == 9 && !(ksize == 3 && stride == 1 && fast_epilogue && !shuffle && cout_pad <= 1024)) return 0;
-    return 1;
+    return tile_class_admits(g_cfgs[cfg].family, g_cfgs[cfg].BC, ksize, stride, cout_pad, fast_epilogue, shuffle) ? 1 : 0;
 }
 const char* vgh_conv_cfg_name(int cfg) { return (cfg >= 0 && cfg < kNumCfgs) ? g_cfgs[cfg].name : "?"; }
 int vgh_conv_cfg_cout_tile(int cfg) { return (cfg >= 0 && cfg < kNumCfgs) ? g_cfgs[cfg].BC : 0; }
-// as vgh_conv_cfg_ok, for a concrete launch: a grouped conv additionally needs cout tiles that do not straddle groups
-static int cfg_ok_for(int cfg, const ConvArgs& a) {
-    if (!vgh_conv_cfg_ok(cfg, a.ksize, a.stride, a.cout_pad, a.fast_epi && !a.out_f32, a.shuffle)) return 0;
-    if (a.grp_cout && a.grp_cout % g_cfgs[cfg].BC) return 0;
-    if ((a.in_fp8 || a.out_fp8) && g_cfgs[cfg].patch != 5) return 0;  // e4m3 links: g tiles only (conv_pp.hip)
-    if (a.dvec && g_cfgs[cfg].BC == 128) return 0;
-    if ((g_cfgs[cfg].patch == 5 || g_cfgs[cfg].patch == 6 || g_cfgs[cfg].patch == 7) && (a.grp_cout || a.act == VGH_ACT_SILU || a.out_f32 || !vgh_conv_pp_fits(a))) return 0;  // ping-pong tiles: dense bf16 -> bf16, ReLU / none
-    if (g_cfgs[cfg].patch == 7 && (a.Wo < 8 || a.Ho < 4)) return 0;  // 4 x 8 sub-patches are moved back inside the map, never cut
-    if (g_cfgs[cfg].patch == 3 && (a.res || a.grp_cout || a.act == VGH_ACT_SILU || a.out_f32 || a.pad)) return 0;  // streaming 1x1 tiles: plain bf16 -> bf16 only
-    if (g_cfgs[cfg].patch == 8 && !vgh_conv_ds_ok(a)) return 0;  // r tile: 96 input channels, whole 8 x 8 tiles
-    if (g_cfgs[cfg].patch == 9 && !(vgh_conv_w_ok(a) && a.cin == g_cfgs[cfg].BC)) return 0;  // w tiles: cin = the tile's 96 / 128, whole 8 x 8 tiles
-    return 1;
-}
+// as vgh_conv_cfg_ok, for a concrete launch (conv_tiles.h; no bf16 tile has a KBS clause)
+static int cfg_ok_for(int cfg, const ConvArgs& a) { return cfg >= 0 && cfg < kNumCfgs && tile_admits(g_cfgs[cfg].family, g_cfgs[cfg].BC, 1, a); }
 
 // for net.hip: can tile `cfg` run the PREPARED launch `a` (the only batch-dependent term is the ping-pong tiles' 2 GiB rule, vgh_conv_pp_fits)
 int vgh_conv_cfg_ok_for(int cfg, const ConvArgs& a) { return a.split ? 1 : cfg_ok_for(cfg, a); }
@@ -349,6 +334,23 @@ int cfg_by_name(const char* name) {
     for (int i = 0; i < kNumCfgs; ++i)
         if (strcmp(g_cfgs[i].name, name) == 0) return i;
     return -1;
+}
+
+// every name of the tables resolved once (function-local static: thread-safe): the heuristic rows' tiles, and each q tile's p twin -- the same tile shape, "p" for "q"
+struct Resolved {
+    int row_cfg[kNumHeur], q_twin[kNumCfgs];
+    Resolved() {
+        for (int i = 0; i < kNumHeur; ++i) row_cfg[i] = cfg_by_name(g_heur[i].name);
+        for (int i = 0; i < kNumCfgs; ++i) {
+            char twin[48];
+            snprintf(twin, sizeof(twin), "p%s", g_cfgs[i].name + 1);
+            q_twin[i] = g_cfgs[i].family == TileFamily::PatchPipe ? cfg_by_name(twin) : -1;
+        }
+    }
+};
+const Resolved& resolved() {
+    static const Resolved r;
+    return r;
 }
 
 int pick_size_only(const ConvArgs& a) {  // last resort: largest plain implicit-GEMM tile that still fills the chip
@@ -377,12 +379,7 @@ int vgh_conv_pick_cfg(const ConvArgs& a) {
         return (a.cout_pad % 128 == 0 && !a.dvec) ? g128 : a.cout_pad % 96 == 0 ? g96 : g64;
     }
     // A measured per-layer table (tuning/*.json) overrides this through force_cfg.
-    static int row_cfg[kNumHeur];
-    static bool resolved = false;
-    if (!resolved) {
-        for (int i = 0; i < kNumHeur; ++i) row_cfg[i] = cfg_by_name(g_heur[i].name);
-        resolved = true;
-    }
+    const int* row_cfg = resolved().row_cfg;
     const int64_t P = a.P;
     const int N = a.cout_pad, K = a.nkb * 32;
     const int pb = P < 8192 ? 0 : P < 40000 ? 1 : P < 160000 ? 2 : P < 600000 ? 3 : 4;
@@ -453,33 +450,16 @@ int vgh_launch_conv(const ConvArgs& a0, int force_cfg, hipStream_t stream) {
         VGH_REQUIRE(cfg >= 0 && cfg < kNumCfgs, "conv: fallback cfg %d out of range", cfg);
         VGH_REQUIRE(cfg_ok_for(cfg, a), "conv: no tile for this conv (cout_pad=%d k=%d s=%d grp=%d)", a.cout_pad, a.ksize, a.stride, a.grp_cout);
     }
-    if (g_cfgs[cfg].patch == 2 && !(a.cout_store == a.cout_pad && (a.out_split >= a.cout_pad || a.out_split % g_cfgs[cfg].BC == 0))) {
+    if (g_cfgs[cfg].family == TileFamily::PatchPipe && !(a.cout_store == a.cout_pad && (a.out_split >= a.cout_pad || a.out_split % g_cfgs[cfg].BC == 0))) {
         // the pipelined kernel stores whole cout tiles into ONE output segment: ragged channel counts run on its "p" twin
-        char twin[48];
-        snprintf(twin, sizeof(twin), "p%s", g_cfgs[cfg].name + 1);
-        const int t = cfg_by_name(twin);
+        const int t = resolved().q_twin[cfg];
         VGH_REQUIRE(t >= 0, "conv: cfg %s has no fallback tile", g_cfgs[cfg].name);
         cfg = t;
     }
     const CfgEntry& e = g_cfgs[cfg];
-    if (e.patch == 8) return vgh_launch_conv_ds(a, stream);
-    if (e.patch == 9) return vgh_launch_conv_w(a, stream);
-    if (e.patch == 5 || e.patch == 6 || e.patch == 7) return vgh_launch_conv_pp(a, e.BC, e.patch == 7 ? 3 : e.patch == 6 ? 2 : 1, g_max_blocks_per_xcd.load(std::memory_order_relaxed), stream);
-    if (e.patch == 1 || e.patch == 2 || e.patch == 4) {
-        const int ntc = a.cout_pad / e.BC, ntx = (a.Wo + e.TW - 1) / e.TW, nty = (a.Ho + e.TH - 1) / e.TH;  // (Ho, Wo) = (H, W) for the stride-1 tiles
-        const int64_t total = (int64_t)a.B * nty * ntx * ntc;
-        VGH_REQUIRE(total < (1ll << 30), "conv: too many tiles");
-        const int chunk = (int)((total + 7) / 8);
-        e.launch_patch(a, ntc, ntx, nty, (int)total, chunk, e.lds, stream);
-        VGH_HIP(hipGetLastError());
-        return VGH_OK;
-    }
-    const int ntc = a.cout_pad / e.BC;
-    const int64_t ntp = ((int64_t)a.P + e.BP - 1) / e.BP;
-    const int64_t total = ntp * ntc;
-    VGH_REQUIRE(total < (1ll << 30), "conv: too many tiles");
-    const int chunk = (int)((total + 7) / 8);
-    e.launch(a, ntc, (int)total, chunk, e.lds, stream);
+    TileGrid grid;
+    VGH_REQUIRE(tile_grid(e.family, e.BP, e.BC, e.TW, e.TH, a, &grid), "conv: too many tiles");
+    if (int rc = e.launch(a, grid, e.lds, stream)) return rc;
     VGH_HIP(hipGetLastError());
     return VGH_OK;
 }
@@ -492,10 +472,9 @@ int launch_b2b_96(const ConvArgs& a, hipStream_t st) {
     constexpr int lds0 = lds_bytes(BP, BC, WP, WC, KBS, NST), w2 = 3 * T2 * 2048;
     constexpr int lds = lds0 > w2 ? lds0 : w2;
     static_assert(lds <= 64 * 1024, "b2b: within the default dynamic-LDS limit");
-    const int64_t total = ((int64_t)a.P + BP - 1) / BP;
-    VGH_REQUIRE(total < (1ll << 30), "conv b2b: too many tiles");
-    const int chunk = (int)((total + 7) / 8);
-    hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, 0, T2>), dim3(chunk * 8), dim3((BP / WP) * 64), lds, st, a, 1, (int)total, chunk);
+    TileGrid g;  // one cout tile: cout_pad = BC (vgh_conv_b2b_ok)
+    VGH_REQUIRE(tile_grid(TileFamily::Igemm, BP, BC, 0, 0, a, &g), "conv b2b: too many tiles");
+    hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, 0, T2>), dim3(g.chunk * 8), dim3((BP / WP) * 64), lds, st, a, 1, g.total, g.chunk);
     VGH_HIP(hipGetLastError());
     return VGH_OK;
 }
@@ -509,11 +488,6 @@ int launch_b2b_96_any(const ConvArgs& a, hipStream_t st) {
     return launch_b2b_96<T2, 2>(a, st);
 }
 }  // namespace
-
-int vgh_conv_b2b_ok(int ksize, int stride, int cout_pad, int cout2_pad) {
-    (void)stride;
-    return (ksize == 1 || ksize == 3) && cout_pad == 96 && (cout2_pad == 256 || cout2_pad == 192 || cout2_pad == 128);
-}
 
 int vgh_launch_conv_b2b(const ConvArgs& a0, hipStream_t stream) {
     ConvArgs a = a0;
@@ -529,20 +503,4 @@ int vgh_launch_conv_b2b(const ConvArgs& a0, hipStream_t stream) {
     return a.cout2_pad == 256 ? launch_b2b_96_any<8>(a, stream) : a.cout2_pad == 192 ? launch_b2b_96_any<6>(a, stream) : launch_b2b_96_any<4>(a, stream);
 }
 
-void vgh_pack_conv_weights_host(const float* w, int cout_pad, int ksize, int cin, uint16_t* dst) {
-    // dst[kb][cout][slot][8] with slot = chunk ^ ((cout>>2)&3), kb = (ky*ks + kx)*(cin/32) + cb
-    const int cblocks = cin / 32, taps = ksize * ksize;
-    for (int tap = 0; tap < taps; ++tap)
-        for (int cb = 0; cb < cblocks; ++cb) {
-            const int kb = tap * cblocks + cb;
-            for (int co = 0; co < cout_pad; ++co) {
-                const float* src = w + ((size_t)co * taps + tap) * cin + cb * 32;
-                uint16_t* d = dst + ((size_t)kb * cout_pad + co) * 32;
-                const int sw = (co >> 2) & 3;
-                for (int chunk = 0; chunk < 4; ++chunk) {
-                    const int slot = chunk ^ sw;
-                    for (int e = 0; e < 8; ++e) d[slot * 8 + e] = vgh_f32_to_bf16_host(src[chunk * 8 + e]);
-                }
-            }
-        }
-}
+void vgh_pack_conv_weights_host(const float* w, int cout_pad, int ksize, int cin, uint16_t* dst) { vgh_pack_conv_image(w, cout_pad, ksize, cin, dst, vgh_f32_to_bf16_host); }

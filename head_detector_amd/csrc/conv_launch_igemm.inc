@@ -1,9 +1,9 @@
 // Host-side launchers of conv_igemm_kernel (included inside an anonymous namespace by conv_igemm.hip and conv_rings.hip, after conv_kernels.inc and conv_cfg_list.h).
 template <int BP, int BC, int WP, int WC, int KBS, int NST>
-void launch_cfg(const ConvArgs& a, int ntc, int total, int chunk, int lds, hipStream_t st) {
+VGH_TILE_LAUNCHER(launch_cfg) {
     static PerDevice opted_in;
     if (lds > 64 * 1024) (void)opt_in_dynamic_lds(opted_in, lds, conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST>, conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST>);
-    const dim3 grid(chunk * 8), block((BP / WP) * (BC / WC) * 64);
+    const dim3 grid(g.chunk * 8), block((BP / WP) * (BC / WC) * 64);
     constexpr int nw = (BP / WP) * (BC / WC);
     constexpr int loop_lds = NST * KBS * (BP + BC) * 64 + (NST > 2 ? nw * 1024 : 0), epi_lds = nw * 32 * (WC + 4) * 4;
     if (NST == 2 && (a.nkb + KBS - 1) / KBS == 1) {  // the whole K fits one stage: no second buffer -> more blocks per CU
@@ -17,26 +17,28 @@ void launch_cfg(const ConvArgs& a, int ntc, int total, int chunk, int lds, hipSt
     if constexpr (epi_lds > loop_lds && loop_lds <= 64 * 1024) {
         if (regepi && a.fast_epi && !a.out_f32 && !a.res && !a.shuffle && a.act != VGH_ACT_SILU) {
             const int l3 = (NST == 2 && (a.nkb + KBS - 1) / KBS == 1) ? KBS * (BP + BC) * 64 : loop_lds;
-            hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 3, NST>), grid, block, l3, st, a, ntc, total, chunk);
-            return;
+            hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 3, NST>), grid, block, l3, st, a, g.ntc, g.total, g.chunk);
+            return VGH_OK;
         }
     }
 #endif
     if (a.fast_epi)
-        hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST>), grid, block, lds, st, a, ntc, total, chunk);
+        hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST>), grid, block, lds, st, a, g.ntc, g.total, g.chunk);
     else
-        hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST>), grid, block, lds, st, a, ntc, total, chunk);
+        hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST>), grid, block, lds, st, a, g.ntc, g.total, g.chunk);
+    return VGH_OK;
 }
 
 // loader-wave tiles (conv_igemm_kernel<..., LF>): LF x the waves, the same LDS
 template <int BP, int BC, int WP, int WC, int KBS, int NST, int LF>
-void launch_cfg_lf(const ConvArgs& a, int ntc, int total, int chunk, int lds, hipStream_t st) {
+VGH_TILE_LAUNCHER(launch_cfg_lf) {
     static PerDevice opted_in;
     if (lds > 64 * 1024) (void)opt_in_dynamic_lds(opted_in, lds, conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST, 0, 0, LF>, conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, 0, 0, LF>);
-    const dim3 grid(chunk * 8), block((BP / WP) * (BC / WC) * 64 * LF);
+    const dim3 grid(g.chunk * 8), block((BP / WP) * (BC / WC) * 64 * LF);
     if (a.fast_epi)
-        hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, 0, 0, LF>), grid, block, lds, st, a, ntc, total, chunk);
+        hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, 0, 0, LF>), grid, block, lds, st, a, g.ntc, g.total, g.chunk);
     else
-        hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST, 0, 0, LF>), grid, block, lds, st, a, ntc, total, chunk);
+        hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST, 0, 0, LF>), grid, block, lds, st, a, g.ntc, g.total, g.chunk);
+    return VGH_OK;
 }
 

@@ -986,18 +986,13 @@ int launch_pp(const ConvArgs& a, int ntc, int nsx, int nsy, int nsp, int total, 
 
 }  // namespace
 
-// the epilogue addresses the output and residual tensors through buffer descriptors: 32-bit byte offsets
-int vgh_conv_pp_fits(const ConvArgs& a) {
-    const int64_t lim = (1ll << 31) - 4096;
-    return (int64_t)a.P * a.out_pitch * (a.out_fp8 ? 1 : 2) < lim && (!a.res || (int64_t)a.P * a.res_pitch * 2 < lim) && a.cout_pad <= 2048 &&
-           (int64_t)a.W * a.in_pitch * 2 < (1 << 24);  // one input row in 24 bits: the halo offsets are 24-bit multiply-adds
-}
 int vgh_conv_pp_lds(int bc) { return bc == 128 ? PPGeo<4, 2>::LDS : bc == 96 ? PPGeo<3, 2>::LDS : bc == 64 ? PPGeo<2, 2>::LDS : 0; }
 static_assert(PPGeo<4, 1, 1>::LDS <= 160 * 1024, "e4m3 g tiles: bias + factor vectors must fit the 160 KB LDS");
 static_assert(PPGeo<4, 1, 0, 1>::LDS <= 160 * 1024, "4 x 8 sub-patch tiles: two 8-KB halo stages per wave + the weight ring must fit the 160 KB LDS");
 
-int vgh_launch_conv_pp(const ConvArgs& a, int bc, int version, int max_blocks_per_xcd, hipStream_t stream) {
-    const bool h16 = a.split == VGH_FMT_F16X2 && a.nseg == 1;  // single-plane fp16 (VGH_FMT_F16) through conv_split.hip's pseudo-tiles
+int vgh_launch_conv_pp(const ConvArgs& a, TileFamily family, int bc, const TileGrid& g, int max_blocks_per_xcd, hipStream_t stream) {
+    const int version = family == TileFamily::PingPongS ? 3 : family == TileFamily::PingPongH ? 2 : 1;  // 1: "g" (two barriers per tap; also the fp16 variant), 2: "h" (one), 3: "s" (g with two 4 x 8 sub-patches per wave)
+    const bool h16 = a.split == VGH_FMT_F16X2 && a.nseg == 1;  // single-plane fp16 (VGH_FMT_F16) through the PingPongF16 rows of conv_split.hip's table
     VGH_REQUIRE(a.ksize == 3 && a.stride == 1 && a.fast_epi && !a.out_f32 && !a.shuffle && !a.grp_cout && (!a.split || h16) && a.act != VGH_ACT_SILU, "conv: the ping-pong tiles run plain 3x3 / stride-1 bf16 / fp16 / e4m3 convs only");
     VGH_REQUIRE(!h16 || (version == 1 && !a.in_fp8 && !a.out_fp8 && a.out_scale > 0.0f && a.cout_store == a.cout_pad), "conv: the fp16 ping-pong variant takes whole cout tiles and the op's weight prescale");
     if (a.in_fp8 || a.out_fp8) {
@@ -1012,26 +1007,22 @@ int vgh_launch_conv_pp(const ConvArgs& a, int bc, int version, int max_blocks_pe
     VGH_REQUIRE(vgh_conv_pp_fits(a), "conv: output / residual tensor above 2 GiB (32-bit buffer offsets), or an input row above 16 MiB");
     const bool geo = version == 3;  // "s" tiles: two 4 x 8 sub-patches per wave
     VGH_REQUIRE(!geo || (a.Wo >= 8 && a.Ho >= 4 && a.cout_pad <= 1024 && !a.in_fp8 && !a.out_fp8 && !h16), "conv: the 4 x 8 sub-patch tiles need a bf16 map of at least 4 x 8 pixels and cout_pad <= 1024");
-    const int nsx = (a.Wo + 7) / 8, nsy = geo ? (a.Ho + 3) / 4 : (a.Ho + 7) / 8, ntc = a.cout_pad / bc;
-    const int64_t nsp = (int64_t)a.B * nsy * nsx;
-    const int64_t total = (nsp + (geo ? 15 : 7)) / (geo ? 16 : 8) * ntc;
-    VGH_REQUIRE(total < (1ll << 30), "conv: too many tiles");
-    const int chunk = (int)((total + 7) / 8);
+    const int nsx = g.ntx, nsy = g.nty, ntc = g.ntc, nsp = a.B * nsy * nsx, total = g.total, chunk = g.chunk;  // sub-patches across / down a map and in the batch (conv_tiles.h)
     if (a.in_fp8 || a.out_fp8) {
         const int f = a.in_fp8 ? 1 : 0, o = a.out_fp8 ? 1 : 0;
         const bool i8 = a.in_fp8 == 2 || a.out_fp8 == 2;
 #define PP_F8_CASE(TI_, Q_)                                                                                            \
     if (bc == 32 * TI_) {                                                                                              \
-        if (f && o) return launch_pp<TI_, 1, Q_, Q_>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream); \
-        if (f) return launch_pp<TI_, 1, Q_, 0>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);       \
-        return launch_pp<TI_, 1, 0, Q_>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);              \
+        if (f && o) return launch_pp<TI_, 1, Q_, Q_>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream); \
+        if (f) return launch_pp<TI_, 1, Q_, 0>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);       \
+        return launch_pp<TI_, 1, 0, Q_>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);              \
     }
         if (a.dvec) {
             VGH_REQUIRE(a.in_fp8 == 2 && !a.out_fp8 && a.cout_pad <= 1024 && a.cin >= a.cout_pad && a.Ho == a.H && a.Wo == a.W,
                         "conv: the diagonal bypass (dvec) belongs to an int8 -> bf16 conv with cout_pad <= min(cin, 1024)");
             switch (bc) {  // (no 128-cout variant: it spills ~90 registers; vgh_conv_pick_cfg / cfg_ok_for keep such ops on 96 / 64)
-                case 96: return launch_pp<3, 1, 2, 0, 0, 1>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
-                case 64: return launch_pp<2, 1, 2, 0, 0, 1>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
+                case 96: return launch_pp<3, 1, 2, 0, 0, 1>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
+                case 64: return launch_pp<2, 1, 2, 0, 0, 1>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
             }
         }
         if (i8) {
@@ -1050,27 +1041,27 @@ int vgh_launch_conv_pp(const ConvArgs& a, int bc, int version, int max_blocks_pe
         ConvArgs ah = a;
         ah.bias_scale = 1.0f / a.out_scale;
         switch (bc) {
-            case 128: return launch_pp<4, 1, 0, 0, 1>(ah, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
-            case 96: return launch_pp<3, 1, 0, 0, 1>(ah, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
-            case 64: return launch_pp<2, 1, 0, 0, 1>(ah, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
+            case 128: return launch_pp<4, 1, 0, 0, 1>(ah, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
+            case 96: return launch_pp<3, 1, 0, 0, 1>(ah, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
+            case 64: return launch_pp<2, 1, 0, 0, 1>(ah, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
         }
         VGH_REQUIRE(false, "conv: no fp16 ping-pong tile with %d couts", bc);
     }
     if (geo) {
         switch (bc) {
-            case 128: return launch_pp<4, 1, 0, 0, 0, 0, 1>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
-            case 96: return launch_pp<3, 1, 0, 0, 0, 0, 1>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
-            case 64: return launch_pp<2, 1, 0, 0, 0, 0, 1>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
+            case 128: return launch_pp<4, 1, 0, 0, 0, 0, 1>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
+            case 96: return launch_pp<3, 1, 0, 0, 0, 0, 1>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
+            case 64: return launch_pp<2, 1, 0, 0, 0, 0, 1>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
         }
         VGH_REQUIRE(false, "conv: no 4 x 8 ping-pong tile with %d couts", bc);
     }
     switch (bc + (version == 2 ? 1 : 0)) {
-        case 128: return launch_pp<4, 1>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
-        case 96: return launch_pp<3, 1>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
-        case 64: return launch_pp<2, 1>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
-        case 129: return launch_pp<4, 2>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
-        case 97: return launch_pp<3, 2>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
-        case 65: return launch_pp<2, 2>(a, ntc, nsx, nsy, (int)nsp, (int)total, chunk, max_blocks_per_xcd, stream);
+        case 128: return launch_pp<4, 1>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
+        case 96: return launch_pp<3, 1>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
+        case 64: return launch_pp<2, 1>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
+        case 129: return launch_pp<4, 2>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
+        case 97: return launch_pp<3, 2>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
+        case 65: return launch_pp<2, 2>(a, ntc, nsx, nsy, nsp, total, chunk, max_blocks_per_xcd, stream);
     }
     VGH_REQUIRE(false, "conv: no ping-pong tile with %d couts", bc);
     return VGH_OK;

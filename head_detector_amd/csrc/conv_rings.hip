@@ -8,14 +8,10 @@ namespace {
 }  // namespace
 
 namespace vghcfg {
-#define VGH_DEF_R(BP, BC, WP, WC, KBS, NST)                                                                                        \
-    void lr_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST(const ConvArgs& a, int ntc, int total, int chunk, int lds, hipStream_t st) { \
-        launch_cfg<BP, BC, WP, WC, KBS, NST>(a, ntc, total, chunk, lds, st);                                                       \
-    }
-#define VGH_DEF_L(BP, BC, WP, WC, KBS, NST, LF)                                                                                             \
-    void ll_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST##_##LF(const ConvArgs& a, int ntc, int total, int chunk, int lds, hipStream_t st) { \
-        launch_cfg_lf<BP, BC, WP, WC, KBS, NST, LF>(a, ntc, total, chunk, lds, st);                                                        \
-    }
+#define VGH_DEF_R(BP, BC, WP, WC, KBS, NST) \
+    VGH_TILE_LAUNCHER(lr_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST) { return launch_cfg<BP, BC, WP, WC, KBS, NST>(a, g, lds, st); }
+#define VGH_DEF_L(BP, BC, WP, WC, KBS, NST, LF) \
+    VGH_TILE_LAUNCHER(ll_##BP##_##BC##_##WP##_##WC##_##KBS##_##NST##_##LF) { return launch_cfg_lf<BP, BC, WP, WC, KBS, NST, LF>(a, g, lds, st); }
 VGH_RCFG_LIST(VGH_DEF_R)
 VGH_LCFG_LIST(VGH_DEF_L)
 }  // namespace vghcfg

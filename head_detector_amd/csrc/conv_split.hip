@@ -24,59 +24,57 @@
 
 namespace {
 
-constexpr int igemm_lds(int BP, int BC, int WP, int WC, int KBS, int NST) {
-    const int nw = (BP / WP) * (BC / WC);
-    const int loop = NST * KBS * (BP + BC) * 64 + (NST > 2 ? nw * 1024 : 0), epi = nw * 32 * (WC + 4) * 4;
-    return loop > epi ? loop : epi;
-}
-
 struct SplitCfg {
     const char* name;
-    int BP, BC, lds, patch, TW, TH, KBS;
-    void (*launch)(const ConvArgs&, int sp, int ntc, int ntx, int nty, int total, int chunk, int lds, hipStream_t);
+    TileFamily family;  // SplitIgemm, SplitPatch or PingPongF16 (conv_tiles.h)
+    int BP, BC, lds, TW, TH, KBS;
+    VGH_TILE_LAUNCHER((*launch));  // (the plane format is a.split)
 };
 
 template <int BP, int BC, int WP, int WC, int KBS, int NST, int SP>
-void launch_igemm_sp(const ConvArgs& a, int ntc, int total, int chunk, int lds, hipStream_t st) {
+VGH_TILE_LAUNCHER(launch_igemm_sp) {
     static PerDevice opted_in;
     if (lds > 64 * 1024) (void)opt_in_dynamic_lds(opted_in, lds, conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST, SP>, conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, SP>);
-    const dim3 grid(chunk * 8), block((BP / WP) * (BC / WC) * 64);
+    const dim3 grid(g.chunk * 8), block((BP / WP) * (BC / WC) * 64);
     if (a.fast_epi)
-        hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, SP>), grid, block, lds, st, a, ntc, total, chunk);
+        hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 1, NST, SP>), grid, block, lds, st, a, g.ntc, g.total, g.chunk);
     else
-        hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST, SP>), grid, block, lds, st, a, ntc, total, chunk);
+        hipLaunchKernelGGL((conv_igemm_kernel<BP, BC, WP, WC, KBS, 0, NST, SP>), grid, block, lds, st, a, g.ntc, g.total, g.chunk);
+    return VGH_OK;
 }
 template <int BP, int BC, int WP, int WC, int KBS, int NST>
-void launch_igemm(const ConvArgs& a, int sp, int ntc, int, int, int total, int chunk, int lds, hipStream_t st) {
-    if (sp == VGH_FMT_F16X2)
-        launch_igemm_sp<BP, BC, WP, WC, KBS, NST, VGH_FMT_F16X2>(a, ntc, total, chunk, lds, st);
-    else
-        launch_igemm_sp<BP, BC, WP, WC, KBS, NST, VGH_FMT_BF16X2>(a, ntc, total, chunk, lds, st);
+VGH_TILE_LAUNCHER(launch_sp_igemm) {
+    return a.split == VGH_FMT_F16X2 ? launch_igemm_sp<BP, BC, WP, WC, KBS, NST, VGH_FMT_F16X2>(a, g, lds, st) : launch_igemm_sp<BP, BC, WP, WC, KBS, NST, VGH_FMT_BF16X2>(a, g, lds, st);
 }
 
 template <int TW, int TH, int BC, int NWP, int NWC, int SP>
-void launch_patch_sp(const ConvArgs& a, int ntc, int ntx, int nty, int total, int chunk, int lds, hipStream_t st) {
+VGH_TILE_LAUNCHER(launch_patch_sp) {
     static PerDevice per_cu;
     const int n = patch_blocks_per_cu(conv3x3_patch_kernel<TW, TH, BC, NWP, NWC, SP>, NWP * NWC * 64, lds, per_cu);
-    const int gpx = vgh_conv_persistent_blocks_per_xcd(a, chunk, n);  // as the bf16 patch tiles: lane share + vgh_conv_set_max_blocks_per_xcd (multi-tile tests)
-    hipLaunchKernelGGL((conv3x3_patch_kernel<TW, TH, BC, NWP, NWC, SP>), dim3(gpx * 8), dim3(NWP * NWC * 64), lds, st, a, ntc, ntx, nty, total, chunk);
+    const int gpx = vgh_conv_persistent_blocks_per_xcd(a, g.chunk, n);  // as the bf16 patch tiles: lane share + vgh_conv_set_max_blocks_per_xcd (multi-tile tests)
+    hipLaunchKernelGGL((conv3x3_patch_kernel<TW, TH, BC, NWP, NWC, SP>), dim3(gpx * 8), dim3(NWP * NWC * 64), lds, st, a, g.ntc, g.ntx, g.nty, g.total, g.chunk);
+    return VGH_OK;
 }
 template <int TW, int TH, int BC, int NWP, int NWC>
-void launch_patch(const ConvArgs& a, int sp, int ntc, int ntx, int nty, int total, int chunk, int lds, hipStream_t st) {
-    if (sp == VGH_FMT_F16X2)
-        launch_patch_sp<TW, TH, BC, NWP, NWC, VGH_FMT_F16X2>(a, ntc, ntx, nty, total, chunk, lds, st);
-    else
-        launch_patch_sp<TW, TH, BC, NWP, NWC, VGH_FMT_BF16X2>(a, ntc, ntx, nty, total, chunk, lds, st);
+VGH_TILE_LAUNCHER(launch_sp_patch) {
+    return a.split == VGH_FMT_F16X2 ? launch_patch_sp<TW, TH, BC, NWP, NWC, VGH_FMT_F16X2>(a, g, lds, st) : launch_patch_sp<TW, TH, BC, NWP, NWC, VGH_FMT_BF16X2>(a, g, lds, st);
+}
+// the fp16 ping-pong tiles (conv_pp.hip), which size their own LDS
+template <int BC>
+VGH_TILE_LAUNCHER(launch_pp16) {
+    return vgh_launch_conv_pp(a, TileFamily::PingPongF16, BC, g, vgh_conv_max_blocks_per_xcd(), st);
 }
 
 #define SCFG(BP, BC, WP, WC) \
-    { "s" #BP "x" #BC "_w" #WP "x" #WC, BP, BC, igemm_lds(BP, BC, WP, WC, 1, 2), 0, 0, 0, 1, launch_igemm<BP, BC, WP, WC, 1, 2> }
+    { "s" #BP "x" #BC "_w" #WP "x" #WC, TileFamily::SplitIgemm, BP, BC, lds_bytes(BP, BC, WP, WC, 1, 2), 0, 0, 1, launch_sp_igemm<BP, BC, WP, WC, 1, 2> }
 #define SCFGR(BP, BC, WP, WC, KBS, NST) \
-    { "s" #BP "x" #BC "_w" #WP "x" #WC "_k" #KBS "_r" #NST, BP, BC, igemm_lds(BP, BC, WP, WC, KBS, NST), 0, 0, 0, KBS, launch_igemm<BP, BC, WP, WC, KBS, NST> }
+    { "s" #BP "x" #BC "_w" #WP "x" #WC "_k" #KBS "_r" #NST, TileFamily::SplitIgemm, BP, BC, lds_bytes(BP, BC, WP, WC, KBS, NST), 0, 0, KBS, launch_sp_igemm<BP, BC, WP, WC, KBS, NST> }
 #define SPCFG(TW, TH, BC, NWP, NWC) \
-    { "sp" #TH "x" #TW "x" #BC "_n" #NWP "x" #NWC, (TW) * (TH), BC, patch_lds<TW, TH, BC, NWP, NWC>(), 1, TW, TH, 1, launch_patch<TW, TH, BC, NWP, NWC> }
+    { "sp" #TH "x" #TW "x" #BC "_n" #NWP "x" #NWC, TileFamily::SplitPatch, (TW) * (TH), BC, patch_lds<TW, TH, BC, NWP, NWC>(), TW, TH, 1, launch_sp_patch<TW, TH, BC, NWP, NWC> }
+#define PP16CFG(BC) \
+    { "g8x8x" #BC "_n8", TileFamily::PingPongF16, 512, BC, 0, 8, 8, 1, launch_pp16<BC> }
 
-// indices 0..15 are what pick_split_cfg returns; the rest are tuner candidates (tools/tune_conv.py --precision fp16x3)
+// The order is frozen: the first 16 rows are what pick_split_cfg returns by index; the rest are tuner candidates (tools/tune_conv.py --precision fp16x3)
 const SplitCfg g_scfgs[] = {
     SCFG(128, 128, 64, 64),    // 0
     SCFG(128, 96, 32, 96),     // 1
@@ -109,31 +107,16 @@ const SplitCfg g_scfgs[] = {
     SPCFG(16, 16, 256, 4, 4),  // 28
     SPCFG(16, 8, 64, 4, 1),    // 29  128 px x 64: three blocks per CU
     SPCFG(16, 8, 128, 4, 2),   // 30
+    // single-plane fp16 (VGH_FMT_F16, r05): besides the tiles above, the 8-wave ping-pong 3x3 tiles of conv_pp.hip in their fp16 variant, 128 / 96 / 64 couts per
+    // workgroup: the LAST three rows (include/vgh.h says so)
+    PP16CFG(128),
+    PP16CFG(96),
+    PP16CFG(64),
 };
 constexpr int kNumSplitCfgs = sizeof(g_scfgs) / sizeof(g_scfgs[0]);
+constexpr int kFirstPP16 = kNumSplitCfgs - 3;
 
-// single-plane fp16 (VGH_FMT_F16, r05): besides the tiles above, the 8-wave ping-pong 3x3 tiles of conv_pp.hip in their fp16 variant, addressed as the three
-// pseudo-indices kNumSplitCfgs + {0, 1, 2} = 128 / 96 / 64 couts per workgroup
-constexpr int kPPBC[3] = {128, 96, 64};
-const char* const kPPNames[3] = {"g8x8x128_n8", "g8x8x96_n8", "g8x8x64_n8"};
-bool pp16_ok(int cfg, const ConvArgs& a) {
-    const int i = cfg - kNumSplitCfgs;
-    return i >= 0 && i < 3 && a.nseg == 1 && a.split == VGH_FMT_F16X2 && a.ksize == 3 && a.stride == 1 && a.fast_epi && !a.out_f32 && !a.shuffle && !a.grp_cout && a.act != VGH_ACT_SILU &&
-           a.cout_pad % kPPBC[i] == 0 && a.cout_store == a.cout_pad && vgh_conv_pp_fits(a);
-}
-
-bool scfg_ok(int cfg, const ConvArgs& a) {
-    if (cfg >= kNumSplitCfgs) return pp16_ok(cfg, a);
-    if (cfg < 0 || cfg >= kNumSplitCfgs) return false;
-    const SplitCfg& e = g_scfgs[cfg];
-    if (a.cout_pad % e.BC) return false;
-    if (a.grp_cout && a.grp_cout % e.BC) return false;
-    if (e.patch && !(a.ksize == 3 && a.stride == 1 && a.fast_epi && !a.out_f32 && !a.shuffle)) return false;
-    // the accumulators are rescaled between two steps of the K loop: the boundary (2 x the k-blocks of a segment) must fall on a step.  The
-    // ABI-level query has no channel count (cblocks = 0): there only KBS <= 2 is promised, which every segment length satisfies
-    if (e.KBS > 2 && (a.cblocks == 0 || (2 * a.ksize * a.ksize * a.cblocks) % e.KBS)) return false;
-    return true;
-}
+bool scfg_ok(int cfg, const ConvArgs& a) { return cfg >= 0 && cfg < kNumSplitCfgs && tile_admits(g_scfgs[cfg].family, g_scfgs[cfg].BC, g_scfgs[cfg].KBS, a); }
 
 int pick_split_cfg(const ConvArgs& a) {
     const int n = a.grp_cout ? a.grp_cout : a.cout_pad;
@@ -141,8 +124,8 @@ int pick_split_cfg(const ConvArgs& a) {
     // single-plane fp16: the ping-pong tiles where the bf16 table runs them -- 3x3 / stride-1 layers of the maps at least 40 pixels a side (8 x 8 sub-patches tile
     // a 20-wide map badly)
     if (a.nseg == 1 && bc >= 64 && a.W >= 40 && a.H >= 40) {
-        const int c = kNumSplitCfgs + (bc == 128 ? 0 : bc == 96 ? 1 : 2);
-        if (pp16_ok(c, a)) return c;
+        const int c = kFirstPP16 + (bc == 128 ? 0 : bc == 96 ? 1 : 2);
+        if (scfg_ok(c, a)) return c;
     }
     const bool patch_ok = a.ksize == 3 && a.stride == 1 && a.fast_epi && !a.out_f32 && !a.shuffle;
     if (patch_ok && a.W % 16 == 0 && a.H % 16 == 0) return bc == 128 ? 8 : bc == 96 ? 9 : bc == 64 ? 10 : 11;
@@ -193,27 +176,17 @@ float bf16_to_f32_host(uint16_t h) {
     return out;
 }
 
-// [cout_pad][taps][cin] 16-bit values -> the kernel image [kb][cout][slot ^ ((cout>>2)&3)][8] of vgh_pack_conv_weights_host
+// [cout_pad][taps][cin] 16-bit values -> the kernel image of vgh_pack_conv_weights_host
 void pack_image16(const uint16_t* w16, int cout_pad, int ksize, int cin, uint16_t* dst) {
-    const int cblocks = cin / 32, taps = ksize * ksize;
-    for (int tap = 0; tap < taps; ++tap)
-        for (int cb = 0; cb < cblocks; ++cb) {
-            const int kb = tap * cblocks + cb;
-            for (int co = 0; co < cout_pad; ++co) {
-                const uint16_t* src = w16 + ((size_t)co * taps + tap) * cin + cb * 32;
-                uint16_t* d = dst + ((size_t)kb * cout_pad + co) * 32;
-                const int sw = (co >> 2) & 3;
-                for (int chunk = 0; chunk < 4; ++chunk) memcpy(d + (chunk ^ sw) * 8, src + chunk * 8, 16);
-            }
-        }
+    vgh_pack_conv_image(w16, cout_pad, ksize, cin, dst, [](uint16_t v) { return v; });
 }
 
 }  // namespace
 
 int vgh_conv_split_pick(const ConvArgs& a) { return pick_split_cfg(a); }
 
-extern "C" int vgh_conv_split_num_cfgs(void) { return kNumSplitCfgs + 3; }
-extern "C" const char* vgh_conv_split_cfg_name(int cfg) { return (cfg >= 0 && cfg < kNumSplitCfgs) ? g_scfgs[cfg].name : (cfg >= kNumSplitCfgs && cfg < kNumSplitCfgs + 3) ? kPPNames[cfg - kNumSplitCfgs] : "?"; }
+extern "C" int vgh_conv_split_num_cfgs(void) { return kNumSplitCfgs; }
+extern "C" const char* vgh_conv_split_cfg_name(int cfg) { return (cfg >= 0 && cfg < kNumSplitCfgs) ? g_scfgs[cfg].name : "?"; }
 extern "C" int vgh_conv_split_cfg_ok(int cfg, int ksize, int stride, int cout_pad, int fast_epilogue, int shuffle, int grp_cout) {
     ConvArgs a;
     memset(&a, 0, sizeof(a));
@@ -223,7 +196,7 @@ extern "C" int vgh_conv_split_cfg_ok(int cfg, int ksize, int stride, int cout_pa
     a.fast_epi = fast_epilogue;
     a.shuffle = shuffle;
     a.grp_cout = grp_cout;
-    if (cfg >= kNumSplitCfgs) {  // the fp16 ping-pong tiles: single-plane fp16 nets only (the ABI-level query has no tensor sizes: P = 0 passes the 2 GiB rule)
+    if (cfg >= kFirstPP16) {  // the fp16 ping-pong tiles: single-plane fp16 nets only (the ABI-level query has no tensor sizes: P = 0 passes the 2 GiB rule)
         a.nseg = 1;
         a.split = VGH_FMT_F16X2;
         a.cout_store = cout_pad;
@@ -289,19 +262,10 @@ int vgh_launch_conv_split(const ConvArgs& a0, int force_cfg, hipStream_t stream)
     VGH_REQUIRE((int64_t)a.B * a.H * a.W * a.in_pitch * 2 < (1ll << 31), "conv_split: input tensor (both planes) must stay below 2 GiB; run the batch in chunks");
     int cfg = (force_cfg >= 0 && scfg_ok(force_cfg, a)) ? force_cfg : (a.fallback_cfg1 > 0 && scfg_ok(a.fallback_cfg1 - 1, a)) ? a.fallback_cfg1 - 1 : pick_split_cfg(a);
     VGH_REQUIRE(scfg_ok(cfg, a), "conv_split: no tile for cout_pad=%d k=%d s=%d grp=%d", a.cout_pad, a.ksize, a.stride, a.grp_cout);
-    if (cfg >= kNumSplitCfgs) return vgh_launch_conv_pp(a, kPPBC[cfg - kNumSplitCfgs], 1, vgh_conv_max_blocks_per_xcd(), stream);  // fp16 ping-pong tiles (conv_pp.hip)
     const SplitCfg& e = g_scfgs[cfg];
-    const int ntc = a.cout_pad / e.BC;
-    if (e.patch) {
-        const int ntx = (a.W + e.TW - 1) / e.TW, nty = (a.H + e.TH - 1) / e.TH;
-        const int64_t total = (int64_t)a.B * nty * ntx * ntc;
-        VGH_REQUIRE(total < (1ll << 30), "conv_split: too many tiles");
-        e.launch(a, a.split, ntc, ntx, nty, (int)total, (int)((total + 7) / 8), e.lds, stream);
-    } else {
-        const int64_t total = (((int64_t)a.P + e.BP - 1) / e.BP) * ntc;
-        VGH_REQUIRE(total < (1ll << 30), "conv_split: too many tiles");
-        e.launch(a, a.split, ntc, 0, 0, (int)total, (int)((total + 7) / 8), e.lds, stream);
-    }
+    TileGrid grid;
+    VGH_REQUIRE(tile_grid(e.family, e.BP, e.BC, e.TW, e.TH, a, &grid), "conv_split: too many tiles");
+    if (int rc = e.launch(a, grid, e.lds, stream)) return rc;
     VGH_HIP(hipGetLastError());
     return VGH_OK;
 }

@@ -979,68 +979,39 @@ int launch_dt(const ConvArgs& a, const StemArgs& sa, hipStream_t st) {
 
 }  // namespace
 
-// the pair a (3x3 / stride 2 / pad 1, 48 real input channels at a 48-channel pitch declared as cin = 64, 96 couts) -> 1x1 with 128 / 192 couts, on a map of whole 8 x 8 tiles
-int vgh_conv_ds_b2b_ok(const ConvArgs& a) {
-    return a.ksize == 3 && a.stride == 2 && a.pad == 1 && a.cin == 64 && a.in_pitch == 48 && a.in_coff % 8 == 0 && a.cout_pad == 96 && a.cout_store == 96 && (a.cout2_pad == 128 || a.cout2_pad == 192) && a.cout2_store == a.cout2_pad &&
-           a.H == 2 * a.Ho && a.W == 2 * a.Wo && a.Ho % 8 == 0 && a.Wo % 8 == 0 && (int64_t)a.W * a.in_pitch * 2 * 20 < (1ll << 30) && !a.split && !a.res && !a.shuffle && !a.grp_cout &&
-           !a.in_fp8 && !a.out_fp8 && !a.out_f32 && a.act != VGH_ACT_SILU && a.act2 != VGH_ACT_SILU;
-}
-
-
-// plain 3x3 / stride-2 / pad-1 conv, 96 input channels, whole 96-cout workgroup tiles, a map of whole 8 x 8 tiles ("r" tile)
-int vgh_conv_ds_ok(const ConvArgs& a) {
-    return a.ksize == 3 && a.stride == 2 && a.pad == 1 && a.cin == 96 && a.in_pitch % 8 == 0 && a.in_pitch >= 96 && a.in_coff % 8 == 0 && a.cout_pad % 96 == 0 && a.cout_pad <= 192 &&
-           a.cout_store == a.cout_pad && (a.out_split >= a.cout_pad || a.out_split % 16 == 0) && a.out_coff % 8 == 0 && a.out_coff2 % 8 == 0 && a.out_pitch % 8 == 0 && a.H == 2 * a.Ho &&
-           a.W == 2 * a.Wo && a.Ho % 8 == 0 && a.Wo % 8 == 0 && (int64_t)a.W * a.in_pitch * 2 * 20 < (1ll << 30) && (int64_t)a.Wo * a.out_pitch * 2 * 9 < (1ll << 30) && !a.split && !a.res &&
-           !a.shuffle && !a.grp_cout && !a.in_fp8 && !a.out_fp8 && !a.out_f32 && a.act != VGH_ACT_SILU && !a.w2pack;
-}
-
-int vgh_launch_conv_ds(const ConvArgs& a, hipStream_t st) {
+int vgh_launch_conv_ds(const ConvArgs& a, const TileGrid& g, hipStream_t st) {
     VGH_REQUIRE(vgh_conv_ds_ok(a), "conv: not a 96-channel stride-2 conv on whole 8 x 8 tiles (the r tile)");
     static PerDevice opted_in;
     VGH_HIP(opt_in_dynamic_lds(opted_in, DR_LDS, ds_conv_kernel));
-    const int nsx = a.Wo / 8, nsy = a.Ho / 8, per = nsx * nsy, nh = a.cout_pad / 96;
-    const int64_t total = (int64_t)a.B * per * nh;
-    VGH_REQUIRE(total < (1ll << 30), "conv: too many tiles");
+    const int nsx = g.ntx, per = g.ntx * g.nty, nh = g.ntc, total = g.total;
     const auto [chunk, gpx] = persistent_grid(a, total, nh);  // nh = 1 or 2: even chunks, item parity = cout half
     DtDiv dv;
     vgh_fastdiv_magic((unsigned)per, &dv.m_per, &dv.s_per);
     vgh_fastdiv_magic((unsigned)nsx, &dv.m_nsx, &dv.s_nsx);
-    hipLaunchKernelGGL(ds_conv_kernel, dim3(gpx * 8), dim3(256), DR_LDS, st, a, nsx, per, (int)total, chunk, dv, nh);
+    hipLaunchKernelGGL(ds_conv_kernel, dim3(gpx * 8), dim3(256), DR_LDS, st, a, nsx, per, total, chunk, dv, nh);
     VGH_HIP(hipGetLastError());
     return VGH_OK;
 }
 
-// 3x3 / stride-1 / pad-1 conv with 96 (-> cout_pad a multiple of 96) or 128 (-> a multiple of 128) input channels on a map of whole 8 x 8 tiles ("w" tile)
-int vgh_conv_w_ok(const ConvArgs& a) {
-    const int ncg = a.cin == 96 ? 3 : a.cin == 128 ? 4 : 0;
-    return ncg && a.ksize == 3 && a.stride == 1 && a.pad == 1 && a.in_pitch % 8 == 0 && a.in_coff % 8 == 0 && a.cout_pad % (32 * ncg) == 0 && a.cout_pad <= 1024 && a.cout_store == a.cout_pad &&
-           (a.out_split >= a.cout_pad || a.out_split % 16 == 0) && a.out_coff % 8 == 0 && a.out_coff2 % 8 == 0 && a.out_pitch % 8 == 0 && a.Ho == a.H && a.Wo == a.W && a.H % 8 == 0 && a.W % 8 == 0 &&
-           (int64_t)a.W * a.in_pitch * 2 * 12 < (1ll << 30) && (int64_t)a.Wo * a.out_pitch * 2 * 9 < (1ll << 30) && (!a.res || ((int64_t)a.Wo * a.res_pitch * 2 * 9 < (1ll << 30) && a.res_pitch % 4 == 0 && a.res_coff % 4 == 0)) &&
-           !a.split && !a.shuffle && !a.grp_cout && !a.in_fp8 && !a.out_fp8 && !a.out_f32 && a.act != VGH_ACT_SILU && !a.w2pack;
-}
-
 template <int CIN16, int NCG, int RES>
-static int launch_w(const ConvArgs& a, hipStream_t st) {
+static int launch_w(const ConvArgs& a, const TileGrid& g, hipStream_t st) {
     using G = WGeo<CIN16>;
     static PerDevice opted_in;
     VGH_HIP(opt_in_dynamic_lds(opted_in, G::LDS, w_conv_kernel<CIN16, NCG, RES>));
-    const int nsx = a.Wo / 8, nsy = a.Ho / 8, per = nsx * nsy, nh = a.cout_pad / (32 * NCG);
-    const int64_t total = (int64_t)a.B * per * nh;
-    VGH_REQUIRE(total < (1ll << 30), "conv: too many tiles");
+    const int nsx = g.ntx, per = g.ntx * g.nty, nh = g.ntc, total = g.total;  // nh = cout_pad / (32 * NCG): cin is the tile's BC (tile_admits)
     const auto [chunk, gpx] = persistent_grid(a, total, nh);
     DtDiv dv;
     vgh_fastdiv_magic((unsigned)per, &dv.m_per, &dv.s_per);
     vgh_fastdiv_magic((unsigned)nsx, &dv.m_nsx, &dv.s_nsx);
-    hipLaunchKernelGGL((w_conv_kernel<CIN16, NCG, RES>), dim3(gpx * 8), dim3(64 * NCG), G::LDS, st, a, nsx, per, (int)total, chunk, dv, nh);
+    hipLaunchKernelGGL((w_conv_kernel<CIN16, NCG, RES>), dim3(gpx * 8), dim3(64 * NCG), G::LDS, st, a, nsx, per, total, chunk, dv, nh);
     VGH_HIP(hipGetLastError());
     return VGH_OK;
 }
 
-int vgh_launch_conv_w(const ConvArgs& a, hipStream_t st) {
+int vgh_launch_conv_w(const ConvArgs& a, const TileGrid& g, hipStream_t st) {
     VGH_REQUIRE(vgh_conv_w_ok(a), "conv: not a 96 / 128-channel 3x3 stride-1 conv on whole 8 x 8 tiles (the w tile)");
-    if (a.cin == 96) return a.res ? launch_w<6, 3, 1>(a, st) : launch_w<6, 3, 0>(a, st);
-    return a.res ? launch_w<8, 4, 1>(a, st) : launch_w<8, 4, 0>(a, st);
+    if (a.cin == 96) return a.res ? launch_w<6, 3, 1>(a, g, st) : launch_w<6, 3, 0>(a, g, st);
+    return a.res ? launch_w<8, 4, 1>(a, g, st) : launch_w<8, 4, 0>(a, g, st);
 }
 
 // `a` prepared, with its b2b fields set and checked by vgh_launch_conv_b2b

@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/vgh.h"
+#include "conv_tiles.h"  // ConvArgs (conv_args.h), the tile families and their admission rule
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_t;
@@ -33,66 +34,6 @@ void vgh_set_error(const char* fmt, ...);
         }                                 \
     } while (0)
 
-// ---- conv launch descriptor (device pointers resolved) ---------------------------------
-struct ConvArgs {
-    const uint16_t* in;    // bf16 NHWC, pixel pitch in_pitch elements, first channel in_coff
-    const uint16_t* wpack; // packed weights [nkb][cout_pad][32] bf16, 16B chunks pre-swizzled
-    const float* bias;     // [cout_pad]
-    void* out;             // bf16 (or f32 when out_f32) NHWC
-    const uint16_t* res;   // residual, same spatial dims as out (or nullptr)
-    const uint16_t* zeros; // >= 64 B of zeros (im2col padding source)
-    int64_t in_pitch, out_pitch, res_pitch;
-    int in_coff, out_coff, out_coff2, out_split, res_coff;
-    int B, H, W, Ho, Wo;
-    int cin;        // multiple of 32
-    int cout_pad;   // rows in wpack (multiple of 32)
-    int cout_store; // channels actually written (<= cout_pad)
-    int ksize, stride, pad;
-    int act;        // VGH_ACT_*
-    int out_f32;    // 1: write float
-    int shuffle;    // 1: ConvTranspose2d(k=2,s=2) pixel-shuffle store, cout_pad = 4*C
-    int shuffle_c;  // C of the transposed conv
-    float alpha;    // residual scale
-    int P;          // B*Ho*Wo output pixels
-    int nkb;        // ksize*ksize*cin/32
-    int cblocks;    // cin/32
-    unsigned div_howo_m, div_howo_s, div_wo_m, div_wo_s;  // n / d == (umulhi(n, m) + n) >> s for n < 2^30 (filled by vgh_launch_conv)
-    int fast_epi;   // 1: LDS-transposed 16-byte epilogue (bf16 out, 8-channel aligned offsets)
-    int stagger;    // persistent patch kernels: odd resident-slot blocks start this many ~0.5 us sleeps late (de-phases co-resident blocks)
-    int grid_share; // persistent patch kernels: take 1/grid_share of the CU slots (the executor's other lane streams own the rest)
-    // ---- grouped convolution (block-diagonal launch of sibling branches): cout tile c0 belongs to group c0 / grp_cout and reads its
-    //      input channels at in_coff + group * grp_in_stride; every row of wpack holds that group's cin = a.cin channels ----
-    int grp_cout, grp_in_stride;  // 0: dense
-    // ---- split-precision parity modes (conv_split.hip): activations are two 16-bit planes per pixel [hi C | lo C] and the K loop runs
-    //      three segments x_hi*w_lo, x_lo*w_hi (corrections), then -- after one multiply of the accumulators by acc_scale -- x_hi*w_hi ----
-    int split;        // VGH_FMT_BF16 (0): plain; VGH_FMT_BF16X2 / VGH_FMT_F16X2: hi|lo planes
-    int in_plane, out_plane, res_plane;  // elements from a pixel's hi plane to its lo plane (the buffer's logical pitch)
-    int seg_kb;       // k-blocks per segment = ksize^2 * cblocks (nkb = nseg * seg_kb)
-    int nseg;         // 3: the split modes' x_hi*w_lo, x_lo*w_hi, x_hi*w_hi; 1: the single-plane fp16 format (VGH_FMT_F16, r05) rides the F16X2 kernels with its one
-                      //    plane as "hi" (split = VGH_FMT_F16X2, in/out/res_plane = 0, acc_scale = 0: no lo plane is read or written) and the [w_hi] weight image
-    float acc_scale;  // 1/2048 (fp16: lo planes are stored scaled by 2^11) or 1 (bf16)
-    float lo_scale;   // lo = (v - hi) * lo_scale
-    float out_scale;  // undoes the per-op power-of-two weight prescale (fp16), applied to the accumulator before the bias
-    // ---- e4m3 links (conv_pp.hip, r05): the input view / the output tensor hold OCP e4m3 bytes (pitches and channel offsets then count bytes); the residual stays
-    //      bf16.  gscale[cout_pad]: per-cout output factor applied to the accumulator (which starts at bias / gscale when the input is e4m3) ----
-    //      in_fp8 / out_fp8: 0 = 16-bit, 1 = e4m3, 2 = int8 (VGH_FMT_I8: the `bias` vector of an int8-INPUT conv holds int32 BIT PATTERNS in accumulator units,
-    //      rn(bias[c] / (wscale[c] * scale(in))); the int32 accumulator starts there and out = act(float(acc) * gscale[c]) -- include/vgh.h, conv_pp.hip PP_INIT_ROWS) ----
-    int in_fp8, out_fp8;
-    const float* gscale;
-    const float* dvec;  // int8 -> bf16 only (or nullptr): the diagonal bypass, out[c] += dvec[c] * code(input pixel, channel c) before the activation (conv_pp.hip DG)
-    float bias_scale;  // fp16 ping-pong variant: 1 / out_scale (set by vgh_launch_conv_pp)
-    int fallback_cfg1;  // 0: a forced tile that cannot run this conv is an error; k + 1: it falls back to tile k (network executor: a table may be stale)
-    int nt_out;          // bf16 output stores carry the non-temporal hint (set by vgh_conv_prepare from vgh_conv_set_nt_store)
-    // ---- back-to-back GEMM (r06, conv_kernels.inc T2 > 0): this conv's output tile feeds a 1x1 / stride-1 conv inside the same launch; only that conv's output is stored ----
-    const uint16_t* w2pack;  // the second conv's packed weights [cout_pad / 32][cout2_pad][32] (vgh_pack_conv_weights_host), or nullptr
-    const float* bias2;      // [cout2_pad]
-    void* out2;              // the second conv's output tensor (bf16 NHWC), pitch / offsets / split / stored channels as for `out`
-    int64_t out2_pitch;
-    int out2_coff, out2_coff2, out2_split, cout2_pad, cout2_store, act2;
-    int b2b_igemm;           // 1: keep the pair on the implicit-GEMM b2b tile even where the persistent t tile (ds_b2b.hip) could run it (vgh_net_set_b2b(n, 2): A/B, tests)
-    int ablate;     // -DVGH_EXPERIMENTS builds only: bit0 skip tile loads, bit1 skip MFMAs, bit3 skip the epilogue (results are garbage)
-    unsigned long long* trace;  // -DVGH_EXPERIMENTS builds only: per-(block, tile) phase timestamps (s_memtime), or nullptr
-};
 #define VGH_TRACE_TILES 16  // tiles recorded per block
 #define VGH_TRACE_MARKS 4   // marks per tile: tile top, operands landed, K loop done, epilogue done
 
@@ -137,18 +78,16 @@ int vgh_nms_select(const float* boxes_dev, const float* scores_dev, const float*
                    int32_t* head_image_dev, int32_t* n_heads_dev, int32_t* ticket_dev, const vgh_head_level* lazy_levels, int n_levels, const int32_t* lazy_idx_dev,
                    int shape_c, int expr_c, void* stream);  // lazy_idx_dev != null: flame_dev is not read, the survivors' vectors come from the prediction buffers
 int vgh_launch_conv(const ConvArgs& a, int force_cfg, hipStream_t stream);
+// the ONE launcher type of both tile tables (conv_igemm.hip, conv_split.hip): the prepared launch, its tile counts (tile_grid), the dynamic LDS of the table row, the stream
+#define VGH_TILE_LAUNCHER(name) int name(const ConvArgs& a, const TileGrid& g, int lds, hipStream_t st)
 // conv_igemm.hip: `a` with its b2b fields set (w2pack ...): the fused launch, or VGH_ERR_INVALID when the pair does not fit a b2b tile (vgh_conv_b2b_ok says so beforehand)
 int vgh_launch_conv_b2b(const ConvArgs& a, hipStream_t stream);
-int vgh_conv_b2b_ok(int ksize, int stride, int cout_pad, int cout2_pad);
 // ds_b2b.hip ("t" tile): the stage-1 downsample + conv1|conv2 pair as one persistent launch with register-resident weights; `a` prepared, b2b fields set
-int vgh_conv_ds_b2b_ok(const ConvArgs& a);
 int vgh_launch_conv_ds_b2b(const ConvArgs& a, hipStream_t stream);
-// ("r" tile) a plain 3x3 / stride-2 conv with 96 input channels in the same execution structure; `a` prepared
-int vgh_conv_ds_ok(const ConvArgs& a);
-int vgh_launch_conv_ds(const ConvArgs& a, hipStream_t stream);
-// ("w" tile) 3x3 / stride-1 convs with 96 / 128 input channels, weights resident in registers; `a` prepared
-int vgh_conv_w_ok(const ConvArgs& a);
-int vgh_launch_conv_w(const ConvArgs& a, hipStream_t stream);
+// ("r" tile) a plain 3x3 / stride-2 conv with 96 input channels in the same execution structure; `a` prepared, `g` its tile_grid
+int vgh_launch_conv_ds(const ConvArgs& a, const TileGrid& g, hipStream_t stream);
+// ("w" tile) 3x3 / stride-1 convs with 96 / 128 input channels, weights resident in registers; `a` prepared, `g` its tile_grid
+int vgh_launch_conv_w(const ConvArgs& a, const TileGrid& g, hipStream_t stream);
 // ("u" tile) the same with the stem conv in the launch: u8 NHWC images in, the stem tensor never exists; `a` = the pair (b2b fields set, not yet prepared)
 int vgh_launch_stem_ds_b2b(const ConvArgs& a, const void* image_u8, int Hi, int Wi, const float* wstem, const float* bstem, hipStream_t stream);
 int vgh_launch_conv_split(const ConvArgs& a, int force_cfg, hipStream_t stream);  // conv_split.hip: a.split = VGH_FMT_BF16X2 / VGH_FMT_F16X2
@@ -164,11 +103,10 @@ void vgh_pack_conv_weights_fp8_host(const float* w, int cout_pad, int ksize, int
 void vgh_pack_conv_weights_i8_host(const float* w, int cout_pad, int ksize, int cin, uint8_t* dst, float* wscale);
 static inline int vgh_fmt_is_q8(int fmt) { return fmt == VGH_FMT_FP8 || fmt == VGH_FMT_I8; }    // an 8-bit link format
 static inline int vgh_fmt_q8_kind(int fmt) { return fmt == VGH_FMT_FP8 ? 1 : fmt == VGH_FMT_I8 ? 2 : 0; }  // ConvArgs::in_fp8 / out_fp8 code
-// conv_pp.hip: the 8-wave ping-pong 3x3 / stride-1 tiles ("g" tiles; bc = 128 / 96 / 64 couts per workgroup); `a` must be prepared
-int vgh_launch_conv_pp(const ConvArgs& a, int bc, int version /* 1: "g" (two barriers per tap), 2: "h" (one), 3: "s" (g with two 4 x 8 sub-patches per wave) */, int max_blocks_per_xcd, hipStream_t stream);
+// conv_pp.hip: the 8-wave ping-pong 3x3 / stride-1 tiles (family PingPongG / H / S, or PingPongF16; bc = 128 / 96 / 64 couts per workgroup); `a` prepared, `g` its tile_grid
+int vgh_launch_conv_pp(const ConvArgs& a, TileFamily family, int bc, const TileGrid& g, int max_blocks_per_xcd, hipStream_t stream);
 int vgh_conv_pp_lds(int bc);
 int vgh_conv_max_blocks_per_xcd();  // the process-wide cap of vgh_conv_set_max_blocks_per_xcd (0 = none)
-int vgh_conv_pp_fits(const ConvArgs& a);
 int vgh_conv_persistent_blocks_per_xcd(const ConvArgs& a, int chunk, int blocks_per_cu);
 int vgh_conv_pick_cfg(const ConvArgs& a);
 int vgh_conv_cfg_ok_for(int cfg, const ConvArgs& a);  // `a` prepared; bf16 tiles only (split launches validate in conv_split.hip)
@@ -179,6 +117,25 @@ int vgh_conv_pick_auto(const ConvArgs& a);
 int vgh_conv_split_pick(const ConvArgs& a);
 // host-side weight packing: dense [cout_pad][ks][ks][cin] f32 -> wpack bf16 image
 void vgh_pack_conv_weights_host(const float* w, int cout_pad, int ksize, int cin, uint16_t* dst);
+// the packing loop of every 16-bit weight image: dense [cout_pad][ks][ks][cin] -> dst[kb][cout][slot][8] with slot = chunk ^ ((cout>>2)&3), kb = (ky*ks + kx)*(cin/32) + cb,
+// every element through `cvt` (fp32 -> bf16 for vgh_pack_conv_weights_host, the identity for conv_split.hip's planes that are 16-bit already)
+template <class Src, class Cvt>
+static inline void vgh_pack_conv_image(const Src* w, int cout_pad, int ksize, int cin, uint16_t* dst, Cvt cvt) {
+    const int cblocks = cin / 32, taps = ksize * ksize;
+    for (int tap = 0; tap < taps; ++tap)
+        for (int cb = 0; cb < cblocks; ++cb) {
+            const int kb = tap * cblocks + cb;
+            for (int co = 0; co < cout_pad; ++co) {
+                const Src* src = w + ((size_t)co * taps + tap) * cin + cb * 32;
+                uint16_t* d = dst + ((size_t)kb * cout_pad + co) * 32;
+                const int sw = (co >> 2) & 3;
+                for (int chunk = 0; chunk < 4; ++chunk) {
+                    const int slot = chunk ^ sw;
+                    for (int e = 0; e < 8; ++e) d[slot * 8 + e] = cvt(src[chunk * 8 + e]);
+                }
+            }
+        }
+}
 static inline size_t vgh_wpack_elems(int cout_pad, int ksize, int cin) { return (size_t)cout_pad * ksize * ksize * cin; }
 
 static inline void vgh_fastdiv_magic(unsigned d, unsigned* m, unsigned* s) {

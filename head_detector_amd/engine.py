@@ -642,6 +642,7 @@ def tile_can_run(lib, program: "arch.Program", precision: str, cfg: int, op: dic
         return bool(lib.vgh_conv_split_cfg_ok(cfg, op["ksize"], op["stride"], op["cout_pad"], fast, op["shuffle"], op.get("grp_cout", 0)))
     if not lib.vgh_conv_cfg_ok(cfg, op["ksize"], op["stride"], op["cout_pad"], fast, op["shuffle"]):
         return False
+    # the three launch-level clauses of csrc/conv_tiles.h (tile_admits) restated by name prefix: Stream (dense_relu_16bit, no residual), PingPongG / H / S (dense_relu_16bit), grp_cout % BC
     if names[cfg].startswith("t") and (op.get("res_buf", -1) >= 0 or op.get("grp_cout") or op.get("act") == 2):
         return False  # streaming 1x1 tiles: plain bf16 -> bf16 convs only (the executor would fall back to another tile)
     if names[cfg][0] in "ghs" and (op.get("grp_cout") or op.get("act") == 2):
