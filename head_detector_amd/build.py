@@ -27,8 +27,9 @@ class Companion(NamedTuple):
 HOST_HEADERS = ["companion_host.h"]  # the host plumbing of every companion (codes, message, check macros, staging, queue-then-record): header-only
 RASTER_HEADERS = HOST_HEADERS + ["tile_fold.h"]  # the tile-major triangle fold: header-only, compiled into each of the three libraries that rasterise
 COMPANIONS = [  # built in this order, before the core
-    # mesh benchmark metrics (Z_n, chamfer): float64 distances in a stated operation order, so no contraction into fused multiply-adds anywhere in this library
-    Companion("libvgheval.so", ["mesh_metrics.hip"], HOST_HEADERS, "vgh_eval.h", ["-ffp-contract=off"], "build_eval"),
+    # benchmark metrics, mesh (Z_n, chamfer) and detection (COCO-style box AP): float64 in a stated operation order, so no contraction into fused
+    # multiply-adds anywhere in this library
+    Companion("libvgheval.so", ["mesh_metrics.hip", "detection_ap.hip"], HOST_HEADERS, "vgh_eval.h", ["-ffp-contract=off"], "build_eval"),
     Companion("libvghtex.so", ["texture.hip"], RASTER_HEADERS, "vgh_tex.h", [], "build_tex"),  # head textures (Sim3DR's render_texture)
     Companion("libvghvis.so", ["visibility.hip"], RASTER_HEADERS, "vgh_vis.h", [], "build_vis"),  # head visibility buffers
     Companion("libvghview.so", ["aligned.hip", "draw.hip", "mesh_render.hip"], RASTER_HEADERS, "vgh_view.h", [], "build_view"),  # result-side image helpers

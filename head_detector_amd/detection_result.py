@@ -13,7 +13,8 @@ triangle that show, per head the covered and the visible pixels and the visible 
 and the heads' surface with Sim3DR's ``render_texture`` (csrc/texture.hip, libvghtex.so, ``head_detector_amd.texture``): the first cuts every head's UV
 texture map out of the image, the second paints textures back onto the heads; both need ``faces`` and a per-vertex UV layout (``texture.cylindrical_uv``
 makes one from the template mesh).  ``compare_meshes`` judges the heads against ground-truth meshes with the reference's benchmark metrics (Z_n, chamfer;
-csrc/mesh_metrics.hip, libvgheval.so, ``head_detector_amd.mesh_metrics``)."""
+csrc/mesh_metrics.hip, libvgheval.so, ``head_detector_amd.mesh_metrics``).  ``detection_rows`` gives the boxes as the detection benchmarks take them
+(``head_detector_amd.detection_metrics``: COCO-style AP, csrc/detection_ap.hip)."""
 from __future__ import annotations
 
 import os
@@ -96,6 +97,11 @@ class PredictionResult:
 
         return compare_heads(self.heads, gt_vertices, subset=subset, top_k=top_k, neighbours=neighbours, gt_landmarks7=gt_landmarks7,
                              pred_landmarks7=pred_landmarks7, chamfer_subset=chamfer_subset, to_host=to_host)
+
+    def detection_rows(self) -> list:
+        """``[[x, y, w, h, score], ...]`` of ``heads``, in their order: the rows the reference's detection benchmarks hand to COCOeval
+        (evaluation/evaluate_wider.py: parse_predictions) and ``detection_metrics.DetectionEvaluator.add`` takes."""
+        return [[head.bbox.x, head.bbox.y, head.bbox.w, head.bbox.h, float(head.score)] for head in self.heads]
 
     def get_pncc(self):
         """detection_result.py:58-59: PNCC image of all heads (uint8 [H,W,3]); like the reference it negates z of every

@@ -17,7 +17,9 @@ check prints PASS / FAIL / SKIPPED with the number behind it, and the exit code 
                        the time that loop takes for the same heads.
   4. --images + weights (+ --pkl): bf16 / fp16 / int8 / fp8 against the fp16x3 parity mode on those photographs -- dense boxes IoU, scores, the kept detections'
                        parameters and vertices; int8 / fp8 calibrated on the same photographs.
-GPU needed for 2 - 4 (the library has no CPU path)."""
+  5. pycocotools     : wherever that package is installed, detection_metrics.average_precision (csrc/detection_ap.hip) against COCOeval(..., 'bbox') itself on a seeded set
+                       written the way the reference's evaluate_wider.py / evaluate_fddb.py write it: precision, recall, scores and the twelve stats, bit for bit.
+GPU needed for 2 - 5 (the library has no CPU path)."""
 import argparse
 import os
 import sys
@@ -246,6 +248,53 @@ def main():
             print(f"[INFO] {prec} vs fp16x3 on {B} photographs: IoU min over the {int(conf.sum())} anchors with score > 0.5 = {i_min:.5f}; max |score diff| {s_err:.2e}", flush=True)
     else:
         skipped("precision modes on photographs", "needs weights, --images and a GPU")
+    # ---- 5. detection AP against pycocotools itself ----
+    try:
+        from pycocotools.coco import COCO
+        from pycocotools.cocoeval import COCOeval
+    except ImportError:
+        COCO = None
+    if COCO is None or not gpu:
+        skipped("average_precision vs pycocotools", "needs pycocotools and a GPU")
+    else:
+        import contextlib
+        import io
+
+        from head_detector_amd import detection_metrics as dm
+
+        rng = np.random.default_rng(7)
+        gts, dts = [], []
+        for ng in (0, 1, 3, 17, 64, 65, 130, 2, 40, 9):
+            side = rng.choice([6, 12, 24, 32, 48, 96, 160], ng)
+            gt = np.stack([rng.integers(0, 600, ng), rng.integers(0, 400, ng), side, side], axis=1).reshape(ng, 4)
+            found = gt[rng.random(ng) < 0.8]  # integer boxes, as parse_predictions makes them
+            found = found + rng.integers(-2, 3, found.shape)
+            false = np.stack([rng.integers(0, 600, 30), rng.integers(0, 400, 30), rng.integers(1, 90, 30), rng.integers(1, 90, 30)], axis=1)
+            boxes = np.concatenate([found, false]).astype(np.float64)
+            boxes[:, 2:] = np.maximum(boxes[:, 2:], 1)
+            gts.append(gt.astype(np.float64))
+            dts.append(np.concatenate([boxes, rng.integers(1, 100, (len(boxes), 1)) / 100.0], axis=1))
+        gt_json = {"images": [{"id": i + 1} for i in range(len(gts))], "categories": [{"id": 1, "name": "object"}], "annotations": []}
+        for i, gt in enumerate(gts):
+            for x, y, w, h in gt.tolist():
+                gt_json["annotations"].append({"id": len(gt_json["annotations"]) + 1, "image_id": i + 1, "category_id": 1, "bbox": [x, y, w, h], "area": w * h, "iscrowd": 0})
+        dt_json = [{"image_id": i + 1, "category_id": 1, "bbox": row[:4], "score": row[4]} for i, dt in enumerate(dts) for row in dt.tolist()]
+        try:
+            with contextlib.redirect_stdout(io.StringIO()):
+                coco_gt = COCO()
+                coco_gt.dataset = gt_json
+                coco_gt.createIndex()
+                coco_eval = COCOeval(coco_gt, coco_gt.loadRes(dt_json), "bbox")
+                coco_eval.evaluate()
+                coco_eval.accumulate()
+                coco_eval.summarize()
+            got = dm.average_precision(dts, gts)
+            want_p, want_r, want_s = (coco_eval.eval[k] for k in ("precision", "recall", "scores"))
+            same = (np.array_equal(got.precision, want_p[:, :, 0]), np.array_equal(got.recall, want_r[:, 0]), np.array_equal(got.scores, want_s[:, :, 0]),
+                    np.array_equal(got.stats, coco_eval.stats))
+            report("average_precision vs pycocotools (bit for bit)", all(same), f"precision, recall, scores, stats equal: {same}; AP {got.ap:.6f} against {coco_eval.stats[0]:.6f}")
+        except Exception as e:  # noqa: BLE001
+            report("average_precision vs pycocotools", False, f"{type(e).__name__}: {e}")
     print(f"{len(FAILS)} FAIL(s): {FAILS}")
     return len(FAILS)
 
