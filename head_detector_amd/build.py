@@ -1,4 +1,4 @@
-"""In-tree build of libvgh.so and its companions libvghview.so, libvghvis.so, libvghtex.so and libvgheval.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
+"""In-tree build of libvgh.so and its companions libvghview.so, libvghvis.so, libvghtex.so, libvgheval.so and libvghmerge.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
 from __future__ import annotations
 
 import os
@@ -30,6 +30,8 @@ COMPANIONS = [  # built in this order, before the core
     # benchmark metrics, mesh (Z_n, chamfer) and detection (COCO-style box AP): float64 in a stated operation order, so no contraction into fused
     # multiply-adds anywhere in this library
     Companion("libvgheval.so", ["mesh_metrics.hip", "detection_ap.hip"], HOST_HEADERS, "vgh_eval.h", ["-ffp-contract=off"], "build_eval"),
+    # the cross-tile merge of sliced detection: float32 in a stated operation order, equal bit for bit to its NumPy restatement
+    Companion("libvghmerge.so", ["slice_merge.hip"], HOST_HEADERS, "vgh_merge.h", ["-ffp-contract=off"], "build_merge"),
     Companion("libvghtex.so", ["texture.hip"], RASTER_HEADERS, "vgh_tex.h", [], "build_tex"),  # head textures (Sim3DR's render_texture)
     Companion("libvghvis.so", ["visibility.hip"], RASTER_HEADERS, "vgh_vis.h", [], "build_vis"),  # head visibility buffers
     Companion("libvghview.so", ["aligned.hip", "draw.hip", "mesh_render.hip"], RASTER_HEADERS, "vgh_view.h", [], "build_view"),  # result-side image helpers

@@ -3,6 +3,7 @@
     detector = HeadDetector()                       # model="vgg_heads_l", image_size=640
     predictions = detector(image, confidence_threshold=0.5)
     predictions.heads -> List[HeadMetadata(bbox, score, flame_params, vertices_3d, head_pose)]
+    predictions = detector.detect_sliced(image)     # large photographs: overlapping tiles + the whole image, merged on the device (sliced.py)
 
 Differences that are forced, not chosen:
   * weights: the reference downloads ``okupyn/vgg_heads/<model>.trcd`` from the HF hub (detector.py:25-30).
@@ -303,6 +304,66 @@ class HeadDetector:
                 at += 1
             results.append(PredictionResult(original_image=orig, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc, head_indices=self._head_indices, triangles=self._triangles, face_indices=self._face_indices))
         return results
+
+    def detect_sliced(self, image: Union[str, "np.ndarray", Any], confidence_threshold: float = 0.5, *, tile_sizes: Optional[Sequence[int]] = None, overlap: float = 0.25,
+                      include_full: bool = True, border: float = 2.0, match_thr: float = 0.5, metric: str = "iou", max_heads: int = 1000, return_info: bool = False):
+        """Sliced inference for a photograph much larger than the network input, where ``__call__`` would shrink a small head away: the image is uploaded once and cut
+        into overlapping tiles (``sliced.plan_slices``: ``tile_sizes``, default one size = the network's; ``overlap``; ``include_full`` adds the whole image as tile 0
+        for the heads larger than a tile overlap), the tiles -- pitched sub-views of the photograph on the device, no copy -- go through the network ``max_batch`` at a
+        time, ONE device call merges the per-tile detections into image coordinates (``sliced.merge_tiles``, include/vgh_merge.h: ``border``, ``match_thr``,
+        ``metric``, ``max_heads``), the host reads the head count once, and FLAME decode runs on the merged survivors only, each un-padded with its own tile's row so
+        that the vertices land in image coordinates.  ``border`` and ``overlap`` are API defaults, not tuned values (no real weights exist in this tree to tune them on).
+        Boxes are rint(image-coordinate box) clipped to the image (``sliced.image_boxes``: the heads of the whole-image tile keep ``__call__``'s box, which may reach
+        into the letterbox border); FlameParams are expressed in the convention of a whole-image detection
+        (``sliced.to_whole_image_params``); head pose as ``__call__`` computes it.  With only the whole-image tile (``tile_sizes=()``) the heads are those of
+        ``__call__``.  -> PredictionResult, or (PredictionResult, sliced.SliceInfo) with ``return_info``."""
+        from . import sliced
+
+        original = self._convert_image(image)
+        src = torch.from_numpy(np.ascontiguousarray(original))
+        if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] < 3:
+            raise ValueError(f"detect_sliced expects a uint8 image [H,W,3]; got {src.dtype} {tuple(src.shape)}")
+        if max_heads > self._flame.max_heads:
+            raise ValueError(f"detect_sliced: max_heads={max_heads} exceeds the FLAME layer's capacity of {self._flame.max_heads} heads")
+        H, W, S = int(src.shape[0]), int(src.shape[1]), self._image_size
+        plan = sliced.plan_slices(H, W, S, tile_sizes, overlap, include_full)
+        eng, T = self.model, plan.n_tiles
+        kk = eng.keep_k
+        photo = src.to(self._device, non_blocking=True)
+        f32 = dict(dtype=torch.float32, device=self._device)
+        boxes, scores = torch.empty(T, kk, 4, **f32), torch.empty(T, kk, **f32)
+        params, counts = torch.empty(T, kk, _lib.NUM_FLAME_PARAMS, **f32), torch.empty(T, dtype=torch.int32, device=self._device)
+        for at in range(0, T, self._max_batch):  # the slabs of every chunk side by side on the device
+            rows = plan.tiles[at:at + self._max_batch]
+            det = eng.detect([photo[y:y + h, x:x + w] for x, y, w, h in rows[:, :4].tolist()], confidence_threshold=confidence_threshold, flame=None)
+            for dst, part in ((boxes, det.boxes), (scores, det.scores), (params, det.flame_params), (counts, det.counts)):
+                dst[at:at + len(rows)].copy_(part)
+        merged = sliced.merge_tiles(boxes, scores, counts, plan, border=border, match_thr=match_thr, metric=metric, max_heads=max_heads, want_status=return_info)
+        n = int(merged.n_heads.item())  # the one host read the heads depend on
+        head_row, head_tile = merged.head_row[:n].long(), merged.head_tile[:n].long()
+        survivors = params.view(T * kk, -1)[head_row]
+        P = eng.program
+        if n:  # decode of the merged survivors only, un-padded straight into image coordinates by each head's own tile row
+            unpad = torch.from_numpy(plan.unpad).to(self._device)[head_tile].contiguous()
+            _, _, verts = self._flame.decode(survivors, unpad=unpad, shape_live=P.shape_c, expr_live=P.expr_c, want_vertices=False)
+            verts = verts.cpu().numpy()
+        else:
+            verts = np.zeros((0, self._flame.v_template.shape[0], 3), dtype=np.float32)
+        sc, tile_of = merged.scores[:n].cpu().numpy(), head_tile.cpu().numpy().astype(np.int32)
+        bb = sliced.image_boxes(merged.boxes_full[:n].cpu().numpy(), tile_of, plan)
+        survivors = survivors.detach().cpu()
+        heads = []
+        for i in range(n):
+            fp = FlameParams.from_3dmm(survivors[i].unsqueeze(0))
+            fp.translation, fp.scale = sliced.to_whole_image_params(fp.translation, fp.scale, plan.tiles[tile_of[i]], H, W, S)
+            heads.append(HeadMetadata(bbox=Bbox(x=bb[i, 0], y=bb[i, 1], w=bb[i, 2] - bb[i, 0], h=bb[i, 3] - bb[i, 1]), score=sc[i], flame_params=fp, vertices_3d=verts[i],
+                                      head_pose=calculate_rpy(fp)))
+        result = PredictionResult(original_image=original, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc, head_indices=self._head_indices,
+                                  triangles=self._triangles, face_indices=self._face_indices)
+        if not return_info:
+            return result
+        tally = torch.bincount(merged.status.long(), minlength=len(sliced.STATUS_NAMES)).cpu().tolist()
+        return result, sliced.SliceInfo(plan=plan, head_tile=tile_of, status_counts=dict(zip(sliced.STATUS_NAMES, tally)), n_kept_uncapped=int(merged.n_kept_uncapped.item()))
 
     def __call__(self, image: Union[str, "np.ndarray", Any], confidence_threshold: float = 0.5) -> PredictionResult:
         original_image = self._convert_image(image)

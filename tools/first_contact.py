@@ -19,7 +19,9 @@ check prints PASS / FAIL / SKIPPED with the number behind it, and the exit code 
                        parameters and vertices; int8 / fp8 calibrated on the same photographs.
   5. pycocotools     : wherever that package is installed, detection_metrics.average_precision (csrc/detection_ap.hip) against COCOeval(..., 'bbox') itself on a seeded set
                        written the way the reference's evaluate_wider.py / evaluate_fddb.py write it: precision, recall, scores and the twelve stats, bit for bit.
-GPU needed for 2 - 5 (the library has no CPU path)."""
+  6. --images + weights + --pkl: HeadDetector.detect_sliced (csrc/slice_merge.hip) on those photographs: heads found plain (one letterboxed pass) against sliced
+                       (overlapping tiles + the whole image, merged on the device), with the per-status candidate counts; its border and overlap defaults are untuned.
+GPU needed for 2 - 6 (the library has no CPU path)."""
 import argparse
 import os
 import sys
@@ -248,6 +250,21 @@ def main():
             print(f"[INFO] {prec} vs fp16x3 on {B} photographs: IoU min over the {int(conf.sum())} anchors with score > 0.5 = {i_min:.5f}; max |score diff| {s_err:.2e}", flush=True)
     else:
         skipped("precision modes on photographs", "needs weights, --images and a GPU")
+    # ---- 6. sliced detection on real photographs: heads found plain against sliced ----
+    weights = args.trcd or args.onnx
+    if gpu and sd is not None and args.images and args.pkl:
+        try:
+            hd = det.HeadDetector(args.model, args.image_size, weights=weights, flame_path=args.pkl, max_batch=8)
+            for pth in args.images:
+                plain = hd(pth)
+                cut, info = hd.detect_sliced(pth, return_info=True)
+                print(f"[INFO] {pth}: {len(plain.heads)} heads plain, {len(cut.heads)} sliced ({info.plan.n_tiles} tiles; candidates {info.status_counts}; "
+                      f"{int((info.head_tile != 0).sum())} of the sliced heads come from a tile, not from the whole image)", flush=True)
+            report("detect_sliced on photographs", True, f"{len(args.images)} photographs; border and overlap are untuned defaults")
+        except Exception as e:  # noqa: BLE001
+            report("detect_sliced on photographs", False, f"{type(e).__name__}: {e}")
+    else:
+        skipped("heads found plain vs sliced", "needs weights, --pkl, --images and a GPU")
     # ---- 5. detection AP against pycocotools itself ----
     try:
         from pycocotools.coco import COCO
