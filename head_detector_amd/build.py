@@ -1,4 +1,4 @@
-"""In-tree build of libvgh.so and its companions libvghview.so, libvghvis.so, libvghtex.so, libvgheval.so and libvghmerge.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
+"""In-tree build of libvgh.so and its companions libvghview.so, libvghvis.so, libvghtex.so, libvgheval.so, libvghmerge.so and libvghtrack.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
 from __future__ import annotations
 
 import os
@@ -32,6 +32,8 @@ COMPANIONS = [  # built in this order, before the core
     Companion("libvgheval.so", ["mesh_metrics.hip", "detection_ap.hip"], HOST_HEADERS, "vgh_eval.h", ["-ffp-contract=off"], "build_eval"),
     # the cross-tile merge of sliced detection: float32 in a stated operation order, equal bit for bit to its NumPy restatement
     Companion("libvghmerge.so", ["slice_merge.hip"], HOST_HEADERS, "vgh_merge.h", ["-ffp-contract=off"], "build_merge"),
+    # head tracking across video frames: float32 in a stated operation order, equal bit for bit to its NumPy restatement
+    Companion("libvghtrack.so", ["head_track.hip"], HOST_HEADERS, "vgh_track.h", ["-ffp-contract=off"], "build_track"),
     Companion("libvghtex.so", ["texture.hip"], RASTER_HEADERS, "vgh_tex.h", [], "build_tex"),  # head textures (Sim3DR's render_texture)
     Companion("libvghvis.so", ["visibility.hip"], RASTER_HEADERS, "vgh_vis.h", [], "build_vis"),  # head visibility buffers
     Companion("libvghview.so", ["aligned.hip", "draw.hip", "mesh_render.hip"], RASTER_HEADERS, "vgh_view.h", [], "build_view"),  # result-side image helpers

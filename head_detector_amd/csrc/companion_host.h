@@ -1,5 +1,5 @@
-// The host plumbing of the five companion libraries (libvghview.so: csrc/aligned.hip, csrc/draw.hip, csrc/mesh_render.hip; libvghvis.so: csrc/visibility.hip;
-// libvghtex.so: csrc/texture.hip; libvgheval.so: csrc/mesh_metrics.hip, csrc/detection_ap.hip; libvghmerge.so: csrc/slice_merge.hip): the return codes, the calling thread's error message, the check / require macros of
+// The host plumbing of the six companion libraries (libvghview.so: csrc/aligned.hip, csrc/draw.hip, csrc/mesh_render.hip; libvghvis.so: csrc/visibility.hip;
+// libvghtex.so: csrc/texture.hip; libvgheval.so: csrc/mesh_metrics.hip, csrc/detection_ap.hip; libvghmerge.so: csrc/slice_merge.hip; libvghtrack.so: csrc/head_track.hip): the return codes, the calling thread's error message, the check / require macros of
 // the C entry points, the per-device staging block and the queue-then-record discipline around it.  Host-only, header-only and internal: everything is
 // inline, and the companions are built with -fvisibility=hidden, so the sources of one library share one message and no library exports any of this or
 // sees another's.  Nothing of libvgh.so (csrc/vgh_internal.h) is used here and libvgh.so uses nothing of this.
@@ -13,7 +13,7 @@
 namespace companion {
 
 // ---- error plumbing: never throw across the C ABI -------------------------------------------------------------------------------------------------
-// The codes of the five public headers are the same numbers; every includer static_asserts its own against these.
+// The codes of the six public headers are the same numbers; every includer static_asserts its own against these.
 constexpr int OK = 0, ERR_INVALID = -1, ERR_HIP = -2, ERR_NOMEM = -3;
 
 inline thread_local char g_error[512] = "";  // one per thread and library: an inline variable is one object across the sources of a shared object
