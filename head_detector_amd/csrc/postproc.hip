@@ -66,19 +66,29 @@ __global__ __launch_bounds__(256) void head_decode_kernel(Levels L, int B, int A
 }
 
 // ---- K7: per-image top-k via radix select on a 64-bit composite (score key, ~index) -------------
+// The order of torch.sort(descending=True, stable=True), which is what the reference's top-k is held to: every NaN (either sign, any payload) ranks above +inf,
+// -0.0 == +0.0, equal keys by ascending index.  Key 0 is taken by no score (-inf has 0x007fffff): topk_kernel<.., FILTER> gives it to the rows that fail the filter.
 __device__ __forceinline__ uint32_t float_key(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // order-preserving
+    uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;  // NaN
+    if (u == 0x80000000u) u = 0u;                             // -0.0
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);        // order-preserving
 }
-__device__ __forceinline__ uint64_t composite(float f, int idx) { return ((uint64_t)float_key(f) << 32) | (uint32_t)(~(uint32_t)idx); }
+template <bool FILTER>
+__device__ __forceinline__ uint64_t composite(float f, int idx, float conf) {
+    const uint32_t key = (FILTER && !(f >= conf)) ? 0u : float_key(f);
+    return ((uint64_t)key << 32) | (uint32_t)(~(uint32_t)idx);
+}
 
 // r06 (profiles/r06_latency_trace_l1.txt: 47 us of a 2.0-ms single-image call): (i) RC composites per thread live in registers when the row fits (A <= RC * 1024: the
 // 8 400 anchors of a 640 image; the 33 600 of a 1280 image re-read the scores as before), so the scores are read once instead of once per pass; (ii) the radix
 // select STOPS at the first pass whose selected bin holds exactly the remaining count -- every element of that bin is then selected, the threshold is the bin's lower
 // edge, and with distinct scores that is the 3rd or 4th of the 8 passes (the index bits only matter when the k-th score is tied).  Same selected set, same order.
-template <bool CACHED>
+// FILTER (vgh_topk_nms): a row that fails score >= conf ranks below every row that passes (key 0, ascending index among themselves), so it takes a candidate slot
+// only when fewer than k rows pass -- and the NMS never visits it.  The selected set of passing rows is that of "filter, then top-k".
+template <bool CACHED, bool FILTER>
 __global__ __launch_bounds__(1024) void topk_kernel(const float* __restrict__ scores, int A, int k, int32_t* __restrict__ out_idx,
-                                                    float* __restrict__ out_scores) {
+                                                    float* __restrict__ out_scores, float conf) {
     constexpr int RC = 9;
     __shared__ uint32_t hist[256];
     __shared__ uint64_t s_prefix;
@@ -100,7 +110,7 @@ __global__ __launch_bounds__(1024) void topk_kernel(const float* __restrict__ sc
 #pragma unroll
         for (int r = 0; r < RC; ++r) {
             const int i = tid + r * 1024;
-            cache[r] = i < A ? composite(sc[i], i) : 0ull;  // 0 is below every real composite (its low word would be the index 0xffffffff)
+            cache[r] = i < A ? composite<FILTER>(sc[i], i, conf) : 0ull;  // 0 is below every real composite (its low word would be the index 0xffffffff)
         }
     }
     __syncthreads();
@@ -119,7 +129,7 @@ __global__ __launch_bounds__(1024) void topk_kernel(const float* __restrict__ sc
             }
         } else {
             for (int i = tid; i < A; i += 1024) {
-                const uint64_t c = composite(sc[i], i);
+                const uint64_t c = composite<FILTER>(sc[i], i, conf);
                 const bool match = (pass == 0) || ((c >> (shift + 8)) == (prefix >> (shift + 8)));
                 if (match) atomicAdd(&hist[(c >> shift) & 255], 1u);
             }
@@ -152,7 +162,7 @@ __global__ __launch_bounds__(1024) void topk_kernel(const float* __restrict__ sc
         }
     } else {
         for (int i = tid; i < A; i += 1024) {
-            const uint64_t c = composite(sc[i], i);
+            const uint64_t c = composite<FILTER>(sc[i], i, conf);
             if (c >= T) {
                 const int slot = atomicAdd(&s_count, 1);
                 if (slot < 1024) sel[slot] = c;
@@ -245,25 +255,23 @@ __device__ __forceinline__ bool iou_gt(const float4 a, const float area_a, const
     return ovr > thr;
 }
 
-__global__ __launch_bounds__(1024) void nms_kernel(const float* __restrict__ boxes, const float* __restrict__ scores, int n_in, float conf, float thr,
-                                                   int keep_k, int32_t* __restrict__ keep_idx, int32_t* __restrict__ counts) {
-    __shared__ float4 sb[1024];
-    __shared__ unsigned long long removed[16];
-    __shared__ int s_n;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    if (tid < 16) removed[tid] = 0ull;
-    if (tid == 0) s_n = 0;
-    __syncthreads();
+// The greedy loop of nms_kernel and nms_select_kernel: one 1024-thread block per image, thread t owns candidate row t; `boxes` / `scores` / `keep_row` are the image's.
+// Every row that fails score >= conf (utils.py:174), and every position behind n_in, is marked in `removed` BEFORE the first round: such a row is never visited,
+// never kept and never suppresses anything, wherever it stands.  With scores sorted descending the rows that pass are a prefix -- except for NaN scores, which head
+// vgh_topk's order and fail every filter.  The remaining rows are visited in position order, torchvision's loop.  Writes keep_row[0 .. keep_k) (positions, -1 behind
+// the count) and, where s_keep is given, the kept positions to LDS as well; returns the count (block-uniform).
+__device__ __forceinline__ int greedy_nms(const float* __restrict__ boxes, const float* __restrict__ scores, int n_in, float conf, float thr, int keep_k,
+                                          int32_t* __restrict__ keep_row, float4* sb, unsigned long long* removed, int* s_keep) {
+    const int tid = threadIdx.x;
     bool valid = false;
     if (tid < n_in) {
-        sb[tid] = *(const float4*)(boxes + ((int64_t)b * n_in + tid) * 4);
-        valid = scores[(int64_t)b * n_in + tid] >= conf;  // utils.py:174  (inputs sorted descending => a prefix)
+        sb[tid] = *(const float4*)(boxes + (int64_t)tid * 4);
+        valid = scores[tid] >= conf;
     }
     const unsigned long long bal = __ballot(valid);
-    if ((tid & 63) == 0) atomicAdd(&s_n, __popcll(bal));
+    if ((tid & 63) == 0) removed[tid >> 6] = ~bal;
+    for (int j = tid; j < keep_k; j += 1024) keep_row[j] = -1;
     __syncthreads();
-    const int n = s_n;
-    for (int j = tid; j < keep_k; j += 1024) keep_idx[(int64_t)b * keep_k + j] = -1;
     int kept = 0;
     int i = 0;
     while (kept < keep_k) {
@@ -274,9 +282,12 @@ __global__ __launch_bounds__(1024) void nms_kernel(const float* __restrict__ box
             if (wd == (i >> 6)) free_bits &= ~0ull << (i & 63);
             if (free_bits) nxt = wd * 64 + __ffsll((long long)free_bits) - 1;
         }
-        if (nxt < 0 || nxt >= n) break;
+        if (nxt < 0) break;
         i = nxt;
-        if (tid == 0) keep_idx[(int64_t)b * keep_k + kept] = i;
+        if (tid == 0) {
+            keep_row[kept] = i;
+            if (s_keep) s_keep[kept] = i;
+        }
         ++kept;
         const float4 bi = sb[i];
         float area_i;
@@ -284,18 +295,27 @@ __global__ __launch_bounds__(1024) void nms_kernel(const float* __restrict__ box
 #pragma clang fp contract(off)
             area_i = (bi.z - bi.x) * (bi.w - bi.y);
         }
-        const bool sup = (tid > i) && (tid < n) && iou_gt(bi, area_i, sb[tid < n_in ? tid : 0], thr);
+        const bool sup = (tid > i) && valid && iou_gt(bi, area_i, sb[valid ? tid : 0], thr);
         const unsigned long long m = __ballot(sup);
         __syncthreads();  // everyone has finished scanning `removed` for this round
         if ((tid & 63) == 0 && m) removed[tid >> 6] |= m;
         __syncthreads();
         ++i;
     }
-    if (tid == 0) counts[b] = kept;
+    return kept;
+}
+
+__global__ __launch_bounds__(1024) void nms_kernel(const float* __restrict__ boxes, const float* __restrict__ scores, int n_in, float conf, float thr,
+                                                   int keep_k, int32_t* __restrict__ keep_idx, int32_t* __restrict__ counts) {
+    __shared__ float4 sb[1024];
+    __shared__ unsigned long long removed[16];
+    const int b = blockIdx.x;
+    const int kept = greedy_nms(boxes + (int64_t)b * n_in * 4, scores + (int64_t)b * n_in, n_in, conf, thr, keep_k, keep_idx + (int64_t)b * keep_k, sb, removed, nullptr);
+    if (threadIdx.x == 0) counts[b] = kept;
 }
 
 // r06 (single-image latency: profiles/r06_latency_trace_l1.txt shows nms -> compact -> head_list as three 5.7-us launches, each waiting for the one before): the three
-// as ONE launch.  Block b = image b: the same greedy loop as nms_kernel (kept positions also kept in LDS), then its 16 waves copy the image's keep_k survivor rows
+// as ONE launch.  Block b = image b: nms_kernel's greedy loop (greedy_nms; kept positions also kept in LDS), then its 16 waves copy the image's keep_k survivor rows
 // (compact_kernel's copy, zeros behind the count); the block that finishes LAST (a ticket in device memory, reset for the next launch) builds the image-major head list
 // from counts[B] (head_list_kernel's scan).  Same decisions, same bytes: tests compare it with the staged entry points.
 __global__ __launch_bounds__(1024) void nms_select_kernel(const float* __restrict__ boxes, const float* __restrict__ scores, const float* __restrict__ flame, int n_in,
@@ -305,53 +325,11 @@ __global__ __launch_bounds__(1024) void nms_select_kernel(const float* __restric
                                                           int32_t* __restrict__ ticket, Levels L, const int32_t* __restrict__ lazy_idx, int S, int E) {
     __shared__ float4 sb[1024];
     __shared__ unsigned long long removed[16];
-    __shared__ int s_n;
     __shared__ int s_keep[1024];
     __shared__ int s_off[1025];
     __shared__ int s_last;
     const int b = blockIdx.x, tid = threadIdx.x;
-    if (tid < 16) removed[tid] = 0ull;
-    if (tid == 0) s_n = 0;
-    __syncthreads();
-    bool valid = false;
-    if (tid < n_in) {
-        sb[tid] = *(const float4*)(boxes + ((int64_t)b * n_in + tid) * 4);
-        valid = scores[(int64_t)b * n_in + tid] >= conf;
-    }
-    const unsigned long long bal = __ballot(valid);
-    if ((tid & 63) == 0) atomicAdd(&s_n, __popcll(bal));
-    __syncthreads();
-    const int n = s_n;
-    for (int j = tid; j < keep_k; j += 1024) keep_idx[(int64_t)b * keep_k + j] = -1;
-    int kept = 0;
-    int i = 0;
-    while (kept < keep_k) {
-        int nxt = -1;
-        for (int wd = i >> 6; wd < 16 && nxt < 0; ++wd) {
-            unsigned long long free_bits = ~removed[wd];
-            if (wd == (i >> 6)) free_bits &= ~0ull << (i & 63);
-            if (free_bits) nxt = wd * 64 + __ffsll((long long)free_bits) - 1;
-        }
-        if (nxt < 0 || nxt >= n) break;
-        i = nxt;
-        if (tid == 0) {
-            keep_idx[(int64_t)b * keep_k + kept] = i;
-            s_keep[kept] = i;
-        }
-        ++kept;
-        const float4 bi = sb[i];
-        float area_i;
-        {
-#pragma clang fp contract(off)
-            area_i = (bi.z - bi.x) * (bi.w - bi.y);
-        }
-        const bool sup = (tid > i) && (tid < n) && iou_gt(bi, area_i, sb[tid < n_in ? tid : 0], thr);
-        const unsigned long long m = __ballot(sup);
-        __syncthreads();
-        if ((tid & 63) == 0 && m) removed[tid >> 6] |= m;
-        __syncthreads();
-        ++i;
-    }
+    const int kept = greedy_nms(boxes + (int64_t)b * n_in * 4, scores + (int64_t)b * n_in, n_in, conf, thr, keep_k, keep_idx + (int64_t)b * keep_k, sb, removed, s_keep);
     if (tid == 0) counts[b] = kept;
     __syncthreads();  // s_keep is complete
     // ---- the image's survivor rows ----
@@ -489,6 +467,20 @@ int make_levels(const vgh_head_level* levels, int n_levels, Levels* L) {
     return VGH_OK;
 }
 
+// vgh_topk (FILTER = false) and the candidate stage of vgh_topk_nms (FILTER = true: rows that fail score >= conf rank behind all others)
+template <bool FILTER>
+int topk_launch(const float* scores_dev, int B, int A, int k, int32_t* idx_dev, float* topk_scores_dev, float conf, void* stream) {
+    VGH_REQUIRE(k >= 1 && k <= 1024, "topk: k=%d must be in [1,1024]", k);
+    VGH_REQUIRE(k <= A, "topk: k=%d exceeds the number of anchors %d (torch.topk raises too)", k, A);
+    if (B == 0) return VGH_OK;
+    if (A <= 9 * 1024)
+        hipLaunchKernelGGL((topk_kernel<true, FILTER>), dim3(B), dim3(1024), 0, (hipStream_t)stream, scores_dev, A, k, idx_dev, topk_scores_dev, conf);
+    else
+        hipLaunchKernelGGL((topk_kernel<false, FILTER>), dim3(B), dim3(1024), 0, (hipStream_t)stream, scores_dev, A, k, idx_dev, topk_scores_dev, conf);
+    VGH_HIP(hipGetLastError());
+    return VGH_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -506,15 +498,7 @@ int vgh_head_decode(const vgh_head_level* levels, int n_levels, int B, float* bo
 }
 
 int vgh_topk(const float* scores_dev, int B, int A, int k, int32_t* idx_dev, float* topk_scores_dev, void* stream) {
-    VGH_REQUIRE(k >= 1 && k <= 1024, "topk: k=%d must be in [1,1024]", k);
-    VGH_REQUIRE(k <= A, "topk: k=%d exceeds the number of anchors %d (torch.topk raises too)", k, A);
-    if (B == 0) return VGH_OK;
-    if (A <= 9 * 1024)
-        hipLaunchKernelGGL(topk_kernel<true>, dim3(B), dim3(1024), 0, (hipStream_t)stream, scores_dev, A, k, idx_dev, topk_scores_dev);
-    else
-        hipLaunchKernelGGL(topk_kernel<false>, dim3(B), dim3(1024), 0, (hipStream_t)stream, scores_dev, A, k, idx_dev, topk_scores_dev);
-    VGH_HIP(hipGetLastError());
-    return VGH_OK;
+    return topk_launch<false>(scores_dev, B, A, k, idx_dev, topk_scores_dev, 0.0f, stream);
 }
 
 int vgh_gather_candidates(const vgh_head_level* levels, int n_levels, int B, int A, int shape_c, int expr_c, const float* boxes_dev,
@@ -596,9 +580,9 @@ int vgh_topk_nms(const float* boxes_dev, const float* scores_dev, const float* f
     float* sbx = (float*)(ws + o_sbx);
     int32_t* keep = (int32_t*)(ws + o_keep);
     int rc;
-    // utils.py:174-185: score >= conf filter and top-k are one stable descending sort (ties by ascending index); the conf filter
-    // is the prefix test inside vgh_nms
-    if ((rc = vgh_topk(scores_dev, B, n, k, idx, ssc, stream))) return rc;
+    // utils.py:174-185: the score >= conf filter comes BEFORE the top-k.  One stable descending sort in which the rows that fail the filter rank behind every row that
+    // passes: they fill candidate slots only where fewer than k rows pass, and vgh_nms never visits them
+    if ((rc = topk_launch<true>(scores_dev, B, n, k, idx, ssc, conf_thr, stream))) return rc;
     hipLaunchKernelGGL(gather_boxes_kernel, dim3((k + 255) / 256, B), dim3(256), 0, (hipStream_t)stream, boxes_dev, (const int32_t*)idx, n, k, sbx);
     VGH_HIP(hipGetLastError());
     if ((rc = vgh_nms(sbx, ssc, B, k, conf_thr, iou_thr, keep_k, keep, counts_dev, stream))) return rc;

@@ -240,8 +240,13 @@ typedef struct vgh_head_level {
 /* boxes_dev [B,A,4] xyxy px, scores_dev [B,A] = sigmoid(cls).  A = sum(h*w), level-major, row-major. */
 int vgh_head_decode(const vgh_head_level* levels, int n_levels, int B, float* boxes_dev, float* scores_dev, void* stream);
 
-/* VGGHeadDecodingModule.forward (yolo_heads.py:63-86): per image top-k (sorted descending, ties by
- * ascending anchor index).  idx_dev [B,k] int32 anchor indices, topk_scores_dev [B,k] (may be NULL). */
+/* VGGHeadDecodingModule.forward (yolo_heads.py:63-86): per image top-k, 1 <= k <= min(A, 1024).  The order is that of a STABLE
+ * DESCENDING SORT of the row (torch.sort(descending=True, stable=True)) for every float, not only for scores in (0, 1):
+ *   - -0.0 == +0.0;
+ *   - every NaN, whatever its sign or payload, ranks above +inf (and all NaNs are equal to each other);
+ *   - ties are broken by ascending anchor index.
+ * idx_dev [B,k] int32 anchor indices; topk_scores_dev [B,k] (may be NULL) returns the ORIGINAL BITS of the selected scores
+ * (the sign of a zero and the payload of a NaN included). */
 int vgh_topk(const float* scores_dev, int B, int A, int k, int32_t* idx_dev, float* topk_scores_dev, void* stream);
 
 /* Gather boxes + build the 413-vector for the selected anchors only (never materialises [B,A,413]):
@@ -254,8 +259,11 @@ int vgh_gather_candidates(const vgh_head_level* levels, int n_levels, int B, int
 /* nms() of head_detector/utils.py:159-194 for EVERY image (the batched twin,
  * yolo_heads_post_prediction_callback.py:55-84): conf filter (>=), greedy NMS with torchvision
  * semantics (suppress when IoU > iou_thr, float32 IEEE arithmetic), first keep_k survivors.
- * Inputs must be sorted by descending score per image (vgh_topk output order), n_in <= 1024.
- * keep_idx_dev [B,keep_k] int32 positions into the n_in candidates (-1 padded), counts_dev [B]. */
+ * Inputs must be sorted by descending score per image (vgh_topk output order), n_in <= 1024; NaN scores at the head of that
+ * order are within the precondition.  A row that fails score >= conf_thr (a NaN score fails every threshold, and every row
+ * fails a NaN threshold) is never visited, never kept and never suppresses anything, WHEREVER it stands in the input: the rows
+ * that pass are visited in position order, exactly the rows the reference hands to torchvision.
+ * keep_idx_dev [B,keep_k] int32 positions into the n_in candidates (-1 padded; keep_k may exceed n_in), counts_dev [B]. */
 int vgh_nms(const float* boxes_dev /*[B,n_in,4]*/, const float* scores_dev /*[B,n_in]*/, int B, int n_in, float conf_thr, float iou_thr,
             int keep_k, int32_t* keep_idx_dev, int32_t* counts_dev, void* stream);
 
@@ -266,7 +274,10 @@ int vgh_compact(const float* boxes_dev, const float* scores_dev, const float* fl
 /* The whole of nms() (head_detector/utils.py:159-194; batched twin yolo_heads_post_prediction_callback.py:55-84) for EVERY image
  * on arbitrary (unsorted) inputs: conf filter, top-k (pre_k), greedy NMS, first keep_k survivors, gathered from the ORIGINAL
  * tensors -- boxes [B,n,4], scores [B,n], flame [B,n,flame_width] (or NULL) -> slabs [B,keep_k,{4,1,flame_width}] + counts [B].
- * min(pre_k, n) <= 1024.  workspace_dev: caller-owned, 16-byte aligned, vgh_topk_nms_workspace_bytes(...) bytes. */
+ * min(pre_k, n) <= 1024.  workspace_dev: caller-owned, 16-byte aligned, vgh_topk_nms_workspace_bytes(...) bytes.
+ * FILTER, THEN TOP-K, as the reference does: a row that fails score >= conf_thr (NaN scores among them) takes none of the
+ * min(pre_k, n) candidate slots from a row that passes -- in the candidate order it ranks behind every passing row -- and is
+ * never visited by the NMS.  Among the rows that pass, the order is vgh_topk's. */
 int64_t vgh_topk_nms_workspace_bytes(int B, int n, int pre_k, int keep_k);
 int vgh_topk_nms(const float* boxes_dev, const float* scores_dev, const float* flame_dev, int flame_width, int B, int n, float conf_thr, float iou_thr,
                  int pre_k, int keep_k, void* workspace_dev, float* out_boxes_dev, float* out_scores_dev, float* out_flame_dev, int32_t* counts_dev,
