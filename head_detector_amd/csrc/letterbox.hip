@@ -17,16 +17,13 @@
 
 namespace {
 
-// One source image and where its resized copy goes on the S x S canvas: kernel argument of vgh_letterbox, device-side descriptor of the
-// batched kernel (VGH_IMG_U8_RAW).
-struct LbImage {
-    const uint8_t* src;    // [src_h, src_w, src_cn >= 3] u8, row stride src_pitch bytes
+// Where the resized copy of one source image goes on the S x S canvas, and the tables that resample it: common to every source format.
+struct LbGeom {
     const int32_t* xofs;   // [new_w]
     const int16_t* alpha;  // [new_w][8]
     const int32_t* yofs;   // [new_h]
     const int16_t* beta;   // [new_h][8]
-    int64_t src_pitch;
-    int32_t src_h, src_w, src_cn, new_w, new_h, pad_x, pad_y;
+    int32_t src_h, src_w, new_w, new_h, pad_x, pad_y;
     uint32_t pad;  // border colour r | g << 8 | b << 16
 };
 
@@ -36,8 +33,53 @@ __device__ __forceinline__ const __attribute__((address_space(1))) T* gmem(const
     return (const __attribute__((address_space(1))) T*)p;
 }
 
-// Canvas pixel (x, y) as r | g << 8 | b << 16: the per-pixel arithmetic of BOTH letterbox kernels (they cannot drift apart).
-__device__ __forceinline__ uint32_t letterbox_pixel(const LbImage& a, int x, int y) {
+typedef const __attribute__((address_space(1))) uint8_t* gbytes;
+
+// A source format is a descriptor that derives from LbGeom and tells letterbox_pixel how to fetch one tap: col(x) prepares the (clamped) source column x once per
+// pixel, row(y) the (clamped) source row y once per tap row, tap(row, col, r, g, b) reads the tap as three bytes' worth of int.
+
+// RGB: kernel argument of vgh_letterbox, device-side descriptor of the batched kernel for VGH_IMG_U8_RAW.
+struct LbImage : LbGeom {
+    const uint8_t* src;  // [src_h, src_w, src_cn >= 3] u8, row stride src_pitch bytes
+    int64_t src_pitch;
+    int32_t src_cn;
+    typedef gbytes Row;
+    __device__ __forceinline__ int col(int x) const { return x * src_cn; }
+    __device__ __forceinline__ Row row(int y) const { return gmem(src) + (size_t)y * src_pitch; }
+    __device__ __forceinline__ void tap(Row p, int c, int& r, int& g, int& b) const {
+        r = p[c];
+        g = p[c + 1];
+        b = p[c + 2];
+    }
+};
+
+// YUV 4:2:0 (VGH_IMG_YUV420_RAW): the tap is converted by the rule of include/vgh.h (vgh_yuv420_image) and clamped to bytes BEFORE it is weighted.  The chroma
+// coordinates derive from the CLAMPED luma coordinates (letterbox_pixel clamps before col() / row()), so (x >> 1, y >> 1) never leaves the ceil-sized chroma planes.
+struct LbYuvImage : LbGeom {
+    const uint8_t *y, *u, *v;
+    int64_t y_pitch, uv_pitch;
+    int32_t chroma_step, y_offset, cy, crv, cgu, cgv, cbu;
+    struct Row {
+        gbytes y, u, v;
+    };
+    __device__ __forceinline__ int col(int x) const { return x; }
+    __device__ __forceinline__ Row row(int yy) const {
+        const size_t c = (size_t)(yy >> 1) * uv_pitch;
+        return Row{gmem(y) + (size_t)yy * y_pitch, gmem(u) + c, gmem(v) + c};
+    }
+    __device__ __forceinline__ void tap(const Row& p, int x, int& r, int& g, int& b) const {
+        const int cx = (x >> 1) * chroma_step;
+        const int l = cy * ((int)p.y[x] - y_offset) + 32768, d = (int)p.u[cx] - 128, e = (int)p.v[cx] - 128;
+        // each channel is shifted and clamped into an int of its own and goes straight into a multiply: no clamp-and-pack chain (see the note at the end of letterbox_pixel)
+        r = min(max((l + crv * e) >> 16, 0), 255);
+        g = min(max((l + cgu * d + cgv * e) >> 16, 0), 255);
+        b = min(max((l + cbu * d) >> 16, 0), 255);
+    }
+};
+
+// Canvas pixel (x, y) as r | g << 8 | b << 16: the per-pixel arithmetic of ALL letterbox kernels (they cannot drift apart); generic over the tap fetch.
+template <typename Img>
+__device__ __forceinline__ uint32_t letterbox_pixel(const Img& a, int x, int y) {
     const int dx = x - a.pad_x, dy = y - a.pad_y;
     if ((unsigned)dx >= (unsigned)a.new_w || (unsigned)dy >= (unsigned)a.new_h) return a.pad;
     const int sx = gmem(a.xofs)[dx] - 3, sy = gmem(a.yofs)[dy] - 3;
@@ -45,20 +87,21 @@ __device__ __forceinline__ uint32_t letterbox_pixel(const LbImage& a, int x, int
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         al[k] = gmem(a.alpha)[dx * 8 + k];
-        cx[k] = min(max(sx + k, 0), a.src_w - 1) * a.src_cn;
+        cx[k] = a.col(min(max(sx + k, 0), a.src_w - 1));
     }
     unsigned acc[3] = {0u, 0u, 0u};  // unsigned: C's int accumulation with defined wrap-around
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int ry = min(max(sy + j, 0), a.src_h - 1);
-        const auto row = gmem(a.src) + (size_t)ry * a.src_pitch;
+        const auto row = a.row(ry);
         unsigned h0 = 0u, h1 = 0u, h2 = 0u;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const auto p = row + cx[k];
-            h0 += (unsigned)((int)p[0] * al[k]);
-            h1 += (unsigned)((int)p[1] * al[k]);
-            h2 += (unsigned)((int)p[2] * al[k]);
+            int p0, p1, p2;
+            a.tap(row, cx[k], p0, p1, p2);
+            h0 += (unsigned)(p0 * al[k]);
+            h1 += (unsigned)(p1 * al[k]);
+            h2 += (unsigned)(p2 * al[k]);
         }
         const int b = gmem(a.beta)[dy * 8 + j];
         acc[0] += (unsigned)((int)h0 * b);
@@ -86,11 +129,13 @@ __global__ __launch_bounds__(256) void letterbox_kernel(LbImage a, uint8_t* dst,
     o[2] = (uint8_t)(rgb >> 16);
 }
 
-// VGH_IMG_U8_RAW: every image of an arena chunk in one launch, canvas [n, S, S, 3].  blockIdx.z = image (its descriptor is wave-uniform:
-// scalar loads); one pixel per lane as in letterbox_kernel.  The kernel is bound by the 128 byte gathers per pixel, not by its stores: four
-// pixels per lane with one 3-dword store measured 1.70 ms per 64 mixed photographs against 1.16 ms for this form (profiles/raw_letterbox_l64.txt).
-__global__ __launch_bounds__(256) void letterbox_batch_kernel(const LbImage* __restrict__ imgs, uint8_t* __restrict__ canvas, int S) {
-    const LbImage& a = imgs[blockIdx.z];
+// VGH_IMG_U8_RAW / VGH_IMG_YUV420_RAW: every image of an arena chunk in one launch, canvas [n, S, S, 3]; one instantiation per source format (a call has ONE format,
+// so no lane branches on it).  blockIdx.z = image (its descriptor is wave-uniform: scalar loads); one pixel per lane as in letterbox_kernel.  The RGB kernel is bound
+// by the 128 byte gathers per pixel, not by its stores: four pixels per lane with one 3-dword store measured 1.70 ms per 64 mixed photographs against 1.16 ms for this
+// form (profiles/raw_letterbox_l64.txt).
+template <typename Img>
+__global__ __launch_bounds__(256) void letterbox_batch_kernel(const Img* __restrict__ imgs, uint8_t* __restrict__ canvas, int S) {
+    const Img& a = imgs[blockIdx.z];
     const int x = blockIdx.x * 32 + (threadIdx.x & 31), y = blockIdx.y * 8 + (threadIdx.x >> 5);
     if (x >= S || y >= S) return;
     uint8_t* o = canvas + (((size_t)blockIdx.z * S + y) * S + x) * 3;
@@ -128,9 +173,9 @@ extern "C" int vgh_letterbox(const uint8_t* src_dev, int src_h, int src_w, int s
     return VGH_OK;
 }
 
-// ---- VGH_IMG_U8_RAW: the detector's batched letterbox (include/vgh.h, vgh_detect) ----------------------------------------------------------
+// ---- VGH_IMG_U8_RAW / VGH_IMG_YUV420_RAW: the detector's batched letterbox (include/vgh.h, vgh_detect) -------------------------------------
 // The host validates the B descriptors, builds (or finds in its cache) the per-axis tables and packs, for every arena chunk, the chunk's
-// LbImage descriptors and tables into a pinned staging slot: ONE async copy and ONE letterbox_batch_kernel launch per chunk.  The first slot
+// LbImage (or LbYuvImage) descriptors and tables into a pinned staging slot: ONE async copy and ONE letterbox_batch_kernel launch per chunk.  The first slot
 // region also holds the un-pad table [max_batch, 3] of the whole call, so it travels with the first chunk's copy.
 //
 // Two slots, alternating per call.  A slot is free again once its last device reader has run: the letterbox launches of its call (on the
@@ -146,6 +191,7 @@ struct vgh_lb_batch {
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool recorded[2] = {false, false};
     int slot = 1;                  // slot of the last prepared call
+    int fmt = VGH_IMG_U8_RAW;      // source format of the last prepared call: which descriptors its slot holds, which kernel reads them
     std::vector<size_t> chunk_at;  // [chunks + 1] byte offsets of the chunk regions in the slot
     std::map<std::pair<int, int>, vgh_lb::AxisTables> cache;  // (src, dst) length -> tables, like letterbox.py's lru_cache
 };
@@ -177,8 +223,10 @@ int lb_create(int S, int max_batch, int arena_batch, vgh_lb_batch** out) {
     lb->S = S;
     lb->max_batch = max_batch;
     lb->arena_batch = arena_batch;
-    // per image at most sizeof(LbImage) + 16 bytes of descriptor region and two axes of <= S entries (4 + 16 bytes, 16-byte aligned)
-    lb->slot_bytes = align16((size_t)max_batch * 12) + (size_t)max_batch * (sizeof(LbImage) + 16 + 2 * (align16((size_t)4 * S) + (size_t)16 * S));
+    // per image at most one descriptor (the larger of the two source formats') + 16 bytes of descriptor region and two axes of <= S entries (4 + 16 bytes, 16-byte
+    // aligned): a slot serves either format, so nothing is allocated when the format changes between calls
+    const size_t desc_bytes = sizeof(LbImage) > sizeof(LbYuvImage) ? sizeof(LbImage) : sizeof(LbYuvImage);
+    lb->slot_bytes = align16((size_t)max_batch * 12) + (size_t)max_batch * (desc_bytes + 16 + 2 * (align16((size_t)4 * S) + (size_t)16 * S));
     const size_t canvas_bytes = (size_t)arena_batch * S * S * 3;
     bool ok = hipMalloc((void**)&lb->canvas, canvas_bytes) == hipSuccess;
     for (int k = 0; k < 2 && ok; ++k)
@@ -195,15 +243,61 @@ int lb_create(int S, int max_batch, int arena_batch, vgh_lb_batch** out) {
 
 }  // namespace
 
-int vgh_lb_prepare(vgh_lb_batch** plb, int S, int max_batch, int arena_batch, const vgh_raw_image* imgs, int B) {
+namespace {
+
+// the source half of a device descriptor from the caller's; the geometry half is filled by vgh_lb_prepare
+void set_source(LbImage& a, const vgh_raw_image& im) {
+    a.src = im.data_dev;
+    a.src_pitch = im.pitch_bytes;
+    a.src_cn = im.channels;
+}
+
+void set_source(LbYuvImage& a, const vgh_yuv420_image& im) {
+    a.y = im.y_dev;
+    a.u = im.u_dev;
+    a.v = im.v_dev;
+    a.y_pitch = im.y_pitch_bytes;
+    a.uv_pitch = im.uv_pitch_bytes;
+    a.chroma_step = im.chroma_step;
+    a.y_offset = im.y_offset;
+    a.cy = im.cy;
+    a.crv = im.crv;
+    a.cgu = im.cgu;
+    a.cgv = im.cgv;
+    a.cbu = im.cbu;
+}
+
+int check_source(const vgh_raw_image& im, int i) {
+    VGH_REQUIRE(im.data_dev, "detector_candidates: image %d: null data_dev", i);
+    VGH_REQUIRE(im.h >= 1 && im.w >= 1, "detector_candidates: image %d: empty (%d x %d)", i, im.h, im.w);
+    VGH_REQUIRE(im.channels >= 3, "detector_candidates: image %d: %d channels (needs >= 3, the first three RGB)", i, im.channels);
+    VGH_REQUIRE(im.pitch_bytes >= (int64_t)im.w * im.channels, "detector_candidates: image %d: pitch_bytes %lld < w * channels = %lld", i, (long long)im.pitch_bytes,
+                (long long)im.w * im.channels);
+    return VGH_OK;
+}
+
+int check_source(const vgh_yuv420_image& im, int i) {
+    VGH_REQUIRE(im.y_dev && im.u_dev && im.v_dev, "detector_candidates: image %d: null plane (y_dev, u_dev and v_dev are all needed)", i);
+    VGH_REQUIRE(im.h >= 1 && im.w >= 1, "detector_candidates: image %d: empty (%d x %d)", i, im.h, im.w);
+    VGH_REQUIRE(im.chroma_step == 1 || im.chroma_step == 2, "detector_candidates: image %d: chroma_step %d (1 = planar, 2 = interleaved)", i, im.chroma_step);
+    VGH_REQUIRE(im.y_pitch_bytes >= (int64_t)im.w, "detector_candidates: image %d: y_pitch_bytes %lld < w = %d", i, (long long)im.y_pitch_bytes, im.w);
+    const int64_t crow = (int64_t)im.chroma_step * (((int64_t)im.w + 1) / 2);
+    VGH_REQUIRE(im.uv_pitch_bytes >= crow, "detector_candidates: image %d: uv_pitch_bytes %lld < chroma_step * ((w + 1) / 2) = %lld", i, (long long)im.uv_pitch_bytes,
+                (long long)crow);
+    VGH_REQUIRE(im.y_offset >= 0 && im.y_offset <= 255, "detector_candidates: image %d: y_offset %d outside 0..255", i, im.y_offset);
+    const int32_t coef[5] = {im.cy, im.crv, im.cgu, im.cgv, im.cbu};
+    static const char* const names[5] = {"cy", "crv", "cgu", "cgv", "cbu"};
+    for (int k = 0; k < 5; ++k)
+        VGH_REQUIRE(coef[k] >= -(1 << 20) && coef[k] <= (1 << 20), "detector_candidates: image %d: coefficient %s = %d outside +-2^20", i, names[k], coef[k]);
+    return VGH_OK;
+}
+
+template <typename Desc, typename Src>
+int lb_prepare(vgh_lb_batch** plb, int S, int max_batch, int arena_batch, int fmt, const Src* imgs, int B) {
     std::vector<vgh_lb::Geometry> geo(B);
     for (int i = 0; i < B; ++i) {  // everything is checked before anything is allocated, written or queued
-        const vgh_raw_image& im = imgs[i];
-        VGH_REQUIRE(im.data_dev, "detector_candidates: image %d: null data_dev", i);
-        VGH_REQUIRE(im.h >= 1 && im.w >= 1, "detector_candidates: image %d: empty (%d x %d)", i, im.h, im.w);
-        VGH_REQUIRE(im.channels >= 3, "detector_candidates: image %d: %d channels (needs >= 3, the first three RGB)", i, im.channels);
-        VGH_REQUIRE(im.pitch_bytes >= (int64_t)im.w * im.channels, "detector_candidates: image %d: pitch_bytes %lld < w * channels = %lld", i, (long long)im.pitch_bytes,
-                    (long long)im.w * im.channels);
+        const Src& im = imgs[i];
+        if (int rc = check_source(im, i)) return rc;
         geo[i] = vgh_lb::geometry(im.h, im.w, S);
         VGH_REQUIRE(geo[i].new_w >= 1 && geo[i].new_h >= 1, "detector_candidates: image %d (%d x %d) is too elongated for a %dx%d letterbox", i, im.h, im.w, S, S);
     }
@@ -224,17 +318,15 @@ int vgh_lb_prepare(vgh_lb_batch** plb, int S, int max_batch, int arena_batch, co
     for (int c0 = 0; c0 < B; c0 += arena_batch) {
         const int n = B - c0 < arena_batch ? B - c0 : arena_batch;
         lb->chunk_at.push_back(at);
-        LbImage* desc = (LbImage*)(h + at);
-        at = align16(at + (size_t)n * sizeof(LbImage));
+        Desc* desc = (Desc*)(h + at);
+        at = align16(at + (size_t)n * sizeof(Desc));
         for (int i = 0; i < n; ++i) {
-            const vgh_raw_image& im = imgs[c0 + i];
+            const Src& im = imgs[c0 + i];
             const vgh_lb::Geometry& g = geo[c0 + i];
-            LbImage& a = desc[i];
-            a.src = im.data_dev;
-            a.src_pitch = im.pitch_bytes;
+            Desc& a = desc[i];
+            set_source(a, im);
             a.src_h = im.h;
             a.src_w = im.w;
-            a.src_cn = im.channels;
             a.new_w = g.new_w;
             a.new_h = g.new_h;
             a.pad_x = g.pad_x;
@@ -258,7 +350,22 @@ int vgh_lb_prepare(vgh_lb_batch** plb, int S, int max_batch, int arena_batch, co
     }
     lb->chunk_at.push_back(at);
     lb->slot = k;
+    lb->fmt = fmt;
     return VGH_OK;
+}
+
+template <typename Desc>
+void launch_batch(const vgh_lb_batch* lb, int k, int chunk, int n, hipStream_t stream) {
+    const int S = lb->S;
+    hipLaunchKernelGGL(letterbox_batch_kernel<Desc>, dim3((S + 31) / 32, (S + 7) / 8, n), dim3(256), 0, stream, (const Desc*)(lb->dev[k] + lb->chunk_at[chunk]), lb->canvas, S);
+}
+
+}  // namespace
+
+int vgh_lb_prepare(vgh_lb_batch** plb, int S, int max_batch, int arena_batch, int image_fmt, const void* imgs, int B) {
+    if (image_fmt == VGH_IMG_YUV420_RAW) return lb_prepare<LbYuvImage>(plb, S, max_batch, arena_batch, image_fmt, (const vgh_yuv420_image*)imgs, B);
+    VGH_REQUIRE(image_fmt == VGH_IMG_U8_RAW, "letterbox: image format %d is not a raw format", image_fmt);
+    return lb_prepare<LbImage>(plb, S, max_batch, arena_batch, image_fmt, (const vgh_raw_image*)imgs, B);
 }
 
 int vgh_lb_chunk(vgh_lb_batch* lb, int chunk, int n, hipStream_t stream) {
@@ -266,9 +373,10 @@ int vgh_lb_chunk(vgh_lb_batch* lb, int chunk, int n, hipStream_t stream) {
     const int k = lb->slot;
     const size_t from = chunk == 0 ? 0 : lb->chunk_at[chunk], to = lb->chunk_at[chunk + 1];  // chunk 0 carries the un-pad table in front
     VGH_HIP(hipMemcpyAsync(lb->dev[k] + from, lb->host[k] + from, to - from, hipMemcpyHostToDevice, stream));
-    const int S = lb->S;
-    hipLaunchKernelGGL(letterbox_batch_kernel, dim3((S + 31) / 32, (S + 7) / 8, n), dim3(256), 0, stream,
-                       (const LbImage*)(lb->dev[k] + lb->chunk_at[chunk]), lb->canvas, S);
+    if (lb->fmt == VGH_IMG_YUV420_RAW)
+        launch_batch<LbYuvImage>(lb, k, chunk, n, stream);
+    else
+        launch_batch<LbImage>(lb, k, chunk, n, stream);
     VGH_HIP(hipGetLastError());
     VGH_HIP(hipEventRecord(lb->ev[k], stream));
     lb->recorded[k] = true;

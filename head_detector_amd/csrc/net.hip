@@ -614,7 +614,7 @@ void vgh_net_destroy(vgh_net* n) {
 
 int vgh_net_forward(vgh_net* n, const void* image_dev, int image_fmt, int B, void* stream) {
     VGH_REQUIRE(n && image_dev, "net_forward: null argument");
-    VGH_REQUIRE(image_fmt == VGH_IMG_F32_NCHW || image_fmt == VGH_IMG_U8_NHWC, "net_forward: image format %d is not a canvas (VGH_IMG_U8_RAW is letterboxed by vgh_detect)", image_fmt);
+    VGH_REQUIRE(image_fmt == VGH_IMG_F32_NCHW || image_fmt == VGH_IMG_U8_NHWC, "net_forward: image format %d is not a canvas (VGH_IMG_U8_RAW and VGH_IMG_YUV420_RAW are letterboxed by vgh_detect)", image_fmt);
     VGH_REQUIRE(B >= 0 && B <= n->max_batch, "net_forward: B=%d exceeds max_batch=%d", B, n->max_batch);
     // Independent branches (the three detection heads) run on side streams: a FORK op records an event on the main stream,
     // the first op of a lane after it makes that lane's stream wait for the event, and every used lane is joined back into
@@ -663,7 +663,7 @@ int vgh_net_forward(vgh_net* n, const void* image_dev, int image_fmt, int B, voi
 
 int vgh_net_profile(vgh_net* n, const void* image_dev, int image_fmt, int B, void* stream, float* op_ms) {
     VGH_REQUIRE(n && image_dev && op_ms, "net_profile: null argument");
-    VGH_REQUIRE(image_fmt == VGH_IMG_F32_NCHW || image_fmt == VGH_IMG_U8_NHWC, "net_profile: image format %d is not a canvas (VGH_IMG_U8_RAW is letterboxed by vgh_detect)", image_fmt);
+    VGH_REQUIRE(image_fmt == VGH_IMG_F32_NCHW || image_fmt == VGH_IMG_U8_NHWC, "net_profile: image format %d is not a canvas (VGH_IMG_U8_RAW and VGH_IMG_YUV420_RAW are letterboxed by vgh_detect)", image_fmt);
     VGH_REQUIRE(B >= 0 && B <= n->max_batch, "net_profile: B=%d exceeds max_batch=%d", B, n->max_batch);
     hipStream_t st = (hipStream_t)stream;
     ++n->generation;
@@ -702,7 +702,7 @@ int vgh_net_profile(vgh_net* n, const void* image_dev, int image_fmt, int B, voi
 
 int vgh_net_capture(vgh_net* n, const void* image_dev, int image_fmt, int B, void* stream) {
     VGH_REQUIRE(n && stream, "net_capture: needs a non-null stream");
-    VGH_REQUIRE(image_fmt == VGH_IMG_F32_NCHW || image_fmt == VGH_IMG_U8_NHWC, "net_capture: image format %d is not a canvas (VGH_IMG_U8_RAW is letterboxed by vgh_detect)", image_fmt);
+    VGH_REQUIRE(image_fmt == VGH_IMG_F32_NCHW || image_fmt == VGH_IMG_U8_NHWC, "net_capture: image format %d is not a canvas (VGH_IMG_U8_RAW and VGH_IMG_YUV420_RAW are letterboxed by vgh_detect)", image_fmt);
     VGH_REQUIRE(!n->pred_guard, "net_capture: a prediction guard event is set (detector overlap mode); graph replay cannot honour it");
     VGH_REQUIRE(!n->lane_wait_cycle, "net_capture: two side lanes of this program wait for each other's ops; the HIP runtime cannot end the capture of such a program (run it eagerly, "
                 "or lay the lanes out so that the wait-for relation among lanes 1..3 is acyclic, as arch.schedule_latency does)");

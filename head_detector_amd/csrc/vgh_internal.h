@@ -182,11 +182,11 @@ extern "C" __attribute__((visibility("hidden"))) int vgh_net_set_pred_guard(vgh_
 // results of the latest one.  The detector's lazy FLAME gather is tied to the generation it decoded (detect.hip)
 extern "C" __attribute__((visibility("hidden"))) uint64_t vgh_net_generation(vgh_net* n);
 
-// letterbox.hip: the batched letterbox of VGH_IMG_U8_RAW, owned by a detector (canvas [arena_batch, S, S, 3] + two pinned / device staging slots)
+// letterbox.hip: the batched letterbox of VGH_IMG_U8_RAW / VGH_IMG_YUV420_RAW, owned by a detector (canvas [arena_batch, S, S, 3] + two pinned / device staging slots)
 struct vgh_lb_batch;
 // Validates the B descriptors (VGH_ERR_INVALID naming the image; nothing allocated or queued) and packs their tables + the un-pad table into the
 // next staging slot; *lb (NULL before the first RAW call) is created here.
-int vgh_lb_prepare(vgh_lb_batch** lb, int S, int max_batch, int arena_batch, const vgh_raw_image* imgs, int B);
+int vgh_lb_prepare(vgh_lb_batch** lb, int S, int max_batch, int arena_batch, int image_fmt, const void* imgs, int B);  // imgs: B vgh_raw_image / vgh_yuv420_image
 int vgh_lb_chunk(vgh_lb_batch* lb, int chunk, int n, hipStream_t stream);  // chunk's upload + ONE launch -> canvas rows [0, n)
 int vgh_lb_unpad_read(vgh_lb_batch* lb, hipStream_t stream);            // a select on `stream` read the un-pad table of the last call
 uint8_t* vgh_lb_canvas(const vgh_lb_batch* lb);

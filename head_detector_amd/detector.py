@@ -262,23 +262,32 @@ class HeadDetector:
         boxes, scores, flame_params = nms(boxes, scores, flame_params, confidence_threshold=confidence_threshold)
         return self._parse_predictions(boxes, scores, flame_params, cache)
 
-    def detect_batch(self, images: Sequence[Union[str, "np.ndarray", Any]], confidence_threshold: float = 0.5) -> List[PredictionResult]:
+    def detect_batch(self, images: Sequence[Union[str, "np.ndarray", Any]], confidence_threshold: float = 0.5, *, rgb: str = "host") -> List[PredictionResult]:
         """Batched twin of ``__call__`` (what yolo_heads_post_prediction_callback.py:41-99 does for a batch): the images, of any sizes, go through
         ONE fused device call (vgh_detect with VGH_IMG_U8_RAW: batched letterbox -> net -> top-k -> NMS per image -> FLAME decode + un-pad + head
-        pose of every survivor); only the final per-head Python objects are built on the host.  Needs ``max_batch >= len(images)``."""
+        pose of every survivor); only the final per-head Python objects are built on the host.  Needs ``max_batch >= len(images)``.
+        Video frames: a list of ``video.YUV420Frame`` (all of them frames) goes through the same call as VGH_IMG_YUV420_RAW; each result's ``original_image`` is the
+        frame's ``to_rgb()``, a NumPy array, or with ``rgb="device"`` a GPU tensor (which ``draw(..., to_host=False)`` and the other device helpers take as it is)."""
         if len(images) > self._max_batch:
             raise ValueError(f"detect_batch: {len(images)} images exceed max_batch={self._max_batch} (pass max_batch= to HeadDetector)")
         from .letterbox import geometry
+        from .video import YUV420Frame, frame_rgb
 
-        originals = [self._convert_image(im) for im in images]
+        frames = any(isinstance(im, YUV420Frame) for im in images)
+        if rgb != "host" and not frames:
+            raise ValueError(f"rgb={rgb!r} applies to YUV420Frame inputs only")
+        originals = list(images) if frames else [self._convert_image(im) for im in images]
         if not originals:
             return []
-        raw = []
-        for im in originals:
-            src = torch.from_numpy(np.ascontiguousarray(im))
-            if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] < 3:
-                raise ValueError(f"detect_batch expects uint8 images [H,W,3]; got {src.dtype} {tuple(src.shape)}")
-            raw.append(src.to(self._device, non_blocking=True))
+        if frames:
+            raw = originals  # already on the device (a list mixing frames and RGB images is refused by the engine)
+        else:
+            raw = []
+            for im in originals:
+                src = torch.from_numpy(np.ascontiguousarray(im))
+                if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] < 3:
+                    raise ValueError(f"detect_batch expects uint8 images [H,W,3]; got {src.dtype} {tuple(src.shape)}")
+                raw.append(src.to(self._device, non_blocking=True))
         det = self.model.detect(raw, confidence_threshold=confidence_threshold, flame=self._flame)  # FLAME outputs un-padded on the device
         counts = det.counts.cpu().numpy()
         n = det.num_heads
@@ -289,6 +298,8 @@ class HeadDetector:
         S = self._image_size
         for b, orig in enumerate(originals):
             _, _, pad_x, pad_y, scale = geometry(orig.shape[0], orig.shape[1], S)
+            if frames:
+                orig = frame_rgb(orig, rgb)
             heads = []
             for i in range(int(counts[b])):
                 if at >= n:
@@ -318,7 +329,11 @@ class HeadDetector:
         (``sliced.to_whole_image_params``); head pose as ``__call__`` computes it.  With only the whole-image tile (``tile_sizes=()``) the heads are those of
         ``__call__``.  -> PredictionResult, or (PredictionResult, sliced.SliceInfo) with ``return_info``."""
         from . import sliced
+        from .video import YUV420Frame
 
+        if isinstance(image, YUV420Frame):
+            raise TypeError("detect_sliced takes an RGB image: its tiles are pitched sub-views of the photograph, which a 4:2:0 frame's half-size chroma planes cannot "
+                            "give at odd offsets; pass frame.to_rgb()")
         original = self._convert_image(image)
         src = torch.from_numpy(np.ascontiguousarray(original))
         if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] < 3:
@@ -365,9 +380,23 @@ class HeadDetector:
         tally = torch.bincount(merged.status.long(), minlength=len(sliced.STATUS_NAMES)).cpu().tolist()
         return result, sliced.SliceInfo(plan=plan, head_tile=tile_of, status_counts=dict(zip(sliced.STATUS_NAMES, tally)), n_kept_uncapped=int(merged.n_kept_uncapped.item()))
 
-    def __call__(self, image: Union[str, "np.ndarray", Any], confidence_threshold: float = 0.5) -> PredictionResult:
-        original_image = self._convert_image(image)
-        image, cache = self._preprocess(original_image)
-        predictions = self._process(image)
+    def __call__(self, image: Union[str, "np.ndarray", Any], confidence_threshold: float = 0.5, *, rgb: str = "host") -> PredictionResult:
+        """``image``: a path, a PIL image, an HWC uint8 array, or a ``video.YUV420Frame`` (NV12 / NV21 / I420, converted inside the device letterbox; the result is
+        that of the frame's ``to_rgb()`` image, which becomes ``original_image``: on the host, or with ``rgb="device"`` as a GPU tensor)."""
+        from .video import YUV420Frame, frame_rgb
+
+        if isinstance(image, YUV420Frame):
+            from .letterbox import geometry
+
+            _, _, pad_x, pad_y, scale = geometry(image.shape[0], image.shape[1], self._image_size)
+            cache = {"padding": (pad_x, pad_y), "scale": scale}
+            predictions = self.model.model([image])  # the same canvas bytes letterbox() makes of to_rgb(), hence the same predictions
+            original_image = frame_rgb(image, rgb)
+        else:
+            if rgb != "host":
+                raise ValueError(f"rgb={rgb!r} applies to YUV420Frame inputs only")
+            original_image = self._convert_image(image)
+            image, cache = self._preprocess(original_image)
+            predictions = self._process(image)
         heads = self._postprocess(predictions, cache, confidence_threshold)
         return PredictionResult(original_image=original_image, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc, head_indices=self._head_indices, triangles=self._triangles, face_indices=self._face_indices)

@@ -186,10 +186,12 @@ class HeadTracker:
         self.state.reset()
         self._frame_shape = None
 
-    def update(self, frame) -> TrackedPredictionResult:
-        return self.update_batch([frame])[0]
+    def update(self, frame, *, rgb: str = "host") -> TrackedPredictionResult:
+        return self.update_batch([frame], rgb=rgb)[0]
 
-    def update_batch(self, frames: Sequence) -> List[TrackedPredictionResult]:
+    def update_batch(self, frames: Sequence, *, rgb: str = "host") -> List[TrackedPredictionResult]:
+        """``frames``: RGB images as ``HeadDetector.detect_batch`` takes them, or ``video.YUV420Frame`` s (all of them; converted inside the device letterbox).  For
+        those, each result's ``original_image`` is the frame's ``to_rgb()``: a NumPy array, or with ``rgb="device"`` a GPU tensor."""
         import torch
 
         from .head_info import Bbox, FlameParams, HeadMetadata
@@ -199,13 +201,18 @@ class HeadTracker:
         det = self.detector
         if len(frames) > det._max_batch:
             raise ValueError(f"update_batch: {len(frames)} frames exceed max_batch={det._max_batch} (pass max_batch= to HeadDetector)")
-        originals = [det._convert_image(im) for im in frames]
+        from .video import YUV420Frame, frame_rgb
+
+        yuv = any(isinstance(im, YUV420Frame) for im in frames)  # (a list mixing them with RGB images is refused by the engine)
+        if rgb != "host" and not yuv:
+            raise ValueError(f"rgb={rgb!r} applies to YUV420Frame inputs only")
+        originals = list(frames) if yuv else [det._convert_image(im) for im in frames]
         if not originals:
             return []
         raw = []
         for im in originals:
-            src = torch.from_numpy(np.ascontiguousarray(im))
-            if src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] < 3:
+            src = im if yuv else torch.from_numpy(np.ascontiguousarray(im))
+            if not yuv and (src.dtype != torch.uint8 or src.dim() != 3 or src.shape[2] < 3):
                 raise ValueError(f"update_batch expects uint8 frames [H,W,3]; got {src.dtype} {tuple(src.shape)}")
             shape = (int(src.shape[0]), int(src.shape[1]))
             if self._frame_shape is None:
@@ -213,7 +220,7 @@ class HeadTracker:
             if shape != self._frame_shape:
                 raise ValueError(f"update_batch: a frame of {shape[0]} x {shape[1]} after frames of {self._frame_shape[0]} x {self._frame_shape[1]}: a tracker's boxes "
                                  "live in one image's coordinates; call reset() before a video of another size")
-            raw.append(src.to(det._device, non_blocking=True))
+            raw.append(src if yuv else src.to(det._device, non_blocking=True))
         H, W = self._frame_shape
         S, B = det._image_size, len(raw)
         _, _, pad_x, pad_y, scale = geometry(H, W, S)
@@ -236,6 +243,8 @@ class HeadTracker:
         ids, hits, misses = tracked.ids.cpu().numpy(), tracked.hits.cpu().numpy(), tracked.misses.cpu().numpy()
         results = []
         for b, orig in enumerate(originals):
+            if yuv:
+                orig = frame_rgb(orig, rgb)
             k = int(n_out[b])
             bb = np.rint(boxes[b, :k]).astype(int)
             bb[:, [0, 2]] = bb[:, [0, 2]].clip(0, W)

@@ -14,7 +14,8 @@ check prints PASS / FAIL / SKIPPED with the number behind it, and the exit code 
                        bit for bit (detector.py:40-52); the warp of get_aligned_heads (csrc/aligned.hip, OpenCV's 8-bit bilinear warpAffine restated) against
                        cv2.getRotationMatrix2D + cv2.warpAffine, bit for bit (utils.py:93-117); PredictionResult.draw (csrc/draw.hip, OpenCV's rectangle / polylines /
                        circle restated) for "full", "bbox", "landmarks" and "points" against the reference's own loop of cv2 calls (draw_utils.py), bit for bit, with
-                       the time that loop takes for the same heads.
+                       the time that loop takes for the same heads.  Also REPORTS (does not require) the largest byte difference between video.YUV420Frame.to_rgb
+                       (bt601, limited range) and cv2.cvtColor(..., COLOR_YUV2RGB_NV12): that parity is unpinned.
   4. --images + weights (+ --pkl): bf16 / fp16 / int8 / fp8 against the fp16x3 parity mode on those photographs -- dense boxes IoU, scores, the kept detections'
                        parameters and vertices; int8 / fp8 calibrated on the same photographs.
   5. pycocotools     : wherever that package is installed, detection_metrics.average_precision (csrc/detection_ap.hip) against COCOeval(..., 'bbox') itself on a seeded set
@@ -150,6 +151,17 @@ def main():
                 worst = max(worst, int(d.max()))
                 nbad += int((d > 0).sum())
             report("letterbox vs cv2 (bit for bit)", worst == 0, f"{len(imgs)} images, max |diff| {worst}, {nbad} differing bytes")
+            # video.YUV420Frame.to_rgb (the rule of include/vgh.h, bt601 limited range) against cv2.cvtColor(COLOR_YUV2RGB_NV12): REPORTED, not required to agree --
+            # cv2 rounds its coefficients to another fixed-point precision, so a difference of a few least significant bits is expected
+            from head_detector_amd.video import YUV420Frame
+
+            yworst, ybad, ytotal = 0, 0, 0
+            for h, w in ((480, 640), (1080, 1920), (2, 2)):
+                surf = rng.integers(0, 256, (h * 3 // 2, w), dtype=np.uint8)
+                got = YUV420Frame.from_nv12(torch.from_numpy(surf), h, w, matrix="bt601").to_rgb().numpy()
+                d = np.abs(got.astype(np.int32) - cv2.cvtColor(surf, cv2.COLOR_YUV2RGB_NV12).astype(np.int32))
+                yworst, ybad, ytotal = max(yworst, int(d.max())), ybad + int((d > 0).sum()), ytotal + d.size
+            print(f"[REPORT] YUV420Frame.to_rgb (bt601, limited) vs cv2 COLOR_YUV2RGB_NV12 (parity unpinned): max |diff| {yworst}, {ybad} of {ytotal} bytes differ", flush=True)
             # the warp of get_aligned_heads (csrc/aligned.hip, OpenCV's 8-bit bilinear warpAffine restated) against cv2.getRotationMatrix2D + cv2.warpAffine
             from head_detector_amd import aligned
 
