@@ -6,6 +6,12 @@
 #include "../../include/vgh.h"
 #include "conv_args.h"
 
+// ---- activation storage formats (VGH_FMT_*, include/vgh.h) ----
+static inline int vgh_fmt_bytes(int fmt) { return (fmt == VGH_FMT_FP8 || fmt == VGH_FMT_I8) ? 1 : (fmt == 0 || fmt == VGH_FMT_F16) ? 2 : 4; }  // bytes per logical element of an activation buffer
+static inline int vgh_fmt_planes(int fmt) { return (fmt == VGH_FMT_BF16X2 || fmt == VGH_FMT_F16X2) ? 2 : 1; }
+static inline int vgh_fmt_is_q8(int fmt) { return fmt == VGH_FMT_FP8 || fmt == VGH_FMT_I8; }    // an 8-bit link format
+static inline int vgh_fmt_q8_kind(int fmt) { return fmt == VGH_FMT_FP8 ? 1 : fmt == VGH_FMT_I8 ? 2 : 0; }  // ConvArgs::in_fp8 / out_fp8 code
+
 // One value per kernel family.  The bf16 table (conv_igemm.hip) holds the first ten, the split / fp16 table (conv_split.hip) the last three.
 enum class TileFamily {
     Igemm,        // conv_igemm_kernel: implicit GEMM, any ksize / stride / epilogue (plain, deep-stage, counted-ring and loader-wave tiles)

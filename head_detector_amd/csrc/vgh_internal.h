@@ -95,14 +95,10 @@ int vgh_launch_conv_split(const ConvArgs& a, int force_cfg, hipStream_t stream);
 // vgh_pack_conv_weights_host); fmt = VGH_FMT_BF16X2 / VGH_FMT_F16X2.  Returns through *out_scale the factor the kernel multiplies the
 // accumulators by (fp16: 2^-s with 2^s the power-of-two prescale that brings max|w| to ~2^9; bf16: 1).
 void vgh_pack_conv_weights_split_host(const float* w, int cout_pad, int ksize, int cin, int fmt, uint16_t* dst, float* out_scale);
-static inline int vgh_fmt_bytes(int fmt) { return (fmt == VGH_FMT_FP8 || fmt == VGH_FMT_I8) ? 1 : (fmt == 0 || fmt == VGH_FMT_F16) ? 2 : 4; }  // bytes per logical element of an activation buffer
-static inline int vgh_fmt_planes(int fmt) { return (fmt == VGH_FMT_BF16X2 || fmt == VGH_FMT_F16X2) ? 2 : 1; }
 // conv_pp.hip (host): OCP e4m3fn conversion and the e4m3 weight image of the ping-pong tiles
 uint8_t vgh_f32_to_e4m3_host(float f);
 void vgh_pack_conv_weights_fp8_host(const float* w, int cout_pad, int ksize, int cin, uint8_t* dst, float* wscale);
 void vgh_pack_conv_weights_i8_host(const float* w, int cout_pad, int ksize, int cin, uint8_t* dst, float* wscale);
-static inline int vgh_fmt_is_q8(int fmt) { return fmt == VGH_FMT_FP8 || fmt == VGH_FMT_I8; }    // an 8-bit link format
-static inline int vgh_fmt_q8_kind(int fmt) { return fmt == VGH_FMT_FP8 ? 1 : fmt == VGH_FMT_I8 ? 2 : 0; }  // ConvArgs::in_fp8 / out_fp8 code
 // conv_pp.hip: the 8-wave ping-pong 3x3 / stride-1 tiles (family PingPongG / H / S, or PingPongF16; bc = 128 / 96 / 64 couts per workgroup); `a` prepared, `g` its tile_grid
 int vgh_launch_conv_pp(const ConvArgs& a, TileFamily family, int bc, const TileGrid& g, int max_blocks_per_xcd, hipStream_t stream);
 int vgh_conv_pp_lds(int bc);

@@ -802,6 +802,33 @@ def test_b2b_pairs_equal_their_two_launches(gpu_lib, variant, S, B, tuned):
     eng.close()
 
 
+def test_profile_splits_the_batch_as_the_forward_does(gpu_lib):
+    """vgh_net_profile with two batch-split lanes runs every op's sub-batches on the lane streams, split by the same rule as vgh_net_forward (csrc/net_plan.h
+    rows_of_lane): 3 images as 2 + 1, one image on the single-lane path.  Every fp32 prediction buffer afterwards holds the bits forward_net leaves for the same
+    images (other images lie in the arena in between), and every op has a finite, non-negative time."""
+    from head_detector_amd import arch
+    from head_detector_amd.engine import VGHeadsEngine
+
+    S = 64
+    eng = VGHeadsEngine("vgg_heads_m", image_size=S, max_batch=3, seed=5, use_tuning=False, keep_top_k=50)  # (a 64 x 64 image has 84 anchors)
+    eng.set_split(2)
+    P = eng.program
+    preds = [i for i, bf in enumerate(P.bufs) if bf["is_f32"] == arch.FMT_F32]
+    assert len(preds) >= 3
+    g = torch.Generator().manual_seed(64)
+    x, other = (torch.randint(0, 256, (3, S, S, 3), dtype=torch.uint8, generator=g).to(_dev()) for _ in range(2))
+    for B in (3, 1):
+        eng.forward_net(x[:B].contiguous())
+        ref = [eng.buffer(i, B).clone() for i in preds]
+        eng.forward_net(other)
+        assert any(not torch.equal(eng.buffer(i, B), r) for i, r in zip(preds, ref))
+        ops = eng.profile_ops(x[:B].contiguous())
+        assert len(ops) == len(P.ops) and all(np.isfinite(o["ms"]) and o["ms"] >= 0.0 for o in ops), [o["ms"] for o in ops]
+        for i, r in zip(preds, ref):
+            assert float(r.abs().max()) > 0 and torch.equal(eng.buffer(i, B), r), (B, P.bufs[i]["name"])
+    eng.close()
+
+
 def test_stem_tensor_at_its_48_channel_pitch(gpu_lib, monkeypatch):
     """bf16 mode (r04): the stem tensor is stored as 96-byte pixels and the stage-1 downsample reads 64-channel K windows over it -- the last 16 channels of
     a window are the next pixel's first 16 and meet all-zero weight columns.  (i) the stem buffer holds the 48 channels of the fp32 reference, nothing else;

@@ -281,7 +281,41 @@ def test_c_abi_argument_validation_reports_errors_without_a_gpu():
     assert lib.vgh_conv_num_cfgs() > 70 and lib.vgh_conv_cfg_name(19).decode().startswith("p8x40")
 
 
+def test_net_create_refuses_a_program_before_its_first_hip_call():
+    """vgh_net_create plans the program (csrc/net_plan.h) before it touches a device, so a refused program allocates nothing: the answer is VGH_ERR_INVALID with the
+    program's message -- with or without a GPU -- and never a HIP error.  (No valid program here: that one would go on to the device.)"""
+    import ctypes as C
+
+    from head_detector_amd import _lib
+
+    lib = _lib.load()
+    CONV, POOL, BF16 = 1, 2, 0
+
+    def conv(in_buf, cin, out_buf, cout, **kw):
+        return _lib.OpDesc(**{**dict(kind=CONV, in_buf=in_buf, cin=cin, out_buf=out_buf, cout_pad=cout, cout_store=cout, out_split=cout, res_buf=-1, ksize=1, stride=1, act=1, force_cfg=-1), **kw})
+
+    def refused(bufs, ops, weights, n_weights=None):
+        b, o = (_lib.BufDesc * len(bufs))(*bufs), (_lib.OpDesc * len(ops))(*ops)
+        w, bias, net = np.ascontiguousarray(weights, np.float32), np.zeros(256, np.float32), C.c_void_p(0xdead)
+        rc = lib.vgh_net_create(0, 32, 1, b, len(bufs), o, len(ops), w.ctypes.data, w.size if n_weights is None else n_weights, bias.ctypes.data, bias.size, C.byref(net))
+        assert rc == -1 and net.value == 0xdead, (rc, lib.vgh_last_error())  # VGH_ERR_INVALID (a HIP error is -2), and no handle
+        m = lib.vgh_last_error().decode()
+        assert "hip" not in m.lower() and "ROCm" not in m, m
+        return m
+
+    bufs = [_lib.BufDesc(8, 8, 48, BF16, 0.0), _lib.BufDesc(8, 8, 32, BF16, 0.0)]
+    # the program of test_stem_tensor_at_its_48_channel_pitch (iii) in miniature: a 48-channel pitch read as cin = 64 with a weight on input channel 50
+    w = np.zeros((32, 64), np.float32)
+    w[:, :48] = 1.0
+    w[5, 50] = 0.25
+    assert refused(bufs, [conv(0, 64, 1, 32)], w) == "net_create: op 0 reads 64 channels of a 48-channel pitch with a non-zero weight at input channel 50"
+    w[5, 50] = 0.0
+    assert refused(bufs, [conv(0, 32, 1, 32), _lib.OpDesc(kind=POOL, in_buf=2, cin=32)], w) == "net_create: op 1 buffer ids"  # a pool op's buffer id
+    assert refused(bufs, [conv(0, 32, 1, 32)], w, n_weights=32 * 32 - 1) == "net_create: op 0 weight range"  # one float short
+
+
 def test_ping_pong_tiles_qualify_only_for_their_conv_class():
+
     """vgh_conv_cfg_ok (host logic, no GPU): the g / h tiles of csrc/conv_pp.hip take 3x3 / stride-1 bf16 convs with the 16-byte epilogue whose cout_pad is a
     multiple of their cout tile -- what the tuner and the table loader rely on when a key names one."""
     from head_detector_amd import _lib
