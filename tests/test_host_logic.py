@@ -1089,7 +1089,9 @@ def test_per_op_checker_and_a_truncated_bf16_tensor_known_limit(small_forward):
     """One bf16 tensor stored by TRUNCATION instead of round-to-nearest.  KNOWN LIMIT: it is caught neither at the op itself nor at a consumer.  At the op: truncation is
     off by less than one bf16 ulp (2^-7 of the value at most), and the project's bf16 tolerance allows two (2e-2 + |e| / 64: an accumulation order may cross a rounding
     boundary).  At a consumer: every op is judged on the forward's OWN inputs, so a consumer sees the truncated tensor on both sides.  What bounds such a systematic
-    half-ulp bias is the end-to-end deviation tests, not the per-op check.  Should a tighter tolerance ever catch it, it has to be at the op it was planted in."""
+    half-ulp bias is the end-to-end deviation tests, not the per-op check.  Should a tighter tolerance ever catch it, it has to be at the op it was planted in.
+    The rounding of every conv tile's store is pinned to the bit by tests/test_gpu_conv_exact.py (exact-arithmetic operands, one launch per tile and store path); the
+    limit that remains is this per-op checker's, on whole networks."""
     P, _, full, chains = small_forward
     op = _first(P, chains, lambda o: o["ksize"] == 3 and o["stride"] == 1 and o["res_buf"] < 0)
 
