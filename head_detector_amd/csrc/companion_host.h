@@ -1,5 +1,6 @@
 // The host plumbing of the six companion libraries (libvghview.so: csrc/aligned.hip, csrc/draw.hip, csrc/mesh_render.hip; libvghvis.so: csrc/visibility.hip;
-// libvghtex.so: csrc/texture.hip; libvgheval.so: csrc/mesh_metrics.hip, csrc/detection_ap.hip; libvghmerge.so: csrc/slice_merge.hip; libvghtrack.so: csrc/head_track.hip): the return codes, the calling thread's error message, the check / require macros of
+// libvghtex.so: csrc/texture.hip; libvgheval.so: csrc/mesh_metrics.hip, csrc/detection_ap.hip; libvghmerge.so: csrc/slice_merge.hip; libvghtrack.so: csrc/head_track.hip)
+// and of the application library libvghanon.so (csrc/anonymize.hip): the return codes, the calling thread's error message, the check / require macros of
 // the C entry points, the per-device staging block and the queue-then-record discipline around it.  Host-only, header-only and internal: everything is
 // inline, and the companions are built with -fvisibility=hidden, so the sources of one library share one message and no library exports any of this or
 // sees another's.  Nothing of libvgh.so (csrc/vgh_internal.h) is used here and libvgh.so uses nothing of this.

@@ -14,7 +14,8 @@ and the heads' surface with Sim3DR's ``render_texture`` (csrc/texture.hip, libvg
 texture map out of the image, the second paints textures back onto the heads; both need ``faces`` and a per-vertex UV layout (``texture.cylindrical_uv``
 makes one from the template mesh).  ``compare_meshes`` judges the heads against ground-truth meshes with the reference's benchmark metrics (Z_n, chamfer;
 csrc/mesh_metrics.hip, libvgheval.so, ``head_detector_amd.mesh_metrics``).  ``detection_rows`` gives the boxes as the detection benchmarks take them
-(``head_detector_amd.detection_metrics``: COCO-style AP, csrc/detection_ap.hip)."""
+(``head_detector_amd.detection_metrics``: COCO-style AP, csrc/detection_ap.hip).  ``anonymize`` returns the image with every head pixelated, blurred or filled, by
+box, ellipse or mesh silhouette (csrc/anonymize.hip, libvghanon.so, ``head_detector_amd.anonymize``): integer arithmetic only, a later head owns an overlap."""
 from __future__ import annotations
 
 import os
@@ -53,6 +54,19 @@ class PredictionResult:
         from .mesh_render import render_mesh
 
         return render_mesh(self.original_image, self.heads, self._faces, alpha=alpha, color=color, ambient=ambient, diffuse=diffuse, light=light, to_host=to_host)
+
+    def anonymize(self, method: str = "pixelate", region: str = "ellipse", *, margin: float = 0.1, cells: int = 8, strength: float = 0.1, color=(0, 0, 0), faces=None,
+                  to_host: bool = True):
+        """A NEW uint8 [H, W, 3] image: the original with every head hidden (csrc/anonymize.hip, libvghanon.so, ``head_detector_amd.anonymize`` states the
+        rules).  ``method``: "pixelate" (``cells`` cells along the longer side), "blur" (an integer Gaussian of sigma ``strength`` times the longer side) or
+        "fill" (``color``).  ``region``: "box" (the ``bbox`` grown by ``margin``), "ellipse" (inscribed in that box) or "mesh" (the head's own silhouette as
+        ``get_visibility`` sees it; needs ``faces``, the FLAME model's own unless given; hair lies outside it).  A later head owns the pixels it shares with
+        an earlier one.  The original is never modified; a GPU ``original_image`` is used where it is.  ``to_host=False`` returns a GPU ``torch.uint8``
+        tensor.  Writing the result back into YUV planes is out of scope."""
+        from .anonymize import anonymize_heads
+
+        return anonymize_heads(self.original_image, self.heads, method, region, margin=margin, cells=cells, strength=strength, color=color,
+                               faces=self._faces if faces is None else faces, to_host=to_host)
 
     def get_visibility(self, occlusion: str = "order", barycentric: bool = False, to_host: bool = True):
         """A ``visibility.HeadVisibility``: Sim3DR's ``rasterize_triangles`` over every head's mesh (the FLAME model's own triangles, ``faces``), depth = -z
