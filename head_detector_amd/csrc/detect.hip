@@ -31,6 +31,14 @@ struct vgh_detector {
     // lazy FLAME gather (r06, vgh_detector_set_lazy_flame): the candidate stage gathers boxes only; the 413-vectors of the SURVIVORS are built by the select from the
     // prediction buffers (106 MB of candidate vectors per 64 images for ~3 survivors per image otherwise).
     bool lazy_flame = false;
+    // deferred FLAME predictions: the net's plan marks the 1x1 convs that write the FLAME channels of every level's prediction rows as deferrable, and together they
+    // write exactly those channels (rows_ok, decided at create).  The lazy gather then turns the net's defer switch on: its forwards skip those convs, and the select
+    // computes the survivors' rows from the convs' inputs (vgh_survivor_rows) instead of reading dense prediction rows.  Every eager stage runs the pending convs first.
+    bool rows_ok = false;
+    bool defer_allowed = true;  // vgh_detector_set_lazy_flame(d, 2) keeps the lazy gather on dense prediction rows (A/B, tests)
+    bool rows_on() const { return rows_ok && defer_allowed; }
+    vgh_row_op row_ops[VGH_MAX_LEVELS * kMaxRowOps] = {};
+    int n_row_ops[VGH_MAX_LEVELS] = {};
     // Where a select finds the 413-vectors of candidate row r (row_src[r], one byte per row of max_batch):
     //   SRC_NONE   nothing decoded into the row yet, or a lazy decode whose rows were since given up (a shorter lazy decode took its place)
     //   SRC_EAGER  cand_flame[r] was written together with cand_boxes[r] / cand_scores[r]
@@ -144,6 +152,24 @@ int vgh_detector_create(vgh_net* net, vgh_flame* flame, const vgh_detect_cfg* cf
         A += cfg->level_h[l] * cfg->level_w[l];
     }
     d->A = A;
+    {
+        const int width = cfg->shape_live + cfg->expr_live + 13;
+        bool ok = true;
+        for (int l = 0; l < cfg->n_levels && ok; ++l) {
+            vgh_row_op* ro = d->row_ops + l * kMaxRowOps;
+            const int k = d->n_row_ops[l] = vgh_net_row_ops(net, cfg->level_buf[l], ro, kMaxRowOps);
+            ok = k >= 1;
+            int stored = 0;
+            for (int i = 0; i < k && ok; ++i) {
+                ok = vgh_row_op_ok(ro[i], width);
+                stored += ro[i].cout_store;
+                for (int j = 0; j < i && ok; ++j)  // disjoint channel ranges that add up to the width: exactly the FLAME channels
+                    ok = ro[i].out_coff + ro[i].cout_store <= ro[j].out_coff || ro[j].out_coff + ro[j].cout_store <= ro[i].out_coff;
+            }
+            ok = ok && stored == width;
+        }
+        d->rows_ok = ok;
+    }
     d->row_src.assign((size_t)cfg->max_batch, vgh_detector::SRC_NONE);
     if (cfg->pre_k > A) {
         delete d;
@@ -237,12 +263,15 @@ int vgh_detector_decode_candidates(vgh_detector* d, int n, int at, void* stream)
     const vgh_detect_cfg& c = d->cfg;
     vgh_head_level lv[VGH_MAX_LEVELS];
     for (int l = 0; l < c.n_levels; ++l) {
-        lv[l].pred_dev = (const float*)vgh_net_buffer(d->net, c.level_buf[l]);
+        lv[l].pred_dev = (const float*)vgh_net_buffer_ptr(d->net, c.level_buf[l]);
         lv[l].h = c.level_h[l];
         lv[l].w = c.level_w[l];
         lv[l].pitch = c.level_pitch[l];
         lv[l].stride = c.level_stride[l];
     }
+    const bool lazy = d->lazy_flame && at == 0;  // (rows at > 0 belong to a chunked batch)
+    if (!(lazy && d->rows_on()))  // this stage (or a select behind it) reads dense FLAME rows: the convs a deferring forward left pending run now, behind that forward
+        if (int rc0 = vgh_net_run_deferred(d->net, stream)) return rc0;
     void* st = stream;
     if (d->overlap) {  // predictions ready on `stream` -> side stream (ordered after everything queued there, incl. the last select)
         if (int rc0 = ensure_side(d, (hipStream_t)stream)) return rc0;
@@ -256,7 +285,6 @@ int vgh_detector_decode_candidates(vgh_detector* d, int n, int at, void* stream)
     int rc;
     if ((rc = vgh_head_decode(lv, c.n_levels, n, ba, sa, st))) return rc;
     if ((rc = vgh_topk(sa, n, d->A, c.pre_k, ix, d->cand_scores + (size_t)at * c.pre_k, st))) return rc;
-    const bool lazy = d->lazy_flame && at == 0;  // (rows at > 0 belong to a chunked batch)
     if ((rc = vgh_gather_candidates(lv, c.n_levels, n, d->A, c.shape_live, c.expr_live, ba, ix, c.pre_k, d->cand_boxes + (size_t)at * c.pre_k * 4,
                                     lazy ? nullptr : d->cand_flame + (size_t)at * c.pre_k * VGH_NUM_FLAME_PARAMS, st)))
         return rc;
@@ -329,10 +357,15 @@ static int select_on(vgh_detector* d, int B, float conf_thr, float iou_thr, vgh_
                 "buffers no longer hold that batch (queue the select before the next forward, or decode with the lazy FLAME gather off)",
                 (unsigned long long)d->lazy_gen, (unsigned long long)(vgh_net_generation(d->net) - d->lazy_gen));
     VGH_REQUIRE(!lazy || c.keep_k <= 1024, "detector_select: the lazy FLAME gather needs keep_k <= 1024");
+    if (lazy && !d->rows_on())  // dense rows are read below: convs that this generation's forward left pending (the switch was turned since) run first, behind the candidate stage
+        if ((rc = vgh_net_run_deferred(d->net, stream))) return rc;
+    // the survivors' rows are computed from the towers' outputs where this generation's forward left the prediction convs pending; where it ran them (the switch was
+    // off then, or an eager stage has run them since) the dense rows are complete and are read as before
+    const bool rows = lazy && d->rows_on() && vgh_net_deferred_pending(d->net);
     if (c.keep_k <= 1024) {  // r06: NMS + compaction + head list as one launch
         vgh_head_level lv[VGH_MAX_LEVELS];
         for (int l = 0; l < c.n_levels; ++l) {
-            lv[l].pred_dev = (const float*)vgh_net_buffer(d->net, c.level_buf[l]);
+            lv[l].pred_dev = (const float*)vgh_net_buffer_ptr(d->net, c.level_buf[l]);
             lv[l].h = c.level_h[l];
             lv[l].w = c.level_w[l];
             lv[l].pitch = c.level_pitch[l];
@@ -340,8 +373,12 @@ static int select_on(vgh_detector* d, int B, float conf_thr, float iou_thr, vgh_
         }
         if ((rc = vgh_nms_select(d->cand_boxes, d->cand_scores, d->cand_flame, B, c.pre_k, conf_thr, iou_thr, c.keep_k, d->keep_idx, o->counts_dev, o->boxes_dev,
                                  o->scores_dev, o->flame_dev, capacity, want_heads ? d->head_row : nullptr, himg, o->n_heads_dev, d->ticket, lazy ? lv : nullptr,
-                                 c.n_levels, lazy ? d->idx : nullptr, c.shape_live, c.expr_live, stream)))
+                                 c.n_levels, lazy ? d->idx : nullptr, c.shape_live, c.expr_live, stream, rows)))
             return rc;
+        if (rows)
+            if ((rc = vgh_survivor_rows(lv, c.n_levels, d->row_ops, d->n_row_ops, B, c.pre_k, c.keep_k, d->idx, d->keep_idx, o->counts_dev, c.shape_live, c.expr_live, o->flame_dev,
+                                        stream)))
+                return rc;
         if (lazy && d->overlap && stream == (void*)d->side) {
             // the select has just read the prediction buffers: the next forward's guard moves behind it (same event, recorded again; the net waits for the latest record).
             // A forward queued BEFORE this select never saw that record -- which is why select_on refuses a lazy source whose generation has passed.
@@ -413,7 +450,8 @@ int vgh_detector_set_overlap(vgh_detector* d, int enable) {
 int vgh_detector_set_lazy_flame(vgh_detector* d, int enable) {
     VGH_REQUIRE(d, "detector_set_lazy_flame: null handle");
     d->lazy_flame = enable != 0;
-    return VGH_OK;
+    d->defer_allowed = enable != 2;  // 2: the lazy gather on dense prediction rows
+    return d->rows_ok ? vgh_net_set_defer(d->net, d->lazy_flame && d->defer_allowed) : VGH_OK;  // from the next forward on
 }
 
 int vgh_detector_streams(vgh_detector* d, void* main_stream, void** out) {

@@ -33,7 +33,7 @@ struct NetOp {
     uint16_t* wds = nullptr;   // stage-1 downsample only: its weights in the fused stem + downsample kernel's layout (stem_ds.hip)
     float* gscale = nullptr;   // device [cout_pad] (NetPlan::Op::gscale), else nullptr
     float* dvec = nullptr;     // device [cout_pad] (NetPlan::Op::dvec), else nullptr
-    int overhang_ok = 0, b2b = 0;  // as planned (NetPlan::Op)
+    int overhang_ok = 0, b2b = 0, deferrable = 0;  // as planned (NetPlan::Op)
     hipEvent_t ev_done = nullptr;  // recorded behind this op when the plan says a later op waits for it (NetPlan::Op::ev_done), else nullptr
 };
 
@@ -71,6 +71,13 @@ struct vgh_net {
     // forward generation: bumped by every call that (re)writes the prediction buffers -- vgh_net_forward (and with it every chunk of vgh_detector_candidates and the
     // capture's recording pass), vgh_net_forward_graph, vgh_net_profile.  A detector's lazy FLAME gather remembers the generation it decoded and its select refuses another one
     uint64_t generation = 0;
+    // deferred prediction ops (vgh_net_set_defer, NetPlan::Op::deferrable): a deferring forward skips them and leaves them pending for vgh_net_run_deferred; their
+    // inputs (the last tensors of the FLAME towers) stay intact in the arena until the next forward.  `skipping`: true while such a forward queues its ops
+    DeferState defer;
+    bool skipping = false;
+    bool graph_skips = false;  // what the captured graph does, whatever the switch says at replay
+    int graph_B = 0;
+    hipStream_t last_stream = nullptr;  // the caller's stream of the latest forward / replay: where vgh_net_buffer queues convs that forward left pending
     int fuse_stem = 0;  // opt-in (vgh_net_set_fuse_stem): measured r03, the fused kernel saves 1.5 GB of HBM traffic per L b64 forward but no time (EXPERIMENTS.md 8c)
 };
 
@@ -156,6 +163,7 @@ static int net_run_op(vgh_net* n, const NetOp& op, const void* image0, int fmt, 
         case VGH_OP_CONV: {
             if ((fused || stem3) && op_index == n->stem_pair + 1) return VGH_OK;  // ran inside the stem's launch
             if (n->fuse_b2b && op.b2b == 2) return VGH_OK;             // ran inside the previous conv's launch
+            if (n->skipping && op.deferrable) return VGH_OK;           // left pending for vgh_net_run_deferred
             ConvArgs a;
             if (int rc = net_conv_args(n, op, B, at, &a)) return rc;
             a.grid_share = share;
@@ -397,6 +405,7 @@ int vgh_net_create(int device, int image_size, int max_batch, const vgh_buf_desc
         op.out_scale = oscale[i];
         op.overhang_ok = po.overhang_ok;
         op.b2b = po.b2b;
+        op.deferrable = po.deferrable;
         if (ops[i].kind == VGH_OP_CONV || ops[i].kind == VGH_OP_STEM) {
             op.wf32 = (float*)(n->wblob + po.w);  // conv: the same storage as wpack, bf16 image (throughput mode) or dense fp32 (parity mode)
             op.bias = (float*)(n->wblob + po.bias);
@@ -460,6 +469,13 @@ int vgh_net_forward(vgh_net* n, const void* image_dev, int image_fmt, int B, voi
     // the main stream at the end (also valid under stream capture: the graph gets parallel branches).
     hipStream_t main = (hipStream_t)stream;
     ++n->generation;  // before anything is queued: a forward that fails half-way has touched the prediction buffers too
+    n->defer.forward(B, n->defer.skip());
+    n->last_stream = main;
+    struct Skipping {  // cleared on every return path
+        vgh_net* n;
+        ~Skipping() { n->skipping = false; }
+    } skipping{n};
+    n->skipping = n->defer.pending;
     if (int rc = ensure_lanes(n, main)) return rc;
     if (n->nsplit > 1 && B > 1) return net_forward_split(n, image_dev, image_fmt, B, main);
     bool pending[vgh_net::kLanes] = {false, false, false, false}, used[vgh_net::kLanes] = {false, false, false, false};
@@ -506,6 +522,7 @@ int vgh_net_profile(vgh_net* n, const void* image_dev, int image_fmt, int B, voi
     VGH_REQUIRE(B >= 0 && B <= n->max_batch, "net_profile: B=%d exceeds max_batch=%d", B, n->max_batch);
     hipStream_t st = (hipStream_t)stream;
     ++n->generation;
+    n->defer.forward(B, false);  // the profiler runs every op: dense prediction buffers, nothing pending
     if (int rc = ensure_lanes(n, st)) return rc;
     const size_t m = n->ops.size();
     struct Events {  // destroyed on every return path
@@ -563,6 +580,9 @@ int vgh_net_capture(vgh_net* n, const void* image_dev, int image_fmt, int B, voi
     if (int rc = ensure_lanes(n, st)) return rc;  // probing launches kernels: before the capture begins
     VGH_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     int rc = vgh_net_forward(n, image_dev, image_fmt, B, stream);
+    n->graph_skips = n->defer.pending;
+    n->graph_B = B;
+    n->defer.forward(0, false);  // the recording pass ran nothing: no tower outputs of this generation to run deferred ops on
     hipError_t e = hipStreamEndCapture(st, &n->graph);
     if (rc) return rc;
     VGH_HIP(e);
@@ -574,11 +594,44 @@ int vgh_net_forward_graph(vgh_net* n, void* stream) {
     VGH_REQUIRE(n && n->graph_exec, "net_forward_graph: call vgh_net_capture first");
     VGH_REQUIRE(!n->pred_guard, "net_forward_graph: a prediction guard event is set (detector overlap mode); use vgh_net_forward");
     ++n->generation;
+    n->defer.forward(n->graph_B, n->graph_skips);
+    n->last_stream = (hipStream_t)stream;
     VGH_HIP(hipGraphLaunch(n->graph_exec, (hipStream_t)stream));
     return VGH_OK;
 }
 
-void* vgh_net_buffer(vgh_net* n, int buf_id) { return (n && buf_id >= 0 && buf_id < (int)n->buf_ptr.size()) ? n->buf_ptr[buf_id] : nullptr; }
+int vgh_net_set_defer(vgh_net* n, int on) {
+    VGH_REQUIRE(n, "net_set_defer: null handle");
+    n->defer.on = on != 0;  // from the next forward on; ops left pending by an earlier one stay pending
+    return VGH_OK;
+}
+
+int vgh_net_run_deferred(vgh_net* n, void* stream) {
+    VGH_REQUIRE(n, "net_run_deferred: null handle");
+    const int B = n->defer.take();
+    if (B == 0) return VGH_OK;
+    // one launch per op for the whole batch, on the stream the forward was joined into: the op's tile is the one chosen for the arena batch (NetOp::auto_cfg),
+    // so the rows are the bits a forward that runs the op itself writes, whatever its batch split
+    for (const NetOp& op : n->ops)
+        if (op.deferrable)
+            if (int rc = net_run_op(n, op, nullptr, VGH_IMG_U8_NHWC, B, 0, (hipStream_t)stream)) return rc;
+    return VGH_OK;
+}
+
+int vgh_net_deferred_pending(vgh_net* n) { return n && n->defer.pending ? 1 : 0; }
+
+void* vgh_net_buffer_ptr(vgh_net* n, int buf_id) { return (n && buf_id >= 0 && buf_id < (int)n->buf_ptr.size()) ? n->buf_ptr[buf_id] : nullptr; }
+// dense buffers are handed out complete: convs that the latest forward left pending (vgh_net_set_defer) and that write this buffer are queued first, behind that forward
+void* vgh_net_buffer(vgh_net* n, int buf_id) {
+    void* p = vgh_net_buffer_ptr(n, buf_id);
+    if (p && n->defer.pending)
+        for (const NetOp& op : n->ops)
+            if (op.deferrable && op.d.out_buf == buf_id) {
+                if (vgh_net_run_deferred(n, n->last_stream)) return nullptr;  // (vgh_last_error says why)
+                break;
+            }
+    return p;
+}
 int64_t vgh_net_buffer_bytes(vgh_net* n, int buf_id) { return (n && buf_id >= 0 && buf_id < (int)n->buf_bytes.size()) ? n->buf_bytes[buf_id] : -1; }
 
 #ifdef VGH_EXPERIMENTS
@@ -628,6 +681,18 @@ int vgh_net_b2b_pairs(vgh_net* n) {
 }
 
 uint64_t vgh_net_generation(vgh_net* n) { return n ? n->generation : 0; }
+
+int vgh_net_row_ops(vgh_net* n, int out_buf, vgh_row_op* out, int max_ops) {
+    if (!n || !out) return -1;
+    int k = 0;
+    for (const NetOp& op : n->ops) {
+        if (!op.deferrable || op.d.out_buf != out_buf) continue;
+        if (k == max_ops) return -1;
+        const vgh_buf_desc& ib = n->bufs[op.d.in_buf];
+        out[k++] = vgh_row_op{(const uint16_t*)n->buf_ptr[op.d.in_buf], op.wpack, op.bias, ib.pitch, op.d.in_coff, op.d.cin / 32, op.d.cout_pad, op.d.cout_store, op.d.out_coff, op.d.act};
+    }
+    return k;
+}
 int vgh_net_max_batch(vgh_net* n) { return n ? n->max_batch : 0; }
 int vgh_net_device(vgh_net* n) { return n ? n->device : 0; }
 int vgh_net_image_size(vgh_net* n) { return n ? n->image_size : 0; }

@@ -97,6 +97,50 @@ inline bool sole_link(const vgh_op_desc* ops, int n_ops, int i, int buf) {
     return true;
 }
 
+// Deferrable op (vgh_net_set_defer): a plain 1x1 / stride-1 bf16 conv that writes FLAME channels (VGH_PRED_FLAME_OFF and up: the box / score channels below are
+// needed densely by the top-k) of an fp32 buffer which NO op of the program reads -- its rows reach the post-network stages only.  A pointwise conv: any row can be
+// computed later, alone, from the row of its input -- which therefore has to survive the forward (no later op writes it) and must not be rewritten by the NEXT
+// forward before the prediction guard has been waited for (every writer of the input stands behind the first conv with an fp32 output, where the executor waits).
+// `fused_or_awaited`: the op is part of a back-to-back pair, a later op waits for its event, or its K window overhangs the pitch.
+inline bool net_op_deferrable(const vgh_buf_desc* bufs, const vgh_op_desc* ops, int n_ops, int i, bool fused_or_awaited) {
+    const vgh_op_desc& d = ops[i];
+    if (d.kind != VGH_OP_CONV || d.ksize != 1 || d.stride != 1 || fused_or_awaited) return false;
+    if (bufs[d.out_buf].is_f32 != VGH_FMT_F32 || bufs[d.in_buf].is_f32 != VGH_FMT_BF16) return false;
+    if (d.res_buf >= 0 || d.shuffle || d.grp_cout || d.act == VGH_ACT_SILU || d.out_coff < VGH_PRED_FLAME_OFF || d.out_split < d.cout_pad || d.cout_store > d.cout_pad) return false;
+    int first_f32 = n_ops;
+    for (int j = n_ops - 1; j >= 0; --j)
+        if (ops[j].kind == VGH_OP_CONV && bufs[ops[j].out_buf].is_f32 == VGH_FMT_F32) first_f32 = j;
+    for (int j = 0; j < n_ops; ++j) {
+        const vgh_op_desc& e = ops[j];
+        if (e.kind == VGH_OP_FORK) continue;
+        const bool conv = e.kind == VGH_OP_CONV;
+        if ((conv || e.kind == VGH_OP_SPP_POOL) && e.in_buf == d.out_buf) return false;  // a second reader of the prediction buffer
+        if (conv && e.res_buf == d.out_buf) return false;
+        const bool writes_in = (conv || e.kind == VGH_OP_STEM) ? e.out_buf == d.in_buf : e.kind == VGH_OP_SPP_POOL && e.in_buf == d.in_buf;  // (the pool writes behind the channels it reads)
+        if (writes_in && (j > i || j < first_f32)) return false;
+    }
+    return true;
+}
+
+// Pending state of the deferred ops, per forward generation: a deferring forward of B images leaves them pending; vgh_net_run_deferred takes them (once); a forward
+// that runs every op, or the next deferring forward, replaces the state.
+struct DeferState {
+    bool on = false;       // vgh_net_set_defer
+    bool pending = false;  // the current generation's deferrable ops have not run
+    int B = 0;             // images of that forward
+    bool skip() const { return on; }  // does a forward queued now skip the deferrable ops?
+    void forward(int batch, bool skipped) {
+        pending = skipped;
+        B = skipped ? batch : 0;
+    }
+    int take() {  // the batch to run the deferred ops for, 0 = nothing pending; clears the mark
+        const int b = pending ? B : 0;
+        pending = false;
+        B = 0;
+        return b;
+    }
+};
+
 struct NetPlan {
     // arena: one slab, every buffer live for the whole forward (288 GB HBM: no aliasing games), in buffer order
     std::vector<int64_t> buf_off, buf_bytes;  // buf_bytes: the tensor for max_batch, without the slack behind it
@@ -108,6 +152,7 @@ struct NetPlan {
         int b2b = 0;                 // back-to-back GEMM: 1 = this conv and the NEXT op (a 1x1 / stride-1 conv, the only reader of its output) run as ONE launch, 2 = that second conv
         int overhang_ok = 0;         // the K window is wider than the input buffer's pitch, over weight columns verified to be exactly zero
         int ev_done = 0;             // a later op names this one as its producer (vgh_op_desc.lane bits 8+): an event is recorded behind it
+        int deferrable = 0;          // a prediction 1x1 conv whose fp32 rows only the post-network stages read (net_op_deferrable): a deferring forward skips it
     };
     std::vector<Op> ops;
     int64_t wds = -1;         // -DVGH_EXPERIMENTS builds: the stage-1 downsample's second weight image (stem_ds.hip), else -1
@@ -229,6 +274,10 @@ inline int net_plan(int image_size, int max_batch, const vgh_buf_desc* bufs, int
         for (int a = 1; a < kNetLanes; ++a)
             for (int b = 1; b < kNetLanes; ++b) w[a][b] = w[a][b] || (w[a][k] && w[k][b]);
     for (int a = 1; a < kNetLanes; ++a) p->lane_wait_cycle = p->lane_wait_cycle || w[a][a];
+    for (int i = 0; i < n_ops; ++i) {
+        const NetPlan::Op& o = p->ops[i];
+        p->ops[i].deferrable = net_op_deferrable(bufs, ops, n_ops, i, o.b2b || o.ev_done || o.overhang_ok) && ops[i].out_coff + ops[i].cout_store <= bufs[ops[i].out_buf].pitch ? 1 : 0;
+    }
     return VGH_OK;
 #undef PLAN_REQUIRE
 }

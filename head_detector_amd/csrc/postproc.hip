@@ -198,10 +198,10 @@ __global__ __launch_bounds__(1024) void topk_kernel(const float* __restrict__ sc
 }
 
 // ---- K6b: gather boxes + FLAME 413-vector for selected anchors ----------------------------------
-// channel c of the reference's 413-vector for the anchor whose prediction row is `pr` (yolo_head_dfl_head.py:162-184, yolo_head_ndfl_heads.py:143-172): tanh * 3 on the
+// channel c of the reference's 413-vector for the anchor whose prediction row has the FLAME segment `pf` (channel VGH_PRED_FLAME_OFF and up of the row) (yolo_head_dfl_head.py:162-184, yolo_head_ndfl_heads.py:143-172): tanh * 3 on the
 // live shape / expression channels (zeros behind them), the rotation / jaw permutation, translation += anchor centre * stride, exp(scale) / 0.05 * stride
 __device__ __forceinline__ float flame_channel(const float* __restrict__ pr, int c, int S, int E, int ax, int ay, float st) {
-    const int o_shape = VGH_PRED_FLAME_OFF, o_expr = o_shape + S, o_rot = o_expr + E, o_jaw = o_rot + 6, o_tr = o_jaw + 3, o_sc = o_tr + 3;
+    const int o_shape = 0, o_expr = o_shape + S, o_rot = o_expr + E, o_jaw = o_rot + 6, o_tr = o_jaw + 3, o_sc = o_tr + 3;
     float v = 0.0f;
     if (c < 300) {
         if (c < S) v = tanhf(pr[o_shape + c]) * 3.0f;
@@ -240,7 +240,7 @@ __global__ __launch_bounds__(256) void gather_kernel(Levels L, int A, int S, int
     if (lane < 4) out_boxes[((int64_t)b * k + j) * 4 + lane] = boxes[((int64_t)b * A + a) * 4 + lane];
     if (!out_flame) return;  // lazy mode (vgh_detector_set_lazy_flame): the 413-vector is built for the SURVIVORS only, inside nms_select_kernel
     float* of = out_flame + ((int64_t)b * k + j) * VGH_NUM_FLAME_PARAMS;
-    for (int c = lane; c < VGH_NUM_FLAME_PARAMS; c += 64) of[c] = flame_channel(pr, c, S, E, ax, ay, st);
+    for (int c = lane; c < VGH_NUM_FLAME_PARAMS; c += 64) of[c] = flame_channel(pr + VGH_PRED_FLAME_OFF, c, S, E, ax, ay, st);
 }
 
 // ---- K8: conf filter + greedy NMS + keep-k -------------------------------------------------------
@@ -322,7 +322,7 @@ __global__ __launch_bounds__(1024) void nms_select_kernel(const float* __restric
                                                           float conf, float thr, int keep_k, int32_t* __restrict__ keep_idx, int32_t* __restrict__ counts,
                                                           float* __restrict__ ob, float* __restrict__ os, float* __restrict__ of, int B, int capacity,
                                                           int32_t* __restrict__ head_row, int32_t* __restrict__ head_image, int32_t* __restrict__ n_heads,
-                                                          int32_t* __restrict__ ticket, Levels L, const int32_t* __restrict__ lazy_idx, int S, int E) {
+                                                          int32_t* __restrict__ ticket, Levels L, const int32_t* __restrict__ lazy_idx, int S, int E, int rows_later) {
     __shared__ float4 sb[1024];
     __shared__ unsigned long long removed[16];
     __shared__ int s_keep[1024];
@@ -346,7 +346,7 @@ __global__ __launch_bounds__(1024) void nms_select_kernel(const float* __restric
         const int64_t sr = (int64_t)b * n_in + s_keep[j];
         if (lane < 4) ob[o * 4 + lane] = boxes[sr * 4 + lane];
         if (lane == 0) os[o] = scores[sr];
-        if (of) {
+        if (of && !rows_later) {  // (rows_later: survivor_rows_kernel, queued behind this launch, writes the survivors' vectors)
             if (lazy_idx) {  // lazy mode: the candidate tensor was never filled; the survivor's vector straight from its prediction row (gather_kernel's arithmetic)
                 const int a = lazy_idx[sr];
                 const int l = find_level(L, a);
@@ -354,7 +354,7 @@ __global__ __launch_bounds__(1024) void nms_select_kernel(const float* __restric
                 const float* pr = L.pred[l] + ((int64_t)b * (L.h[l] * L.w[l]) + p) * L.pitch[l];
                 const int ay = p / L.w[l], ax = p - ay * L.w[l];
                 const float st = (float)L.stride[l];
-                for (int c = lane; c < VGH_NUM_FLAME_PARAMS; c += 64) of[o * VGH_NUM_FLAME_PARAMS + c] = flame_channel(pr, c, S, E, ax, ay, st);
+                for (int c = lane; c < VGH_NUM_FLAME_PARAMS; c += 64) of[o * VGH_NUM_FLAME_PARAMS + c] = flame_channel(pr + VGH_PRED_FLAME_OFF, c, S, E, ax, ay, st);
             } else {
                 for (int c = lane; c < VGH_NUM_FLAME_PARAMS; c += 64) of[o * VGH_NUM_FLAME_PARAMS + c] = flame[sr * VGH_NUM_FLAME_PARAMS + c];
             }
@@ -446,6 +446,94 @@ __global__ __launch_bounds__(64) void compact_indirect_kernel(const float* __res
         for (int c = lane; c < flame_w; c += 64) of[o * flame_w + c] = flame[s * flame_w + c];
 }
 
+// ---- the FLAME prediction rows of the NMS survivors, computed on demand ----------------------------
+// The last layer of the FLAME towers is a set of 1x1 convs with fp32 output (heads.head*.flame_*_pred.3): pointwise, so the rows the select needs -- a handful per
+// image out of 8 400 -- can be computed alone from the survivors' rows of the towers' last bf16 tensors, and a forward that defers those convs (vgh_net_set_defer)
+// never writes or reads the dense rows.  Bit for bit what the implicit-GEMM tiles (conv_kernels.inc, conv_igemm_kernel) write: the same 32x32x16 bf16 MFMA with the
+// weights as A (32 couts) and the pixels as B (here: 32 survivors, missing ones as zero columns that are thrown away), accumulators from zero, the 32-channel
+// k-blocks in ascending order and the two 16-channel halves of each in order, the bias added in fp32 afterwards, the activation as one max against act_bound.  An
+// output element of the MFMA depends on its own weight row and pixel column only, so where the pixel stands in the tile does not matter; nor does the tile of the
+// table (they differ in how many k-blocks a stage holds and in who stores what, not in this chain).
+struct RowOps {
+    Levels L;
+    vgh_row_op op[MAX_LEVELS][kMaxRowOps];
+    int n[MAX_LEVELS];
+};
+constexpr int ROW_W = 416;  // floats per staged row: 300 + 100 + 13 FLAME channels at most, rounded up to 16 bytes
+
+// grid (ceil(keep_k / 32), B), 256 threads: block (g, b) takes survivors [32 g, 32 g + 32) of image b and leaves at once when the image has fewer.  Lane & 31 = the
+// survivor (in every wave), the four waves share the (op, 32-cout tile) units of a level; the rows meet in LDS, then wave w writes survivors w, w + 4, ...
+__global__ __launch_bounds__(256) void survivor_rows_kernel(const RowOps R, int n_in, int keep_k, const int32_t* __restrict__ idx, const int32_t* __restrict__ keep_idx,
+                                                            const int32_t* __restrict__ counts, int S, int E, float* __restrict__ out) {
+    __shared__ float rows[32][ROW_W];
+    const int b = blockIdx.y, j0 = blockIdx.x * 32, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int kept = min(max(counts[b], 0), keep_k);
+    if (j0 >= kept) return;  // (block-uniform)
+    for (int i = tid; i < 32 * ROW_W; i += 256) (&rows[0][0])[i] = 0.0f;
+    const Levels& L = R.L;
+    const int A = L.start[L.n];
+    const int px = lane & 31, hi = lane >> 5;
+    const bool valid = j0 + px < kept;
+    int lvl = -1, p = 0;
+    if (valid) {
+        const int pos = min(max(keep_idx[(int64_t)b * keep_k + j0 + px], 0), n_in - 1);
+        const int a = min(max(idx[(int64_t)b * n_in + pos], 0), A - 1);
+        lvl = find_level(L, a);
+        p = a - L.start[lvl];
+    }
+    __syncthreads();
+    for (int l = 0; l < L.n; ++l) {
+        const bool mine = lvl == l;
+        if (!__any(mine)) continue;  // (the same in every wave: each holds all 32 survivors)
+        const int hw = L.h[l] * L.w[l];
+        int units = 0;
+        for (int k = 0; k < R.n[l]; ++k) units += R.op[l][k].cout_pad >> 5;
+        for (int u = w; u < units; u += 4) {  // (wave-uniform)
+            int k = 0, t = u;
+            while (t >= (R.op[l][k].cout_pad >> 5)) t -= R.op[l][k++].cout_pad >> 5;
+            const vgh_row_op& o = R.op[l][k];
+            const int co = t * 32 + px;  // this lane's weight row of the A fragments
+            const uint16_t* const xr = o.in + ((int64_t)b * hw + p) * o.in_pitch + o.in_coff + hi * 8;
+            const uint16_t* const wr = o.wpack + (int64_t)co * 32;
+            const int sw = (co >> 2) & 3;  // the packed image stores logical 16-byte chunk c of a row in slot c ^ ((row >> 2) & 3)
+            f32x16_t acc;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+            for (int kb = 0; kb < o.cblocks; ++kb) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const bf16x8_t af = *(const bf16x8_t*)(wr + (int64_t)kb * o.cout_pad * 32 + ((2 * h + hi) ^ sw) * 8);
+                    bf16x8_t bf;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) bf[e] = (__bf16)0.0f;
+                    if (mine) bf = *(const bf16x8_t*)(xr + kb * 32 + h * 16);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf, acc, 0, 0, 0);
+                }
+            }
+            const float act_lo = o.act == VGH_ACT_RELU ? 0.0f : __builtin_nanf("");  // (conv_kernels.inc, act_bound)
+            const int oc = o.out_coff - VGH_PRED_FLAME_OFF;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int c = t * 32 + q * 8 + hi * 4 + e;  // accumulator register 4 q + e of lane (pixel px, half hi)
+                    if (mine && c < o.cout_store) rows[px][oc + c] = fmaxf(acc[q * 4 + e] + o.bias[c], act_lo);
+                }
+        }
+    }
+    __syncthreads();
+    for (int r = w; r < 32 && j0 + r < kept; r += 4) {
+        const int pos = min(max(keep_idx[(int64_t)b * keep_k + j0 + r], 0), n_in - 1);
+        const int a = min(max(idx[(int64_t)b * n_in + pos], 0), A - 1);
+        const int l = find_level(L, a);
+        const int pp = a - L.start[l];
+        const int ay = pp / L.w[l], ax = pp - ay * L.w[l];
+        const float st = (float)L.stride[l];
+        const int64_t o = (int64_t)b * keep_k + j0 + r;
+        for (int c = lane; c < VGH_NUM_FLAME_PARAMS; c += 64) out[o * VGH_NUM_FLAME_PARAMS + c] = flame_channel(rows[r], c, S, E, ax, ay, st);
+    }
+}
+
 int make_levels(const vgh_head_level* levels, int n_levels, Levels* L) {
     VGH_REQUIRE(n_levels >= 1 && n_levels <= MAX_LEVELS, "head: n_levels=%d out of range", n_levels);
     L->n = n_levels;
@@ -531,7 +619,7 @@ int vgh_nms(const float* boxes_dev, const float* scores_dev, int B, int n_in, fl
 int vgh_nms_select(const float* boxes_dev, const float* scores_dev, const float* flame_dev, int B, int n_in, float conf_thr, float iou_thr, int keep_k,
                    int32_t* keep_idx_dev, int32_t* counts_dev, float* out_boxes_dev, float* out_scores_dev, float* out_flame_dev, int capacity, int32_t* head_row_dev,
                    int32_t* head_image_dev, int32_t* n_heads_dev, int32_t* ticket_dev, const vgh_head_level* lazy_levels, int n_levels, const int32_t* lazy_idx_dev,
-                   int shape_c, int expr_c, void* stream) {
+                   int shape_c, int expr_c, void* stream, int rows_later) {
     VGH_REQUIRE(n_in >= 0 && n_in <= 1024 && keep_k >= 1 && keep_k <= 1024, "nms_select: n_in=%d / keep_k=%d must be <= 1024", n_in, keep_k);
     VGH_REQUIRE(!head_row_dev || (head_image_dev && n_heads_dev && ticket_dev), "nms_select: the head list needs head_image, n_heads and the ticket");
     if (B == 0) return VGH_OK;
@@ -543,7 +631,32 @@ int vgh_nms_select(const float* boxes_dev, const float* scores_dev, const float*
     }
     hipLaunchKernelGGL(nms_select_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, boxes_dev, scores_dev, flame_dev, n_in, conf_thr, iou_thr, keep_k, keep_idx_dev,
                        counts_dev, out_boxes_dev, out_scores_dev, out_flame_dev, B, capacity, head_row_dev, head_image_dev, n_heads_dev, ticket_dev, L, lazy_idx_dev, shape_c,
-                       expr_c);
+                       expr_c, rows_later);
+    VGH_HIP(hipGetLastError());
+    return VGH_OK;
+}
+
+int vgh_survivor_rows(const vgh_head_level* levels, int n_levels, const vgh_row_op* ops, const int* n_ops, int B, int n_in, int keep_k, const int32_t* idx_dev,
+                      const int32_t* keep_idx_dev, const int32_t* counts_dev, int shape_c, int expr_c, float* out_dev, void* stream) {
+    VGH_REQUIRE(levels && ops && n_ops && idx_dev && keep_idx_dev && counts_dev && out_dev, "survivor_rows: null argument");
+    VGH_REQUIRE(n_in >= 1 && keep_k >= 1 && keep_k <= n_in, "survivor_rows: n_in=%d / keep_k=%d", n_in, keep_k);
+    VGH_REQUIRE(shape_c >= 0 && shape_c <= 300 && expr_c >= 0 && expr_c <= 100, "survivor_rows: bad live channel counts");
+    RowOps R;
+    memset(&R, 0, sizeof(R));
+    if (int rc = make_levels(levels, n_levels, &R.L)) return rc;
+    const int width = shape_c + expr_c + 13;
+    for (int l = 0; l < n_levels; ++l) {
+        VGH_REQUIRE(n_ops[l] >= 1 && n_ops[l] <= kMaxRowOps, "survivor_rows: level %d has %d ops", l, n_ops[l]);
+        R.n[l] = n_ops[l];
+        for (int k = 0; k < n_ops[l]; ++k) {
+            const vgh_row_op& o = ops[l * kMaxRowOps + k];
+            VGH_REQUIRE(vgh_row_op_ok(o, width), "survivor_rows: level %d op %d does not write FLAME channels of the prediction row from 16-byte aligned bf16 rows", l, k);
+            R.op[l][k] = o;
+        }
+    }
+    if (B == 0) return VGH_OK;
+    hipLaunchKernelGGL(survivor_rows_kernel, dim3((keep_k + 31) / 32, B), dim3(256), 0, (hipStream_t)stream, R, n_in, keep_k, idx_dev, keep_idx_dev, counts_dev, shape_c, expr_c,
+                       out_dev);
     VGH_HIP(hipGetLastError());
     return VGH_OK;
 }

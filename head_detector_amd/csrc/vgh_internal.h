@@ -76,7 +76,8 @@ struct VghMarkAtExit {  // "epilogue done" on every return path of a kernel body
 int vgh_nms_select(const float* boxes_dev, const float* scores_dev, const float* flame_dev, int B, int n_in, float conf_thr, float iou_thr, int keep_k,
                    int32_t* keep_idx_dev, int32_t* counts_dev, float* out_boxes_dev, float* out_scores_dev, float* out_flame_dev, int capacity, int32_t* head_row_dev,
                    int32_t* head_image_dev, int32_t* n_heads_dev, int32_t* ticket_dev, const vgh_head_level* lazy_levels, int n_levels, const int32_t* lazy_idx_dev,
-                   int shape_c, int expr_c, void* stream);  // lazy_idx_dev != null: flame_dev is not read, the survivors' vectors come from the prediction buffers
+                   int shape_c, int expr_c, void* stream,   // lazy_idx_dev != null: flame_dev is not read, the survivors' vectors come from the prediction buffers
+                   int rows_later = 0);                     // 1: the survivors' vectors are left to vgh_survivor_rows, queued behind this launch (rows past the count are still zeroed)
 int vgh_launch_conv(const ConvArgs& a, int force_cfg, hipStream_t stream);
 // the ONE launcher type of both tile tables (conv_igemm.hip, conv_split.hip): the prepared launch, its tile counts (tile_grid), the dynamic LDS of the table row, the stream
 #define VGH_TILE_LAUNCHER(name) int name(const ConvArgs& a, const TileGrid& g, int lds, hipStream_t st)
@@ -177,6 +178,33 @@ extern "C" __attribute__((visibility("hidden"))) int vgh_net_set_pred_guard(vgh_
 // net.hip, library-internal: how many forwards (vgh_net_forward, vgh_net_forward_graph, vgh_net_profile) have been queued on this net -- the prediction buffers hold the
 // results of the latest one.  The detector's lazy FLAME gather is tied to the generation it decoded (detect.hip)
 extern "C" __attribute__((visibility("hidden"))) uint64_t vgh_net_generation(vgh_net* n);
+// One deferrable prediction conv (NetPlan::Op::deferrable) as the survivor-row kernel of postproc.hip needs it: row p of the op's output is
+// act(W . in[p * in_pitch + in_coff ...] + bias), channels [0, cout_store) of it landing at channel out_coff of the prediction row.
+struct vgh_row_op {
+    const uint16_t* in;     // bf16 input tensor, batch row 0
+    const uint16_t* wpack;  // packed weights (vgh_pack_conv_weights_host), [cblocks][cout_pad][32]
+    const float* bias;      // [cout_pad]
+    int in_pitch, in_coff, cblocks, cout_pad, cout_store, out_coff, act;
+};
+constexpr int kMaxRowOps = 4;  // per prediction buffer
+// net.hip, library-internal (the exported ABI is frozen): the defer switch (default off: forwards run every op), the pending convs of the latest forward on `stream`
+// (ordered behind that forward; idempotent, a no-op when nothing is pending), whether there are any, and a buffer's address WITHOUT running them (vgh_net_buffer does)
+extern "C" __attribute__((visibility("hidden"))) int vgh_net_set_defer(vgh_net* n, int on);
+extern "C" __attribute__((visibility("hidden"))) int vgh_net_run_deferred(vgh_net* n, void* stream);
+extern "C" __attribute__((visibility("hidden"))) int vgh_net_deferred_pending(vgh_net* n);
+extern "C" __attribute__((visibility("hidden"))) void* vgh_net_buffer_ptr(vgh_net* n, int buf_id);
+// what the survivor-row kernel asks of an op: 16-byte aligned bf16 rows, whole 32-cout weight tiles, its stored channels inside the `width` FLAME channels of the row
+static inline bool vgh_row_op_ok(const vgh_row_op& o, int width) {
+    return o.in && o.wpack && o.bias && o.cblocks >= 1 && o.cout_pad >= 32 && o.cout_pad % 32 == 0 && o.cout_store >= 1 && o.cout_store <= o.cout_pad && o.in_coff >= 0 && o.in_coff % 8 == 0 &&
+           o.in_pitch % 8 == 0 && o.in_coff + 32 * o.cblocks <= o.in_pitch && o.out_coff >= VGH_PRED_FLAME_OFF && o.out_coff - VGH_PRED_FLAME_OFF + o.cout_store <= width && o.act != VGH_ACT_SILU;
+}
+// net.hip: the deferrable ops that write buffer `out_buf`, in program order; their count, or -1 when there are more than max_ops
+extern "C" __attribute__((visibility("hidden"))) int vgh_net_row_ops(vgh_net* n, int out_buf, vgh_row_op* out, int max_ops);
+// postproc.hip: the FLAME segment of the prediction rows of the survivors of a select, computed from the inputs of the deferred prediction convs.  Image b's survivors
+// are keep_idx_dev[b][0 .. counts_dev[b]) (positions into idx_dev[b][0 .. n_in), anchors); launched over B x keep_k, blocks past the device-side count exit.
+// out_dev [B, keep_k, 413]: the fixed-up vectors (gather_kernel's arithmetic); rows at and past the count are not written
+int vgh_survivor_rows(const vgh_head_level* levels, int n_levels, const vgh_row_op* ops /*[n_levels][kMaxRowOps]*/, const int* n_ops, int B, int n_in, int keep_k,
+                      const int32_t* idx_dev, const int32_t* keep_idx_dev, const int32_t* counts_dev, int shape_c, int expr_c, float* out_dev, void* stream);
 
 // letterbox.hip: the batched letterbox of VGH_IMG_U8_RAW / VGH_IMG_YUV420_RAW, owned by a detector (canvas [arena_batch, S, S, 3] + two pinned / device staging slots)
 struct vgh_lb_batch;

@@ -207,6 +207,7 @@ class VGHeadsEngine:
         bf = P.bufs[bid]
         fmt = bf["is_f32"]
         n = B * bf["h"] * bf["w"] * bf["pitch"]
+        self.lib.vgh_net_buffer(self._net, bid)  # (first, before the synchronize: it queues prediction convs that a deferring forward left pending for this buffer)
         self.stream.synchronize()
         if fmt == arch.FMT_FP8:  # e4m3 link: decoded to fp32 (stored * scale)
             t = _alias(self.lib.vgh_net_buffer(self._net, bid), (n,), "|u1", self.device).clone().view(torch.float8_e4m3fn).float() * bf["scale"]
@@ -299,7 +300,7 @@ class VGHeadsEngine:
         if use_graph:
             if getattr(self, "_overlap", False):
                 raise ValueError("hipGraph replay cannot honour the prediction-buffer guard of overlap mode: use one or the other")
-            key = (images.data_ptr(), B, fmt)
+            key = (images.data_ptr(), B, fmt, getattr(self, "_lazy_flame", False))  # (the lazy gather sets the net's defer switch: other launches in the graph)
             if self._graph_key != key:
                 _lib.check(self.lib.vgh_net_forward(self._net, images.data_ptr(), fmt, B, self._sp()))  # warm: lazy attributes before capture
                 self.stream.synchronize()
@@ -398,8 +399,17 @@ class VGHeadsEngine:
 
     def _set_lazy_flame(self, enable: bool):
         if getattr(self, "_lazy_flame", False) != bool(enable):
-            _lib.check(self.lib.vgh_detector_set_lazy_flame(self._det, int(bool(enable))))
+            _lib.check(self.lib.vgh_detector_set_lazy_flame(self._det, (1 if getattr(self, "_defer_allowed", True) else 2) if enable else 0))
             self._lazy_flame = bool(enable)
+
+    def set_defer(self, allow: bool = True):
+        """Deferred FLAME predictions (include/vgh.h, vgh_detector_set_lazy_flame): by default the lazy gather makes the forwards skip the final 1x1 convs of the FLAME
+        towers and the select compute the survivors' rows itself -- the same bits.  ``False`` keeps the lazy gather on dense prediction rows (A/B, tests)."""
+        self._defer_allowed = bool(allow)
+        lazy = getattr(self, "_lazy_flame", False)
+        self._lazy_flame = None  # re-send the flag: its value says which
+        self._set_lazy_flame(lazy)
+        self._graph_key = None  # a captured graph holds the launches of the switch it was captured with
 
     def forward_candidates(self, images: torch.Tensor, use_graph: bool = False, lazy_flame: bool = False) -> int:
         """Network + candidate stages for a batch of any size <= max_batch (arena-sized chunks): one vgh_detector_candidates call.  ``lazy_flame``: see ``candidates``

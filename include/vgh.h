@@ -152,7 +152,8 @@ int vgh_net_profile(vgh_net* net, const void* image_dev, int image_fmt, int B, v
  * lanes wait for each other's ops (vgh_op_desc.lane bits 8+): the HIP runtime cannot end such a capture; waits on the main stream's ops are always fine. */
 int vgh_net_capture(vgh_net* net, const void* image_dev, int image_fmt, int B, void* stream);
 int vgh_net_forward_graph(vgh_net* net, void* stream);
-void* vgh_net_buffer(vgh_net* net, int buf_id);         /* device pointer of an activation buffer   */
+void* vgh_net_buffer(vgh_net* net, int buf_id);         /* device pointer of an activation buffer (prediction convs that the lazy FLAME gather's deferral left pending for
+                                                          * the latest forward and that write this buffer are queued first, on that forward's stream: vgh_detector_set_lazy_flame) */
 int64_t vgh_net_buffer_bytes(vgh_net* net, int buf_id); /* bytes for max_batch                       */
 int vgh_net_set_cfg(vgh_net* net, int op_index, int cfg);
 /* Read-only: the tile configuration SELECTED for op `op_index` for the arena batch -- the one vgh_net_set_cfg left in place, else the automatic choice resolved at
@@ -466,6 +467,17 @@ int vgh_detector_set_overlap(vgh_detector* d, int enable);
  * number of times; a lazy batch that is never selected is simply replaced by the next candidate stage.  A batch that runs in several arena chunks gathers eagerly whatever the
  * flag says.  The detections are the same bits.  Default 0. */
 int vgh_detector_set_lazy_flame(vgh_detector* d, int enable);
+/* (additive) DEFERRED FLAME PREDICTIONS.  vgh_net_create marks, from the program alone, the convs whose output nothing but a post-network stage can need densely: plain
+ * 1x1 / stride-1 bf16 convs that write channels VGH_PRED_FLAME_OFF and up of an fp32 buffer which no op reads (the last layer of the FLAME towers; the box / score convs
+ * below that offset feed the top-k and are never marked), from an input that no later op rewrites.  Where they write exactly the FLAME channels of every level,
+ * vgh_detector_set_lazy_flame(det, 1) also sets a switch of the net (off by default: plan, launch order and bits are then exactly those of a net without it): the
+ * forwards that follow -- vgh_net_forward, vgh_net_capture, a replay of a graph so captured -- SKIP the marked convs and leave them pending for that forward; their inputs
+ * stay intact in the arena until the next one.  A lazy select then computes the survivors' rows itself, from the rows of the convs' inputs, with the arithmetic of the
+ * conv tiles -- the same bits; the dense FLAME rows are neither written nor read.  Whatever needs dense rows runs the pending convs first, for the batch of that forward
+ * and behind it, once: every eager candidate stage (vgh_detector_decode_candidates with the lazy gather off or `at` > 0, the chunks of vgh_detector_candidates) -- so a
+ * deferred forward followed by an eager candidate stage is legal -- and vgh_net_buffer, which queues them on the stream of that forward before it hands out a buffer
+ * they write.  vgh_net_profile always runs every op.  enable = 2: the lazy gather on dense prediction rows, the net's switch off (A/B, tests).  The ABI is unchanged:
+ * the switch has no entry point of its own. */
 int vgh_detector_join(vgh_detector* d, void* stream);
 /* Records the caller's HIP event behind everything queued so far for the post-network stages (overlap mode: on the detector's side stream; else on `stream`)
  * WITHOUT making any stream wait for it: a host that synchronises on the event of an EARLIER batch can queue that batch's consumers (e.g. the N>1 exchange) with no
