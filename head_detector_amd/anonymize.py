@@ -18,8 +18,8 @@ restatement bit for bit.  In short:
 The number of kernel launches does not depend on the number of heads.  There is no CPU path for the pixels.  A blur radius above 1024 raises instead of
 blurring less: a silently weaker blur on a large head would be the wrong failure for a privacy function ("pixelate" has no such limit).
 
-Out of scope: writing the result back into YUV planes (``video.YUV420Frame`` results anonymise their RGB ``original_image``), dilating a mesh or mask region,
-and hair outside the FLAME mesh -- ``margin`` with "box" or "ellipse" is the lever for that."""
+A ``video.YUV420Frame`` is anonymised in its own luma and chroma planes, in place if wanted, by ``video.anonymize_frame`` (``PredictionResult.anonymize_frame``);
+this module works on RGB images.  Out of scope: dilating a mesh or mask region, and hair outside the FLAME mesh -- ``margin`` with "box" or "ellipse" is the lever for that."""
 from __future__ import annotations
 
 import math
@@ -71,8 +71,9 @@ def _check_choice(method: str, region: str) -> None:
         raise ValueError(f"anonymize: region must be one of {REGIONS}, got {region!r}")
 
 
-def anonymize_plan(image_shape: Sequence[int], heads, method: str, region: str, margin: float = 0.1, cells: int = 8, strength: float = 0.1, bounds=None) -> AnonymizePlan:
+def anonymize_plan(image_shape: Sequence[int], heads, method: str, region: str, margin: float = 0.1, cells: int = 8, strength: float = 0.1, bounds=None, tables=None) -> AnonymizePlan:
     """The host half of ``anonymize_heads``; no GPU.  ``bounds``: for ``region="mesh"`` the int32 [n, 4] of ``mesh_geometry.pixel_bounds`` (inclusive, clipped).
+    ``tables``: an empty ``TapTables`` to put the blur tables into, for a caller that appends rows of its own (``video.anonymize_frame``: the chroma rows).
     Raises ValueError naming the head for a bad box, a side above 32767 or a blur radius above 1024."""
     _check_choice(method, region)
     H, W = int(image_shape[0]), int(image_shape[1])
@@ -89,15 +90,13 @@ def anonymize_plan(image_shape: Sequence[int], heads, method: str, region: str, 
     if int(cells) != cells or not 1 <= int(cells) <= _lib_anon.MAX_CELLS:
         raise ValueError(f"anonymize: cells must be an integer in 1 .. {_lib_anon.MAX_CELLS}, got {cells}")
     cells = int(cells)
-    rows = np.zeros(n, dtype=_lib_anon.HEAD_DTYPE)
-    sigmas = np.zeros(n, dtype=np.float64)
     if region == "mesh":
         if bounds is None:
             raise ValueError('anonymize: region="mesh" needs the meshes\' pixel bounds')
         bounds = np.asarray(bounds, dtype=np.int64).reshape(-1, 4)
         if bounds.shape[0] != n:
             raise ValueError(f"anonymize: {bounds.shape[0]} rows of bounds for {n} heads")
-    tables, offsets, n_taps = [], {}, 0
+    boxes = []
     for i, head in enumerate(heads):
         if region == "mesh":
             x0, y0, x1, y1 = (int(v) for v in bounds[i])
@@ -110,6 +109,37 @@ def anonymize_plan(image_shape: Sequence[int], heads, method: str, region: str, 
                 raise ValueError(f"anonymize: head {i}: bbox {tuple(head.bbox)} has a negative side")
             mx, my = int(w * margin), int(h * margin)
             x0, y0, x1, y1 = x - mx, y - my, x + w + mx, y + h + my
+        boxes.append((x0, y0, x1, y1))
+    tables = TapTables() if tables is None else tables
+    rows, sigmas = plan_rows(boxes, method, cells, strength, tables)
+    return AnonymizePlan(rows, tables.taps(), _lib_anon.METHODS[method], sigmas)
+
+
+class TapTables:
+    """The blur tables of one call, one per distinct (sigma, radius), end to end: several ``plan_rows`` (the luma and the chroma rows of a frame) may share one."""
+
+    def __init__(self):
+        self._tables, self._offsets, self._n = [], {}, 0
+
+    def offset(self, sigma: float, radius: int) -> int:
+        if (sigma, radius) not in self._offsets:
+            self._offsets[(sigma, radius)] = self._n
+            self._tables.append(gaussian_taps(sigma, radius))
+            self._n += radius + 1
+        return self._offsets[(sigma, radius)]
+
+    def taps(self) -> np.ndarray:
+        return np.concatenate(self._tables).astype(np.int32) if self._tables else np.zeros(0, dtype=np.int32)
+
+
+def plan_rows(boxes, method: str, cells: int, strength: float, tables: TapTables):
+    """The plan from explicit geometry boxes (x0, y0, x1, y1), half-open and unclipped: -> (rows [n] of ``_lib_anon.HEAD_DTYPE``, sigmas float64 [n]).  Per head
+    the cell side ``max(1, ceil(max side / cells))`` (pixelate), or ``sigma = strength * max side``, ``radius = ceil(3 sigma)`` and the offset of its table in
+    ``tables`` (blur).  Raises ValueError naming the head for a side above 32767, a corner beyond 2^24 or a radius above 1024."""
+    n = len(boxes)
+    rows = np.zeros(n, dtype=_lib_anon.HEAD_DTYPE)
+    sigmas = np.zeros(n, dtype=np.float64)
+    for i, (x0, y0, x1, y1) in enumerate(boxes):
         wb, hb = x1 - x0, y1 - y0
         if max(wb, hb) > _lib_anon.MAX_SIDE:
             raise ValueError(f"anonymize: head {i}: box sides {wb} x {hb} exceed {_lib_anon.MAX_SIDE}")
@@ -125,14 +155,9 @@ def anonymize_plan(image_shape: Sequence[int], heads, method: str, region: str, 
                 raise ValueError(f'anonymize: head {i}: a blur of strength {strength} on a box of {wb} x {hb} pixels needs radius {radius} > {_lib_anon.MAX_RADIUS}; '
                                  'use method="pixelate", which has no such limit, or a smaller strength')
             sigmas[i] = sigma
-            if (sigma, radius) not in offsets:
-                offsets[(sigma, radius)] = n_taps
-                tables.append(gaussian_taps(sigma, radius))
-                n_taps += radius + 1
-            at = offsets[(sigma, radius)]
+            at = tables.offset(sigma, radius)
         rows[i] = (x0, y0, x1, y1, cell, radius, at, 0)
-    taps = np.concatenate(tables).astype(np.int32) if tables else np.zeros(0, dtype=np.int32)
-    return AnonymizePlan(rows, taps, _lib_anon.METHODS[method], sigmas)
+    return rows, sigmas
 
 
 def _check_color(color) -> int:

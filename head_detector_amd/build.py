@@ -1,5 +1,5 @@
-"""In-tree build of libvgh.so, its companions libvghview.so, libvghvis.so, libvghtex.so, libvgheval.so, libvghmerge.so and libvghtrack.so, and the application
-library libvghanon.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
+"""In-tree build of libvgh.so, its companions libvghview.so, libvghvis.so, libvghtex.so, libvgheval.so, libvghmerge.so and libvghtrack.so, the application
+library libvghanon.so and the video library libvghvideo.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
 from __future__ import annotations
 
 import os
@@ -44,6 +44,11 @@ APPLICATIONS = [
     # head anonymisation (pixelate, blur, fill): integer arithmetic only, equal bit for bit to its NumPy restatement
     Companion("libvghanon.so", ["anonymize.hip"], HOST_HEADERS, "vgh_anon.h", [], "build_anon"),
 ]
+# Libraries on the video side (frames in their own YUV planes): built like a companion, before the core
+VIDEO = [
+    # heads anonymised in the planes of a YUV 4:2:0 frame, and RGB packed into such planes: integer arithmetic only, equal bit for bit to its NumPy restatement
+    Companion("libvghvideo.so", ["yuv_anonymize.hip", "yuv_pack.hip"], HOST_HEADERS, "vgh_video.h", [], "build_video"),
+]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -59,7 +64,7 @@ def _stale(lib: str, deps) -> bool:
 
 
 def _core_needs_build() -> bool:  # everything in csrc/ that no companion claims
-    claimed = {f for c in COMPANIONS + APPLICATIONS for f in c.sources + c.headers}
+    claimed = {f for c in COMPANIONS + APPLICATIONS + VIDEO for f in c.sources + c.headers}
     return _stale(LIB, [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in claimed] + [os.path.join(HERE, "..", "include", "vgh.h")])
 
 
@@ -68,7 +73,7 @@ def _needs_build(c: Companion) -> bool:
 
 
 def needs_build() -> bool:
-    return _core_needs_build() or any(_needs_build(c) for c in COMPANIONS + APPLICATIONS)
+    return _core_needs_build() or any(_needs_build(c) for c in COMPANIONS + APPLICATIONS + VIDEO)
 
 
 LIB_EXP = os.path.join(HERE, "libvgh_exp.so")  # -DVGH_EXPERIMENTS build (work-skipping switches, env-var knobs): tools/ only
@@ -79,7 +84,7 @@ def build_lib(force: bool = False, verbose: bool = True, experiments: bool = Fal
         return _build(os.path.join(HERE, "libvgh_var.so"), [f"-D{d}" for d in variant_defines], "build_var", verbose)
     if experiments:
         return _build(LIB_EXP, ["-DVGH_EXPERIMENTS"], "build_exp", verbose)
-    for c in COMPANIONS + APPLICATIONS:
+    for c in COMPANIONS + APPLICATIONS + VIDEO:
         if force or _needs_build(c):
             _build(os.path.join(HERE, c.lib), ["-fvisibility=hidden", *c.flags], c.objdir, verbose, c.sources)
     if force or _core_needs_build():

@@ -1,0 +1,541 @@
+// libvghvideo.so (include/vgh_video.h): video.anonymize_frame -- every head of an 8-bit YUV 4:2:0 frame pixelated, blurred or filled directly in the luma and
+// chroma planes, in place if wanted, without an RGB image and without a launch per head.
+//
+// Every plane is a one-channel image under one rule; the kernels are written once for NC channels that share their geometry: NC = 1 is the luma plane, NC = 2
+// the U and V planes, which are either two planes (planar) or, where they are the two interleaved views of one NV12 / NV21 plane, a (U, V) pair that a lane
+// loads and stores with one 16-bit access.
+// OWNER: the luma owner plane, i32 [H, W], -1 = nobody, is painted by box (atomicMax of the head over its clipped box) or comes in as a pointer; a chroma
+// sample's owner is the maximum of the (up to) four luma owners it colours, taken where it is needed.
+// VALUES: what an owned sample becomes is staged in the workspace from the SOURCE planes before anything is written, NC bytes per pixelation cell or per sample
+// of a blurred head's clipped box:
+//   pixelate   cells_kernel      one workgroup per cell: 64-bit integer sums of the cell's in-plane samples, rounded mean
+//   blur       blur_rows_kernel  one workgroup per 256-sample row segment: the source row and its 2 r halo in LDS, h = the u16 horizontal pass
+//              blur_cols_kernel  one lane per sample of the clipped box, a wave along a row: the vertical pass over h, for the samples the head owns
+// WRITE: write_kernel, one lane per sample of every head's clipped box, stores the value (fill: the colour) where the head owns the sample: the only pass
+// that writes a frame in place.  A plane that is out of place is copied first (copy_kernel, the one pass that walks a whole plane).
+// Heads x tiles, x cells and x row segments are enumerated through prefix sums made on the host; a workgroup finds its head by bisection.  Integer arithmetic
+// only.
+#include <string.h>
+
+#include <map>
+#include <mutex>
+#include <vector>
+
+#include "../../include/vgh_video.h"
+#include "companion_host.h"
+
+namespace {
+
+using namespace companion;
+static_assert(VGHY_OK == OK && VGHY_ERR_INVALID == ERR_INVALID && VGHY_ERR_HIP == ERR_HIP && VGHY_ERR_NOMEM == ERR_NOMEM, "companion_host.h returns these codes");
+
+constexpr int TILE_W = 64, TILE_H = 4;  // a tile of the owner painter, the vertical pass and the write pass: 256 lanes, one wave a row
+constexpr int SEGMENT = 256;            // samples of one row segment of the horizontal pass
+constexpr int LINE_SAMPLES = SEGMENT + 2 * VGHY_MAX_RADIUS;  // the segment and the widest halo in LDS (luma: 256 + 2 * 1024 bytes), so r is never chunked
+
+// One channel of a plane group as the kernels read it, and the group: NC channels of one width and height.
+struct Chan {
+    const uint8_t* src;
+    uint8_t* dst;
+    int64_t spitch, dpitch;
+    int32_t sstep, dstep;
+};
+template <int NC>
+struct View {
+    Chan c[NC];
+    int32_t W, H;          // of the plane
+    int32_t spair, dpair;  // NC = 2: 0 = two planes; 1 / 2 = c[0] / c[1] is the even, lower byte of interleaved pairs
+};
+
+// One head in one plane group.  (cx0, cy0, cx1, cy1) is the geometry box clipped to the plane, all 0 if nothing is left.  A sample's value lies at
+// values[val_at + ((y - vy0) / vdiv) * vstride + (x - vx0) / vdiv]: pixelate (x0, y0, cell, cells in a row), blur (cx0, cy0, 1, clipped width).
+struct HeadRow {
+    int32_t x0, y0, x1, y1;
+    int32_t cx0, cy0, cx1, cy1;
+    int32_t vx0, vy0, vdiv, vstride;
+    int32_t radius, tap_at, hy0, hy1;  // blur: h holds rows hy0 .. hy1 - 1 = the clipped box extended by r rows and clamped to the plane
+    int64_t val_at, h_at;              // in samples: NC bytes of the values, NC u16 of h each
+};
+static_assert(sizeof(HeadRow) == 80, "uploaded as it is");
+
+// the largest i in [0, n) with prefix[i] <= item; prefix[0] = 0 and item < prefix[n], so prefix[i + 1] > item: heads without items are stepped over
+__device__ __forceinline__ int head_of(const uint32_t* __restrict__ prefix, int n, uint32_t item) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (prefix[mid] <= item) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ bool in_ellipse(const HeadRow& r, int x, int y) {
+    const int64_t wb = r.x1 - r.x0, hb = r.y1 - r.y0, ex = 2 * (int64_t)(x - r.x0) + 1 - wb, ey = 2 * (int64_t)(y - r.y0) + 1 - hb;
+    return ex * ex * hb * hb + ey * ey * wb * wb <= wb * wb * hb * hb;
+}
+
+// the sample of lane `threadIdx.x` in tile `t` of the head's clipped box; false = outside the box
+__device__ __forceinline__ bool tile_sample(const HeadRow& r, uint32_t t, int& x, int& y) {
+    const uint32_t across = (uint32_t)(r.cx1 - r.cx0 + TILE_W - 1) / TILE_W, ty = t / across, tx = t - ty * across;
+    x = r.cx0 + (int)tx * TILE_W + (int)(threadIdx.x & 63);
+    y = r.cy0 + (int)ty * TILE_H + (int)(threadIdx.x >> 6);
+    return x < r.cx1 && y < r.cy1;  // cx1 <= W and cy1 <= H of the plane: a sample that passes lies in the plane
+}
+
+template <int NC>
+__device__ __forceinline__ void load(const View<NC>& P, int x, int y, uint32_t (&v)[NC]) {
+    if constexpr (NC == 2) {
+        if (P.spair) {  // one 16-bit access for the (U, V) pair: the lower pointer and the pitch are even
+            const Chan& lo = P.c[P.spair - 1];
+            const uint32_t w = *reinterpret_cast<const uint16_t*>(lo.src + (int64_t)y * lo.spitch + 2 * (int64_t)x);
+            const uint32_t a = w & 255u, b = w >> 8;
+            v[0] = P.spair == 1 ? a : b;
+            v[1] = P.spair == 1 ? b : a;
+            return;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) v[c] = P.c[c].src[(int64_t)y * P.c[c].spitch + (int64_t)x * P.c[c].sstep];
+}
+
+template <int NC>
+__device__ __forceinline__ void store(const View<NC>& P, int x, int y, const uint32_t (&v)[NC]) {
+    if constexpr (NC == 2) {
+        if (P.dpair) {
+            const Chan& lo = P.c[P.dpair - 1];
+            const uint32_t a = P.dpair == 1 ? v[0] : v[1], b = P.dpair == 1 ? v[1] : v[0];
+            *reinterpret_cast<uint16_t*>(lo.dst + (int64_t)y * lo.dpitch + 2 * (int64_t)x) = (uint16_t)(a | b << 8);
+            return;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) P.c[c].dst[(int64_t)y * P.c[c].dpitch + (int64_t)x * P.c[c].dstep] = (uint8_t)v[c];
+}
+
+// Does head i own sample (x, y) of this plane group?  Luma: the owner plane itself.  Chroma: the maximum of the owners, -1 for every value outside [0, n), of
+// the luma pixels {2 y, 2 y + 1} x {2 x, 2 x + 1} that lie in the frame (LW x LH).
+template <int NC>
+__device__ __forceinline__ bool owned_by(const int32_t* __restrict__ owner, int LW, int LH, int n, int x, int y, int i) {
+    if constexpr (NC == 1) {
+        return owner[(size_t)y * LW + x] == i;
+    } else {
+        int o = -1;
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const int lx = 2 * x + dx, ly = 2 * y + dy;
+                if (lx < LW && ly < LH) {
+                    const int32_t k = owner[(size_t)ly * LW + lx];
+                    if ((uint32_t)k < (uint32_t)n) o = max(o, k);
+                }
+            }
+        return o == i;
+    }
+}
+
+// ---- owner (luma) ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void paint_owner_kernel(const HeadRow* __restrict__ rows, const uint32_t* __restrict__ tiles, int n, int32_t* __restrict__ owner, int W, int ellipse) {
+    const int i = head_of(tiles, n, blockIdx.x);
+    const HeadRow r = rows[i];
+    int x, y;
+    if (!tile_sample(r, blockIdx.x - tiles[i], x, y)) return;
+    if (ellipse && !in_ellipse(r, x, y)) return;
+    atomicMax(owner + (size_t)y * W + x, i);
+}
+
+// ---- pixelate -------------------------------------------------------------------------------------------------------------------------------
+// One workgroup per cell: the four waves take the cell's in-plane rows in turn, the lanes its columns.  64-bit sums: 255 * 32767^2 does not fit 32 bits.
+template <int NC>
+__global__ __launch_bounds__(256) void cells_kernel(const HeadRow* __restrict__ rows, const uint32_t* __restrict__ cells, int n, View<NC> P, uint8_t* __restrict__ values) {
+    __shared__ unsigned long long part[NC][256];
+    const int i = head_of(cells, n, blockIdx.x);
+    const HeadRow r = rows[i];
+    const uint32_t q = blockIdx.x - cells[i], cy = q / (uint32_t)r.vstride, cx = q - cy * (uint32_t)r.vstride;
+    const int s = r.vdiv, gx = r.x0 + (int)cx * s, gy = r.y0 + (int)cy * s;
+    const int ax = max(gx, 0), ay = max(gy, 0), bx = min(min(gx + s, r.x1), P.W), by = min(min(gy + s, r.y1), P.H);  // the cell, in the box, in the plane
+    if (bx <= ax || by <= ay) return;  // m = 0: never referenced (the whole workgroup leaves)
+    unsigned long long a[NC] = {};
+    for (int y = ay + (int)(threadIdx.x >> 6); y < by; y += 4)
+        for (int x = ax + (int)(threadIdx.x & 63); x < bx; x += 64) {
+            uint32_t v[NC];
+            load<NC>(P, x, y, v);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) a[c] += v[c];
+        }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) part[c][threadIdx.x] = a[c];
+    __syncthreads();
+    for (int half = 128; half >= 1; half >>= 1) {
+        if ((int)threadIdx.x < half)
+            for (int c = 0; c < NC; ++c) part[c][threadIdx.x] += part[c][threadIdx.x + half];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const unsigned long long m = (unsigned long long)(bx - ax) * (unsigned long long)(by - ay);
+        for (int c = 0; c < NC; ++c) values[(r.val_at + q) * NC + c] = (uint8_t)((2 * part[c][0] + m) / (2 * m));
+    }
+}
+
+// ---- blur -----------------------------------------------------------------------------------------------------------------------------------
+// Horizontal pass.  One workgroup per (head, row of h, 256-sample segment of the clipped box): the segment's source samples and r either side, columns clamped
+// to the plane, staged in LDS; lane t then sums sample t of the segment.  The sum is at most 65536 * 255.  A dense luma row is staged four samples a lane:
+// the line starts `lead` bytes early, at the aligned dword below the first sample, and every dword that lies wholly inside the row is one aligned load.
+template <int NC>
+__global__ __launch_bounds__(256) void blur_rows_kernel(const HeadRow* __restrict__ rows, const uint32_t* __restrict__ segments, int n, const int32_t* __restrict__ taps, View<NC> P,
+                                                        uint16_t* __restrict__ h) {
+    __shared__ __attribute__((aligned(4))) uint8_t line[(LINE_SAMPLES + 4) * NC];
+    const int i = head_of(segments, n, blockIdx.x);
+    const HeadRow r = rows[i];
+    const int cw = r.cx1 - r.cx0;
+    const uint32_t q = blockIdx.x - segments[i], across = (uint32_t)(cw + SEGMENT - 1) / SEGMENT, row = q / across, seg = q - row * across;
+    const int y = r.hy0 + (int)row, sx = r.cx0 + (int)seg * SEGMENT, samples = min(SEGMENT, r.cx1 - sx), rad = r.radius;
+    int lead = 0;
+    if (NC == 1 && P.c[0].sstep == 1) {
+        const uint8_t* from = P.c[0].src + (int64_t)y * P.c[0].spitch;
+        lead = (int)(((uintptr_t)from + (uintptr_t)(intptr_t)(sx - rad)) & 3);  // (sx - rad may be negative: the address is only looked at)
+        const int first = sx - rad - lead;                 // the column of line[0]; from + first is 4-byte aligned
+        for (int p = 4 * (int)threadIdx.x; p < lead + samples + 2 * rad; p += 1024) {
+            const int gx = first + p;
+            if (gx >= 0 && gx + 3 < P.W) {
+                *reinterpret_cast<uint32_t*>(line + p) = *reinterpret_cast<const uint32_t*>(from + gx);
+            } else {
+                for (int b = 0; b < 4; ++b) line[p + b] = from[min(max(gx + b, 0), P.W - 1)];
+            }
+        }
+    } else {
+        for (int j = threadIdx.x; j < samples + 2 * rad; j += 256) {
+            uint32_t v[NC];
+            load<NC>(P, min(max(sx - rad + j, 0), P.W - 1), y, v);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) line[j * NC + c] = (uint8_t)v[c];
+        }
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t >= samples) return;
+    const int32_t* tap = taps + r.tap_at;
+    const uint8_t* mid = line + (lead + t + rad) * NC;
+    uint32_t a[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) a[c] = (uint32_t)tap[0] * mid[c];
+    for (int k = 1; k <= rad; ++k) {
+        const uint32_t w = (uint32_t)tap[k];
+        const uint8_t *l = mid - NC * k, *g = mid + NC * k;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) a[c] += w * ((uint32_t)l[c] + g[c]);
+    }
+    uint16_t* o = h + (r.h_at + (int64_t)row * cw + (sx - r.cx0 + t)) * NC;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) o[c] = (uint16_t)((a[c] + 128u) >> 8);
+}
+
+// Vertical pass.  One lane per sample of the clipped box, a wave along a row, so that every tap reads a row of h coalesced over the columns.  Only the samples
+// the head owns are computed: no other value is ever looked up.  The sum stays below 65536 * 65280 + 2^23 < 2^32.
+template <int NC>
+__global__ __launch_bounds__(256) void blur_cols_kernel(const HeadRow* __restrict__ rows, const uint32_t* __restrict__ tiles, int n, const int32_t* __restrict__ taps,
+                                                        const int32_t* __restrict__ owner, int LW, int LH, int PH, const uint16_t* __restrict__ h, uint8_t* __restrict__ values) {
+    const int i = head_of(tiles, n, blockIdx.x);
+    const HeadRow r = rows[i];
+    int x, y;
+    if (!tile_sample(r, blockIdx.x - tiles[i], x, y)) return;
+    if (!owned_by<NC>(owner, LW, LH, n, x, y, i)) return;
+    const int cw = r.cx1 - r.cx0;
+    const int32_t* tap = taps + r.tap_at;
+    const uint16_t* col = h + (r.h_at + (int64_t)(x - r.cx0)) * NC;  // row yy of the plane is row yy - hy0 of h; clamp(y +- k) stays inside hy0 .. hy1 - 1
+    uint32_t a[NC] = {};
+    for (int k = -r.radius; k <= r.radius; ++k) {
+        const uint32_t w = (uint32_t)tap[abs(k)];
+        const uint16_t* p = col + (int64_t)(min(max(y + k, 0), PH - 1) - r.hy0) * cw * NC;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) a[c] += w * p[c];
+    }
+    uint8_t* o = values + (r.val_at + (int64_t)(y - r.cy0) * cw + (x - r.cx0)) * NC;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) o[c] = (uint8_t)((a[c] + (1u << 23)) >> 24);
+}
+
+// ---- write ----------------------------------------------------------------------------------------------------------------------------------
+// One lane per sample of every head's clipped box: the sample is stored if the head owns it (the clipped box is the part of the geometry box in the plane, so
+// "inside its owner's box" holds by construction).  Nothing else of the destination is touched.
+template <int NC>
+__global__ __launch_bounds__(256) void write_kernel(const HeadRow* __restrict__ rows, const uint32_t* __restrict__ tiles, int n, const int32_t* __restrict__ owner, int LW, int LH,
+                                                    const uint8_t* __restrict__ values, int fill, uint32_t colour, View<NC> P) {
+    const int i = head_of(tiles, n, blockIdx.x);
+    const HeadRow r = rows[i];
+    int x, y;
+    if (!tile_sample(r, blockIdx.x - tiles[i], x, y)) return;
+    if (!owned_by<NC>(owner, LW, LH, n, x, y, i)) return;
+    uint32_t v[NC];
+    if (fill) {
+#pragma unroll
+        for (int c = 0; c < NC; ++c) v[c] = (colour >> (8 * c)) & 255u;
+    } else {
+        const uint8_t* p = values + (r.val_at + (int64_t)((y - r.vy0) / r.vdiv) * r.vstride + (x - r.vx0) / r.vdiv) * NC;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) v[c] = p[c];
+    }
+    store<NC>(P, x, y, v);
+}
+
+// ---- copy -----------------------------------------------------------------------------------------------------------------------------------
+// A plane that is out of place: every sample copied, four of a row per lane; one aligned dword where both sides are dense, aligned and whole.
+__global__ __launch_bounds__(256) void copy_kernel(const uint8_t* __restrict__ src, int64_t spitch, int sstep, uint8_t* __restrict__ dst, int64_t dpitch, int dstep, int W) {
+    const int x0 = (int)(blockIdx.x * 256u + threadIdx.x) * 4, y = (int)blockIdx.y;
+    if (x0 >= W) return;
+    const uint8_t* s = src + (int64_t)y * spitch + (int64_t)x0 * sstep;
+    uint8_t* d = dst + (int64_t)y * dpitch + (int64_t)x0 * dstep;
+    if (sstep == 1 && dstep == 1 && x0 + 4 <= W && (((uintptr_t)s | (uintptr_t)d) & 3) == 0) {
+        *reinterpret_cast<uint32_t*>(d) = *reinterpret_cast<const uint32_t*>(s);
+        return;
+    }
+    for (int b = 0; b < 4 && x0 + b < W; ++b) d[(int64_t)b * dstep] = s[(int64_t)b * sstep];
+}
+
+// ---- the host half: every check and every offset, no HIP call -----------------------------------------------------------------------------------
+struct GroupPlan {  // one plane group: luma, or chroma
+    std::vector<HeadRow> rows;
+    std::vector<uint32_t> tiles, cells, segments;  // prefix sums over the heads, n + 1 entries each
+    int64_t n_values = 0, n_h = 0;                 // samples
+    int64_t at_values = 0, at_h = 0;               // byte offsets in the workspace
+};
+struct Plan {
+    GroupPlan luma, chroma;
+    int64_t total = 0;
+    bool in_place[3] = {false, false, false};
+    int spair = 0, dpair = 0;
+};
+
+int64_t up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+
+const char* const PLANE_NAMES[3] = {"Y", "U", "V"};
+
+// the byte range of a plane of pw x ph samples
+void plane_range(const uint8_t* p, int64_t pitch, int step, int64_t pw, int64_t ph, uintptr_t& a, uintptr_t& b) {
+    a = (uintptr_t)p;
+    b = a + (uintptr_t)((ph - 1) * pitch + (pw - 1) * step + 1);
+}
+
+// 1 / 2: planes 1 / 2 are the even, lower byte of interleaved pairs that one 16-bit access reaches; 0: handled as two planes
+int pair_of(const void* u, const void* v, int64_t upitch, int64_t vpitch, int ustep, int vstep) {
+    if (ustep != 2 || vstep != 2 || upitch != vpitch || (upitch & 1)) return 0;
+    const uintptr_t a = (uintptr_t)u, b = (uintptr_t)v;
+    if (b == a + 1 && !(a & 1)) return 1;
+    if (a == b + 1 && !(b & 1)) return 2;
+    return 0;
+}
+
+// the rows of one plane group (pw x ph samples): every per-head check, the clipped boxes and the offsets
+int plan_group(const vghy_anonymize_job& j, const vghy_head* heads, const char* kind, int64_t PW, int64_t PH, GroupPlan& p, const char* who) {
+    const int n = j.n_heads;
+    const bool blur = j.method == VGHY_METHOD_BLUR, pixelate = j.method == VGHY_METHOD_PIXELATE;
+    p.rows.assign((size_t)n, HeadRow{});
+    p.tiles.assign((size_t)n + 1, 0);
+    p.cells.assign((size_t)n + 1, 0);
+    p.segments.assign((size_t)n + 1, 0);
+    int64_t n_tiles = 0, n_cells = 0, n_segments = 0;
+    int32_t ok_at = -1, ok_radius = -1;  // the table checked last: heads usually share one
+    for (int i = 0; i < n; ++i) {
+        const vghy_head& g = heads[i];
+        HeadRow& r = p.rows[(size_t)i];
+        CH_REQUIRE(g.x0 > -VGHY_MAX_COORD && g.x0 < VGHY_MAX_COORD && g.y0 > -VGHY_MAX_COORD && g.y0 < VGHY_MAX_COORD, "%s: %s head %d: corner (%d, %d) outside +-2^24", who, kind, i, g.x0,
+                   g.y0);
+        const int64_t wb = (int64_t)g.x1 - g.x0, hb = (int64_t)g.y1 - g.y0;
+        CH_REQUIRE(wb >= 0 && hb >= 0 && wb <= VGHY_MAX_SIDE && hb <= VGHY_MAX_SIDE, "%s: %s head %d: box sides %lld x %lld outside 0 .. %d", who, kind, i, (long long)wb, (long long)hb,
+                   VGHY_MAX_SIDE);
+        CH_REQUIRE(g.reserved == 0, "%s: %s head %d: reserved is %d, not 0", who, kind, i, g.reserved);
+        r.x0 = g.x0, r.y0 = g.y0, r.x1 = g.x1, r.y1 = g.y1;
+        r.vdiv = 1;
+        const int cx0 = g.x0 > 0 ? g.x0 : 0, cy0 = g.y0 > 0 ? g.y0 : 0, cx1 = g.x1 < PW ? g.x1 : (int)PW, cy1 = g.y1 < PH ? g.y1 : (int)PH;
+        const bool empty = cx1 <= cx0 || cy1 <= cy0;
+        if (!empty) r.cx0 = cx0, r.cy0 = cy0, r.cx1 = cx1, r.cy1 = cy1;
+        const int64_t cw = r.cx1 - r.cx0, ch = r.cy1 - r.cy0;
+        if (pixelate) {
+            CH_REQUIRE(g.cell >= 1 && g.cell <= VGHY_MAX_SIDE, "%s: %s head %d: cell side %d outside 1 .. %d", who, kind, i, g.cell, VGHY_MAX_SIDE);
+            const int64_t across = (wb + g.cell - 1) / g.cell, down = (hb + g.cell - 1) / g.cell;
+            CH_REQUIRE(across <= VGHY_MAX_CELLS && down <= VGHY_MAX_CELLS, "%s: %s head %d: %lld x %lld cells of side %d exceed %d a side", who, kind, i, (long long)across, (long long)down,
+                       g.cell, VGHY_MAX_CELLS);
+            r.vx0 = g.x0, r.vy0 = g.y0, r.vdiv = g.cell, r.vstride = (int32_t)across, r.val_at = p.n_values;
+            if (!empty) n_cells += across * down, p.n_values += across * down;
+        }
+        if (blur) {
+            CH_REQUIRE(g.radius >= 0 && g.radius <= VGHY_MAX_RADIUS, "%s: %s head %d: radius %d outside 0 .. %d", who, kind, i, g.radius, VGHY_MAX_RADIUS);
+            CH_REQUIRE(g.tap_offset >= 0 && (int64_t)g.tap_offset + g.radius < j.n_taps, "%s: %s head %d: taps %d .. %lld outside the table of %d", who, kind, i, g.tap_offset,
+                       (long long)g.tap_offset + g.radius, j.n_taps);
+            if (g.tap_offset != ok_at || g.radius != ok_radius) {
+                int64_t sum = 0;
+                for (int k = 0; k <= g.radius; ++k) {
+                    const int32_t t = j.taps[g.tap_offset + k];
+                    CH_REQUIRE(t >= 0 && t <= VGHY_TAP_SUM, "%s: %s head %d: tap %d is %d, outside 0 .. %d", who, kind, i, k, t, VGHY_TAP_SUM);
+                    sum += k ? 2 * (int64_t)t : t;
+                }
+                CH_REQUIRE(sum == VGHY_TAP_SUM, "%s: %s head %d: tap sum %lld is not %d", who, kind, i, (long long)sum, VGHY_TAP_SUM);
+                ok_at = g.tap_offset, ok_radius = g.radius;
+            }
+            r.radius = g.radius, r.tap_at = g.tap_offset;
+            r.vx0 = r.cx0, r.vy0 = r.cy0, r.vdiv = 1, r.vstride = (int32_t)cw, r.val_at = p.n_values, r.h_at = p.n_h;
+            r.hy0 = r.cy0 - g.radius > 0 ? r.cy0 - g.radius : 0;
+            r.hy1 = r.cy1 + g.radius < PH ? r.cy1 + g.radius : (int)PH;
+            if (!empty) {
+                p.n_values += cw * ch;
+                p.n_h += (int64_t)(r.hy1 - r.hy0) * cw;
+                n_segments += (int64_t)(r.hy1 - r.hy0) * ((cw + SEGMENT - 1) / SEGMENT);
+            }
+        }
+        if (!empty) n_tiles += ((cw + TILE_W - 1) / TILE_W) * ((ch + TILE_H - 1) / TILE_H);
+        CH_REQUIRE(n_tiles <= INT32_MAX && n_cells <= INT32_MAX && n_segments <= INT32_MAX, "%s: %s head %d: the boxes so far exceed one launch (%lld tiles, %lld cells, %lld row segments)",
+                   who, kind, i, (long long)n_tiles, (long long)n_cells, (long long)n_segments);
+        p.tiles[(size_t)i + 1] = (uint32_t)n_tiles, p.cells[(size_t)i + 1] = (uint32_t)n_cells, p.segments[(size_t)i + 1] = (uint32_t)n_segments;
+    }
+    return OK;
+}
+
+// `who` words the messages: the two entry points share every check of the job
+int make_plan(const vghy_anonymize_job* job, Plan& p, const char* who) {
+    CH_REQUIRE(job, "%s: null job", who);
+    const vghy_anonymize_job& j = *job;
+    CH_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHY_MAX_SIDE && j.width <= VGHY_MAX_SIDE, "%s: frame %d x %d outside 1 .. %d", who, j.height, j.width, VGHY_MAX_SIDE);
+    const int64_t H = j.height, W = j.width, CH = (H + 1) / 2, CW = (W + 1) / 2;
+    uintptr_t s0[3], s1[3], d0[3], d1[3];
+    for (int k = 0; k < 3; ++k) {
+        const vghy_plane& q = j.planes[k];
+        const int64_t pw = k ? CW : W, ph = k ? CH : H;
+        CH_REQUIRE(q.src_dev && q.dst_dev, "%s: plane %s: null plane (src_dev %p, dst_dev %p)", who, PLANE_NAMES[k], (const void*)q.src_dev, (void*)q.dst_dev);
+        CH_REQUIRE((q.src_step == 1 || q.src_step == 2) && (q.dst_step == 1 || q.dst_step == 2), "%s: plane %s: steps %d and %d are not 1 or 2", who, PLANE_NAMES[k], q.src_step, q.dst_step);
+        CH_REQUIRE(q.src_pitch >= (pw - 1) * q.src_step + 1 && q.src_pitch <= ((int64_t)1 << 40), "%s: plane %s: src_pitch %lld outside %lld .. 2^40", who, PLANE_NAMES[k],
+                   (long long)q.src_pitch, (long long)((pw - 1) * q.src_step + 1));
+        CH_REQUIRE(q.dst_pitch >= (pw - 1) * q.dst_step + 1 && q.dst_pitch <= ((int64_t)1 << 40), "%s: plane %s: dst_pitch %lld outside %lld .. 2^40", who, PLANE_NAMES[k],
+                   (long long)q.dst_pitch, (long long)((pw - 1) * q.dst_step + 1));
+        plane_range(q.src_dev, q.src_pitch, q.src_step, pw, ph, s0[k], s1[k]);
+        plane_range(q.dst_dev, q.dst_pitch, q.dst_step, pw, ph, d0[k], d1[k]);
+    }
+    for (int k = 0; k < 3; ++k) {  // a destination plane is exactly its source plane, or overlaps no source plane
+        const vghy_plane& q = j.planes[k];
+        p.in_place[k] = q.dst_dev == q.src_dev && q.dst_pitch == q.src_pitch && q.dst_step == q.src_step;
+        if (p.in_place[k]) continue;
+        CH_REQUIRE(q.dst_dev != q.src_dev, "%s: plane %s: the destination starts where the source does with another pitch or step (%lld and %d, not %lld and %d): in place means exactly the source plane",
+                   who, PLANE_NAMES[k], (long long)q.dst_pitch, q.dst_step, (long long)q.src_pitch, q.src_step);
+        for (int m = 0; m < 3; ++m)
+            CH_REQUIRE(d1[k] <= s0[m] || s1[m] <= d0[k], "%s: plane %s: the destination overlaps source plane %s without being exactly its own source plane", who, PLANE_NAMES[k], PLANE_NAMES[m]);
+    }
+    CH_REQUIRE(j.n_heads >= 0 && j.n_heads <= VGHY_MAX_HEADS, "%s: n_heads %d outside 0 .. %d", who, j.n_heads, VGHY_MAX_HEADS);
+    CH_REQUIRE(j.method >= VGHY_METHOD_FILL && j.method <= VGHY_METHOD_BLUR, "%s: unknown method %d", who, j.method);
+    CH_REQUIRE(j.region >= VGHY_REGION_BOX && j.region <= VGHY_REGION_MAP, "%s: unknown region %d", who, j.region);
+    CH_REQUIRE((j.color & ~0xffffff) == 0, "%s: color 0x%x has more than three bytes", who, (unsigned)j.color);
+    CH_REQUIRE(j.reserved == 0, "%s: reserved is %d, not 0", who, j.reserved);
+    CH_REQUIRE((j.region == VGHY_REGION_MAP) == (j.owner_dev != nullptr), "%s: owner_dev is %s for region %d (needed by VGHY_REGION_MAP alone)", who, j.owner_dev ? "set" : "null", j.region);
+    CH_REQUIRE(((uintptr_t)j.owner_dev & 15) == 0, "%s: owner_dev %p is not 16-byte aligned", who, (const void*)j.owner_dev);
+    const int n = j.n_heads;
+    const bool blur = j.method == VGHY_METHOD_BLUR;
+    CH_REQUIRE(n == 0 || (j.luma_heads && j.chroma_heads), "%s: null heads (luma_heads %p, chroma_heads %p)", who, (const void*)j.luma_heads, (const void*)j.chroma_heads);
+    CH_REQUIRE(j.n_taps >= 0, "%s: n_taps %d is negative", who, j.n_taps);
+    if (blur && n) CH_REQUIRE(j.taps && j.n_taps >= 1, "%s: blur needs a tap table (taps %p, n_taps %d)", who, (const void*)j.taps, j.n_taps);
+    if (int rc = plan_group(j, j.luma_heads, "luma", W, H, p.luma, who)) return rc;
+    if (int rc = plan_group(j, j.chroma_heads, "chroma", CW, CH, p.chroma, who)) return rc;
+    p.spair = pair_of(j.planes[1].src_dev, j.planes[2].src_dev, j.planes[1].src_pitch, j.planes[2].src_pitch, j.planes[1].src_step, j.planes[2].src_step);
+    p.dpair = pair_of(j.planes[1].dst_dev, j.planes[2].dst_dev, j.planes[1].dst_pitch, j.planes[2].dst_pitch, j.planes[1].dst_step, j.planes[2].dst_step);
+    p.luma.at_values = up16(j.region == VGHY_REGION_MAP ? 0 : 4 * H * W);
+    p.chroma.at_values = up16(p.luma.at_values + p.luma.n_values);
+    p.luma.at_h = up16(p.chroma.at_values + 2 * p.chroma.n_values);
+    p.chroma.at_h = up16(p.luma.at_h + 2 * p.luma.n_h);
+    p.total = up16(p.chroma.at_h + 4 * p.chroma.n_h);
+    if (p.total < 16) p.total = 16;
+    return OK;
+}
+
+std::mutex g_mutex;
+std::map<int, Staging> g_staging;  // per device: the head rows, the prefix sums and the taps of one call
+
+Chan chan_of(const vghy_plane& q) { return Chan{q.src_dev, q.dst_dev, q.src_pitch, q.dst_pitch, q.src_step, q.dst_step}; }
+
+}  // namespace
+
+extern "C" VGHY_API const char* vghy_version(void) { return "vghvideo 1 (gfx950)"; }
+extern "C" VGHY_API const char* vghy_last_error(void) { return last_error(); }
+
+extern "C" VGHY_API int64_t vghy_anonymize_workspace_bytes(const vghy_anonymize_job* job) {
+    Plan p;
+    return make_plan(job, p, "anonymize_workspace_bytes") == OK ? p.total : 0;
+}
+
+extern "C" VGHY_API int vghy_anonymize(const vghy_anonymize_job* job, void* workspace_dev, void* stream) {
+    Plan p;
+    // everything is checked before anything is allocated, written or queued
+    if (int rc = make_plan(job, p, "anonymize")) return rc;
+    CH_REQUIRE(workspace_dev, "anonymize: null workspace");
+    CH_REQUIRE(((uintptr_t)workspace_dev & 15) == 0, "anonymize: workspace is not 16-byte aligned");
+    const vghy_anonymize_job& j = *job;
+    const int n = j.n_heads, W = j.width, H = j.height, CW = (W + 1) / 2, CH = (H + 1) / 2;
+    const bool blur = j.method == VGHY_METHOD_BLUR, pixelate = j.method == VGHY_METHOD_PIXELATE, paint = j.region != VGHY_REGION_MAP;
+    const int fill = j.method == VGHY_METHOD_FILL;
+    hipStream_t st = (hipStream_t)stream;
+    int device = 0;
+    CH_HIP(hipGetDevice(&device));
+    std::lock_guard<std::mutex> lock(g_mutex);
+    Staging& s = g_staging[device];
+    // one upload: [luma rows | chroma rows | 2 x (tiles | cells | segments) | taps], each from a 16-byte boundary
+    const size_t prefix_bytes = ((size_t)n + 1) * 4, rows_bytes = align16((size_t)n * sizeof(HeadRow)), prefix_room = align16(prefix_bytes);
+    const size_t at_prefix = 2 * rows_bytes, at_taps = at_prefix + 6 * prefix_room, total = align16(at_taps + (blur ? (size_t)j.n_taps * 4 : 0));
+    if (int rc = reserve(s, total, "anonymize")) return rc;  // also waits for this device's previous call
+    uint8_t* host = s.host;
+    const GroupPlan* groups[2] = {&p.luma, &p.chroma};
+    for (int g = 0; g < 2; ++g) {
+        if (n) memcpy(host + g * rows_bytes, groups[g]->rows.data(), (size_t)n * sizeof(HeadRow));
+        memcpy(host + at_prefix + (3 * g + 0) * prefix_room, groups[g]->tiles.data(), prefix_bytes);
+        memcpy(host + at_prefix + (3 * g + 1) * prefix_room, groups[g]->cells.data(), prefix_bytes);
+        memcpy(host + at_prefix + (3 * g + 2) * prefix_room, groups[g]->segments.data(), prefix_bytes);
+    }
+    if (blur && j.n_taps) memcpy(host + at_taps, j.taps, (size_t)j.n_taps * 4);
+    // from here on work is queued (companion_host.h, queue-then-record)
+    const uint8_t* d = s.dev;
+    const HeadRow* rows[2] = {(const HeadRow*)d, (const HeadRow*)(d + rows_bytes)};
+    const uint32_t *tiles[2], *cells[2], *segments[2];
+    for (int g = 0; g < 2; ++g) {
+        tiles[g] = (const uint32_t*)(d + at_prefix + (3 * g + 0) * prefix_room);
+        cells[g] = (const uint32_t*)(d + at_prefix + (3 * g + 1) * prefix_room);
+        segments[g] = (const uint32_t*)(d + at_prefix + (3 * g + 2) * prefix_room);
+    }
+    const int32_t* taps = (const int32_t*)(d + at_taps);
+    uint8_t* ws = (uint8_t*)workspace_dev;
+    int32_t* painted = (int32_t*)ws;
+    const int32_t* owner = paint ? painted : j.owner_dev;
+    View<1> luma{{chan_of(j.planes[0])}, W, H, 0, 0};
+    View<2> chroma{{chan_of(j.planes[1]), chan_of(j.planes[2])}, CW, CH, p.spair, p.dpair};
+    uint8_t *values_l = ws + p.luma.at_values, *values_c = ws + p.chroma.at_values;
+    uint16_t *h_l = (uint16_t*)(ws + p.luma.at_h), *h_c = (uint16_t*)(ws + p.chroma.at_h);
+    const uint32_t tiles_l = p.luma.tiles[(size_t)n], tiles_c = p.chroma.tiles[(size_t)n];
+    Queue q;
+    CH_QUEUE(q, hipMemcpyAsync(s.dev, host, total, hipMemcpyHostToDevice, st));
+    if (paint) {
+        CH_QUEUE(q, hipMemsetAsync(painted, 0xff, (size_t)W * (size_t)H * 4, st));  // -1 everywhere
+        if (tiles_l && q.ok()) hipLaunchKernelGGL(paint_owner_kernel, dim3(tiles_l), dim3(256), 0, st, rows[0], tiles[0], n, painted, W, (int)(j.region == VGHY_REGION_ELLIPSE));
+    }
+    if (pixelate && q.ok()) {
+        if (const uint32_t c = p.luma.cells[(size_t)n]) hipLaunchKernelGGL(cells_kernel<1>, dim3(c), dim3(256), 0, st, rows[0], cells[0], n, luma, values_l);
+        if (const uint32_t c = p.chroma.cells[(size_t)n]) hipLaunchKernelGGL(cells_kernel<2>, dim3(c), dim3(256), 0, st, rows[1], cells[1], n, chroma, values_c);
+    }
+    if (blur && q.ok()) {
+        if (const uint32_t g = p.luma.segments[(size_t)n]) {
+            hipLaunchKernelGGL(blur_rows_kernel<1>, dim3(g), dim3(256), 0, st, rows[0], segments[0], n, taps, luma, h_l);
+            hipLaunchKernelGGL(blur_cols_kernel<1>, dim3(tiles_l), dim3(256), 0, st, rows[0], tiles[0], n, taps, owner, W, H, H, (const uint16_t*)h_l, values_l);
+        }
+        if (const uint32_t g = p.chroma.segments[(size_t)n]) {
+            hipLaunchKernelGGL(blur_rows_kernel<2>, dim3(g), dim3(256), 0, st, rows[1], segments[1], n, taps, chroma, h_c);
+            hipLaunchKernelGGL(blur_cols_kernel<2>, dim3(tiles_c), dim3(256), 0, st, rows[1], tiles[1], n, taps, owner, W, H, CH, (const uint16_t*)h_c, values_c);
+        }
+    }
+    if (q.ok()) {  // the planes that are out of place: every sample copied, an interleaved pair that stays one as one plane of 2 CW bytes
+        if (!p.in_place[0]) hipLaunchKernelGGL(copy_kernel, dim3((W + 1023) / 1024, H), dim3(256), 0, st, luma.c[0].src, luma.c[0].spitch, 1 * luma.c[0].sstep, luma.c[0].dst, luma.c[0].dpitch, 1 * luma.c[0].dstep, W);
+        if (!p.in_place[1] && !p.in_place[2] && p.spair && p.spair == p.dpair) {
+            const Chan& lo = chroma.c[p.spair - 1];
+            hipLaunchKernelGGL(copy_kernel, dim3((2 * CW + 1023) / 1024, CH), dim3(256), 0, st, lo.src, lo.spitch, 1, lo.dst, lo.dpitch, 1, 2 * CW);
+        } else {
+            for (int k = 0; k < 2; ++k)
+                if (!p.in_place[1 + k]) hipLaunchKernelGGL(copy_kernel, dim3((CW + 1023) / 1024, CH), dim3(256), 0, st, chroma.c[k].src, chroma.c[k].spitch, chroma.c[k].sstep, chroma.c[k].dst, chroma.c[k].dpitch, chroma.c[k].dstep, CW);
+        }
+    }
+    if (q.ok()) {
+        if (tiles_l) hipLaunchKernelGGL(write_kernel<1>, dim3(tiles_l), dim3(256), 0, st, rows[0], tiles[0], n, owner, W, H, (const uint8_t*)values_l, fill, (uint32_t)j.color & 255u, luma);
+        if (tiles_c) hipLaunchKernelGGL(write_kernel<2>, dim3(tiles_c), dim3(256), 0, st, rows[1], tiles[1], n, owner, W, H, (const uint8_t*)values_c, fill, (uint32_t)j.color >> 8, chroma);
+    }
+    return finish(q, s, true, st, "anonymize");
+}

@@ -28,8 +28,9 @@ from .head_info import HeadMetadata
 
 class PredictionResult:
     def __init__(self, original_image: np.ndarray, heads: List[HeadMetadata], faces: Optional[np.ndarray] = None, pncc_processor=None, *,
-                 head_indices: Optional[np.ndarray] = None, triangles: Optional[np.ndarray] = None, face_indices: Optional[np.ndarray] = None):
-        self.original_image = original_image
+                 head_indices: Optional[np.ndarray] = None, triangles: Optional[np.ndarray] = None, face_indices: Optional[np.ndarray] = None, source_frame=None):
+        self.original_image = original_image  # (None for a frame input with rgb="none": no RGB copy was made)
+        self.source_frame = source_frame  # the video.YUV420Frame the result was made from, or None (an RGB input)
         self.heads = heads
         self._faces = faces  # [F,3] 0-based triangle indices of the FLAME mesh
         self.pncc_processor = pncc_processor  # head_detector_amd.pncc.PNCCProcessor or None (no mesh assets supplied)
@@ -62,11 +63,24 @@ class PredictionResult:
         "fill" (``color``).  ``region``: "box" (the ``bbox`` grown by ``margin``), "ellipse" (inscribed in that box) or "mesh" (the head's own silhouette as
         ``get_visibility`` sees it; needs ``faces``, the FLAME model's own unless given; hair lies outside it).  A later head owns the pixels it shares with
         an earlier one.  The original is never modified; a GPU ``original_image`` is used where it is.  ``to_host=False`` returns a GPU ``torch.uint8``
-        tensor.  Writing the result back into YUV planes is out of scope."""
+        tensor.  A result made from a ``video.YUV420Frame`` is hidden in the frame's own planes by ``anonymize_frame``."""
         from .anonymize import anonymize_heads
 
         return anonymize_heads(self.original_image, self.heads, method, region, margin=margin, cells=cells, strength=strength, color=color,
                                faces=self._faces if faces is None else faces, to_host=to_host)
+
+    def anonymize_frame(self, method: str = "pixelate", region: str = "ellipse", *, margin: float = 0.1, cells: int = 8, strength: float = 0.1, color=(0, 0, 0), faces=None,
+                        out=None):
+        """``video.anonymize_frame(self.source_frame, self.heads, ...)``: every head hidden directly in the luma and chroma planes of the YUV 4:2:0 frame the
+        result was made from (csrc/yuv_anonymize.hip, libvghvideo.so), with the keywords of ``anonymize``; no RGB image is made or needed (``rgb="none"``).
+        ``out=None``: a new frame; ``out=self.source_frame``: in place; another ``video.YUV420Frame`` of the same size: written whole.  Returns the frame
+        written.  ValueError if the result was not made from a frame: use ``anonymize()`` then."""
+        if self.source_frame is None:
+            raise ValueError("anonymize_frame: this result was not made from a video.YUV420Frame (source_frame is None); use anonymize() on its RGB original_image")
+        from .video import anonymize_frame
+
+        return anonymize_frame(self.source_frame, self.heads, method, region, margin=margin, cells=cells, strength=strength, color=color,
+                               faces=self._faces if faces is None else faces, out=out)
 
     def get_visibility(self, occlusion: str = "order", barycentric: bool = False, to_host: bool = True):
         """A ``visibility.HeadVisibility``: Sim3DR's ``rasterize_triangles`` over every head's mesh (the FLAME model's own triangles, ``faces``), depth = -z
@@ -150,4 +164,5 @@ class PredictionResult:
                     f.write("f %d %d %d\n" % tuple(t))
 
     def __repr__(self):
-        return f"PredictionResult(original_image={self.original_image.shape}, num heads={len(self.heads)})"
+        shape = (self.source_frame if self.original_image is None else self.original_image).shape
+        return f"PredictionResult(original_image={shape}, num heads={len(self.heads)})"

@@ -267,7 +267,8 @@ class HeadDetector:
         ONE fused device call (vgh_detect with VGH_IMG_U8_RAW: batched letterbox -> net -> top-k -> NMS per image -> FLAME decode + un-pad + head
         pose of every survivor); only the final per-head Python objects are built on the host.  Needs ``max_batch >= len(images)``.
         Video frames: a list of ``video.YUV420Frame`` (all of them frames) goes through the same call as VGH_IMG_YUV420_RAW; each result's ``original_image`` is the
-        frame's ``to_rgb()``, a NumPy array, or with ``rgb="device"`` a GPU tensor (which ``draw(..., to_host=False)`` and the other device helpers take as it is)."""
+        frame's ``to_rgb()``, a NumPy array, or with ``rgb="device"`` a GPU tensor (which ``draw(..., to_host=False)`` and the other device helpers take as it is), or
+        with ``rgb="none"`` None: no RGB copy is made, the mode for video loops that only use ``source_frame`` (``anonymize_frame``).  ``source_frame`` is the frame."""
         if len(images) > self._max_batch:
             raise ValueError(f"detect_batch: {len(images)} images exceed max_batch={self._max_batch} (pass max_batch= to HeadDetector)")
         from .letterbox import geometry
@@ -298,6 +299,7 @@ class HeadDetector:
         S = self._image_size
         for b, orig in enumerate(originals):
             _, _, pad_x, pad_y, scale = geometry(orig.shape[0], orig.shape[1], S)
+            frame = orig if frames else None
             if frames:
                 orig = frame_rgb(orig, rgb)
             heads = []
@@ -313,7 +315,8 @@ class HeadDetector:
                 heads.append(HeadMetadata(bbox=Bbox(x=bb[0], y=bb[1], w=bb[2] - bb[0], h=bb[3] - bb[1]), score=scores[b, i], flame_params=fp, vertices_3d=verts[at],
                                           head_pose=RPY(roll=float(rpy[at, 0]), pitch=float(rpy[at, 1]), yaw=float(rpy[at, 2]))))
                 at += 1
-            results.append(PredictionResult(original_image=orig, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc, head_indices=self._head_indices, triangles=self._triangles, face_indices=self._face_indices))
+            results.append(PredictionResult(original_image=orig, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc, head_indices=self._head_indices, triangles=self._triangles, face_indices=self._face_indices,
+                                            source_frame=frame))
         return results
 
     def detect_sliced(self, image: Union[str, "np.ndarray", Any], confidence_threshold: float = 0.5, *, tile_sizes: Optional[Sequence[int]] = None, overlap: float = 0.25,
@@ -382,9 +385,11 @@ class HeadDetector:
 
     def __call__(self, image: Union[str, "np.ndarray", Any], confidence_threshold: float = 0.5, *, rgb: str = "host") -> PredictionResult:
         """``image``: a path, a PIL image, an HWC uint8 array, or a ``video.YUV420Frame`` (NV12 / NV21 / I420, converted inside the device letterbox; the result is
-        that of the frame's ``to_rgb()`` image, which becomes ``original_image``: on the host, or with ``rgb="device"`` as a GPU tensor)."""
+        that of the frame's ``to_rgb()`` image, which becomes ``original_image``: on the host, or with ``rgb="device"`` as a GPU tensor; ``rgb="none"`` makes no RGB
+        copy, ``original_image`` is None.  The frame itself is the result's ``source_frame``, which ``anonymize_frame`` works on)."""
         from .video import YUV420Frame, frame_rgb
 
+        source_frame = image if isinstance(image, YUV420Frame) else None
         if isinstance(image, YUV420Frame):
             from .letterbox import geometry
 
@@ -399,4 +404,5 @@ class HeadDetector:
             image, cache = self._preprocess(original_image)
             predictions = self._process(image)
         heads = self._postprocess(predictions, cache, confidence_threshold)
-        return PredictionResult(original_image=original_image, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc, head_indices=self._head_indices, triangles=self._triangles, face_indices=self._face_indices)
+        return PredictionResult(original_image=original_image, heads=heads, faces=self._flame.faces, pncc_processor=self._pncc, head_indices=self._head_indices, triangles=self._triangles, face_indices=self._face_indices,
+                                source_frame=source_frame)

@@ -191,7 +191,8 @@ class HeadTracker:
 
     def update_batch(self, frames: Sequence, *, rgb: str = "host") -> List[TrackedPredictionResult]:
         """``frames``: RGB images as ``HeadDetector.detect_batch`` takes them, or ``video.YUV420Frame`` s (all of them; converted inside the device letterbox).  For
-        those, each result's ``original_image`` is the frame's ``to_rgb()``: a NumPy array, or with ``rgb="device"`` a GPU tensor."""
+        those, each result's ``original_image`` is the frame's ``to_rgb()``: a NumPy array, or with ``rgb="device"`` a GPU tensor, or with ``rgb="none"`` None (no RGB
+        copy is made), and its ``source_frame`` is the frame, which ``anonymize_frame`` works on."""
         import torch
 
         from .head_info import Bbox, FlameParams, HeadMetadata
@@ -243,6 +244,7 @@ class HeadTracker:
         ids, hits, misses = tracked.ids.cpu().numpy(), tracked.hits.cpu().numpy(), tracked.misses.cpu().numpy()
         results = []
         for b, orig in enumerate(originals):
+            frame = orig if yuv else None
             if yuv:
                 orig = frame_rgb(orig, rgb)
             k = int(n_out[b])
@@ -257,5 +259,5 @@ class HeadTracker:
                                           vertices_3d=verts[at[b] + i], head_pose=calculate_rpy(fp)))
             results.append(TrackedPredictionResult(original_image=orig, heads=heads, faces=det._flame.faces, pncc_processor=det._pncc, head_indices=det._head_indices,
                                                    triangles=det._triangles, face_indices=det._face_indices, track_ids=ids[b, :k].astype(np.int64),
-                                                   hits=hits[b, :k].astype(np.int64), coasting=misses[b, :k] > 0))
+                                                   hits=hits[b, :k].astype(np.int64), coasting=misses[b, :k] > 0, source_frame=frame))
         return results

@@ -11,6 +11,21 @@ integer rule stated in include/vgh.h (vgh_yuv420_image) -- nearest chroma sample
 
 ``YUV420Frame.to_rgb()`` is that rule in torch integer ops (CPU or GPU tensors); the detector's result is defined as "``to_rgb()``, then what an RGB image gets".
 PARITY UNPINNED against cv2.cvtColor (cv2 rounds its coefficients to another fixed-point precision): ``tools/first_contact.py --cv2`` reports the difference.
+
+Out again, to an encoder (include/vgh_video.h, libvghvideo.so; restated in tests/yuv_anonymize_ref.py and equal to it bit for bit):
+
+    anonymize_frame(frame, heads, out=frame)      # every head hidden in the frame's own luma and chroma planes, in place: no RGB image is made
+    YUV420Frame.from_rgb(image, "nv12")           # what draw(), render_mesh() and anonymize() return, packed to YUV 4:2:0
+
+Every plane is a one-channel image under the rule of ``anonymize``: the luma plane with the head's box, ellipse or mesh region; a chroma sample belongs to the
+latest head that owns any of the (up to) four luma pixels it colours, and is changed inside the chroma box (x0 >> 1, y0 >> 1, (x1 + 1) >> 1, (y1 + 1) >> 1)
+with the cell side and the blur radius worked out from that box by the same formulas.  Limits: 8-bit 4:2:0 only; the luma and the chroma grid of "pixelate" are
+independent, so the edges of their cells may differ by a sample.  The packer, integer like ``to_rgb``:
+
+    Y = clamp8(y_offset + ((kyr R + kyg G + kyb B + 32768) >> 16))
+    U = clamp8(128 + ((kur Rm + kug Gm + kub Bm + 32768) >> 16)),  V likewise;  (Rm, Gm, Bm) the rounded mean (2 S + m) / (2 m) of the 2 x 2 block's in-image pixels
+
+PARITY of the packer UNPINNED against cv2.cvtColor as well (``tools/first_contact.py --cv2``).
 """
 from __future__ import annotations
 
@@ -40,6 +55,41 @@ def yuv_coefficients(matrix: str = "bt709", full_range: bool = False) -> Tuple[i
     sy, sc = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
     q = lambda v: int(round(65536.0 * v))  # noqa: E731
     return (0 if full_range else 16, q(sy), q(sc * 2.0 * (1.0 - kr)), q(sc * -2.0 * kb * (1.0 - kb) / kg), q(sc * -2.0 * kr * (1.0 - kr) / kg), q(sc * 2.0 * (1.0 - kb)))
+
+
+def rgb_to_yuv_coefficients(matrix: str = "bt709", full_range: bool = False) -> Tuple[int, ...]:
+    """-> (y_offset, kyr, kyg, kyb, kur, kug, kub, kvr, kvg, kvb): the fixed-point coefficients (* 2^16) of vghy_pack_rgb, from the same float64 (Kr, Kb) table as
+    ``yuv_coefficients``; sy = 219 / 255 and sc = 224 / 255 for limited range, both 1 for full range:
+
+        kyr = round(65536 sy Kr), kyb = round(65536 sy Kb), kyg = round(65536 sy) - kyr - kyb                  the luma row sums to round(65536 sy)
+        kub = kvr = round(65536 sc / 2)
+        kur = round(65536 sc * -Kr / (2 (1 - Kb))), kug = -(kur + kub)                                          the chroma rows sum to exactly 0:
+        kvb = round(65536 sc * -Kb / (2 (1 - Kr))), kvg = -(kvr + kvb)                                          every grey gives U = V = 128"""
+    if matrix not in MATRICES:
+        raise ValueError(f"rgb_to_yuv_coefficients: matrix {matrix!r} is not one of {sorted(MATRICES)}")
+    kr, kb = MATRICES[matrix]
+    sy, sc = (1.0, 1.0) if full_range else (219.0 / 255.0, 224.0 / 255.0)
+    q = lambda v: int(round(65536.0 * v))  # noqa: E731
+    kyr, kyb = q(sy * kr), q(sy * kb)
+    kyg = q(sy) - kyr - kyb
+    kub = kvr = q(sc / 2.0)
+    kur = q(sc * -kr / (2.0 * (1.0 - kb)))
+    kvb = q(sc * -kb / (2.0 * (1.0 - kr)))
+    return (0 if full_range else 16, kyr, kyg, kyb, kur, -(kur + kub), kub, kvr, -(kvr + kvb), kvb)
+
+
+def rgb_to_yuv(color, matrix: str = "bt709", full_range: bool = False) -> Tuple[int, int, int]:
+    """(Y, U, V) of one RGB colour (three integers in 0 .. 255) by the packer's rule for one pixel; on the host, in Python integers."""
+    c = [int(v) for v in color]
+    if len(c) != 3 or any(not 0 <= v <= 255 or v != w for v, w in zip(c, color)):
+        raise ValueError(f"rgb_to_yuv: color must be three integers in 0 .. 255, got {tuple(color)}")
+    y_offset, *k = rgb_to_yuv_coefficients(matrix, full_range)
+    clamp8 = lambda v: min(max(v, 0), 255)  # noqa: E731
+    dot = lambda at: (k[at] * c[0] + k[at + 1] * c[1] + k[at + 2] * c[2] + 32768) >> 16  # noqa: E731
+    return clamp8(y_offset + dot(0)), clamp8(128 + dot(3)), clamp8(128 + dot(6))
+
+
+LAYOUTS = ("nv12", "nv21", "i420")
 
 
 def _as_tensor(a, what: str) -> torch.Tensor:
@@ -187,6 +237,66 @@ class YUV420Frame:
         v = cls._view(flat, who, (ch, cw), (cp, 1), uv_offset + cp * ch)
         return cls(y, u, v, chroma_step=1, **kw)
 
+    @classmethod
+    def empty(cls, height: int, width: int, layout: str = "nv12", device=None, **kw) -> "YUV420Frame":
+        """A new dense frame of uninitialised bytes: one surface with rows ``2 * ((width + 1) // 2)`` bytes apart, viewed as ``layout`` ("nv12", "nv21" or
+        "i420").  ``device``: a GPU (default: the current one).  ``**kw``: matrix, full_range."""
+        if layout not in LAYOUTS:
+            raise ValueError(f"YUV420Frame.empty: layout must be one of {LAYOUTS}, got {layout!r}")
+        h, w = int(height), int(width)
+        if h < 1 or w < 1:
+            raise ValueError(f"YUV420Frame.empty: frame of {h} x {w}")
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        pitch = 2 * ((w + 1) // 2)
+        surface = torch.empty(pitch * h + pitch * ((h + 1) // 2), dtype=torch.uint8, device=device)
+        return {"nv12": cls.from_nv12, "nv21": cls.from_nv21, "i420": cls.from_i420}[layout](surface, h, w, **kw)
+
+    @classmethod
+    def from_rgb(cls, image, layout: str = "nv12", matrix: str = "bt709", full_range: bool = False, out: Optional["YUV420Frame"] = None) -> "YUV420Frame":
+        """The frame of an RGB image (csrc/yuv_pack.hip, libvghvideo.so): what ``draw()``, ``render_mesh()`` and ``anonymize()`` return, ready for an encoder.
+        ``image``: uint8 [H, W, 3], a NumPy array (uploaded once) or a GPU tensor with pixels 3 bytes apart (rows may be pitched); never modified.  Luma per
+        pixel, chroma from the rounded mean of each 2 x 2 block's in-image pixels, by the integer rule the module text states with
+        ``rgb_to_yuv_coefficients(matrix, full_range)``.  ``out``: a frame of the same size on the same device to write into (its own layout, matrix and range
+        are used; it must not overlap the image); otherwise a new dense ``layout`` frame.  There is no CPU path."""
+        from . import _lib_video
+        from .aligned import _device_image
+
+        if out is None and layout not in LAYOUTS:
+            raise ValueError(f"from_rgb: layout must be one of {LAYOUTS}, got {layout!r}")
+        if out is not None:
+            if not isinstance(out, YUV420Frame):
+                raise ValueError(f"from_rgb: out must be a YUV420Frame, got {type(out).__name__}")
+            matrix, full_range = out.matrix, out.full_range
+        coef = rgb_to_yuv_coefficients(matrix, full_range)
+        lib = _lib_video.load()
+        src = _device_image(image, "packed frames")
+        H, W = int(src.shape[0]), int(src.shape[1])
+        if out is None:
+            out = cls.empty(H, W, layout, src.device, matrix=matrix, full_range=full_range)
+        elif out.shape != (H, W, 3) or out.device != src.device:
+            raise ValueError(f"from_rgb: out is {out!r}; the image is {H} x {W} on {src.device}")
+        job = _lib_video.PackJob()
+        job.src_dev, job.src_pitch_bytes, job.height, job.width = src.data_ptr(), (src.stride(0) if H > 1 else 3 * W), H, W
+        for k, (plane, pitch, step) in enumerate(out._layout()):
+            job.planes[k].dst_dev, job.planes[k].dst_pitch, job.planes[k].dst_step = plane.data_ptr(), pitch, step
+        job.y_offset = coef[0]
+        for k in range(9):
+            job.coef[k] = coef[1 + k]
+        with torch.cuda.device(src.device):
+            _lib_video.check(lib.vghy_pack_rgb(job, torch.cuda.current_stream().cuda_stream))
+        return out
+
+    def _layout(self):
+        """((plane, pitch in bytes, step in bytes) for y, u, v) as include/vgh_video.h describes a plane."""
+        return ((self.y, self.y_pitch, 1), (self.u, self.uv_pitch, self.chroma_step), (self.v, self.uv_pitch, self.chroma_step))
+
+    def _like(self) -> "YUV420Frame":
+        """A new dense frame of this frame's size, layout, matrix and range."""
+        h, w, _ = self.shape
+        layout = "i420" if self.chroma_step == 1 else "nv12" if self.v.data_ptr() > self.u.data_ptr() else "nv21"
+        return YUV420Frame.empty(h, w, layout, self.device, matrix=self.matrix, full_range=self.full_range)
+
     # ---------------------------------------------------------------------------------------------------------------------------------------
     @property
     def shape(self) -> Tuple[int, int, int]:
@@ -217,9 +327,113 @@ class YUV420Frame:
         return f"YUV420Frame({h} x {w}, chroma_step={self.chroma_step}, {self.matrix}, {'full' if self.full_range else 'limited'} range, {self.device})"
 
 
-def frame_rgb(frame: YUV420Frame, rgb: str = "host") -> Union[np.ndarray, torch.Tensor]:
-    """The ``original_image`` of a result whose input was a frame: ``to_rgb()`` on the host (NumPy, the default, like any other call) or kept on the device."""
-    if rgb not in ("host", "device"):
-        raise ValueError(f"rgb={rgb!r}: 'host' (a NumPy original_image) or 'device' (a GPU tensor)")
+def frame_rgb(frame: YUV420Frame, rgb: str = "host") -> Union[np.ndarray, torch.Tensor, None]:
+    """The ``original_image`` of a result whose input was a frame: ``to_rgb()`` on the host (NumPy, the default, like any other call) or kept on the device; with
+    ``rgb="none"`` no RGB copy is made at all (None): the result keeps its ``source_frame``, which ``anonymize_frame`` works on."""
+    if rgb not in ("host", "device", "none"):
+        raise ValueError(f"rgb={rgb!r}: 'host' (a NumPy original_image), 'device' (a GPU tensor) or 'none' (no RGB copy: video loops that use source_frame alone)")
+    if rgb == "none":
+        return None
     out = frame.to_rgb()
     return out if rgb == "device" else out.cpu().numpy()
+
+
+def chroma_box(box) -> Tuple[int, int, int, int]:
+    """The chroma box of a luma geometry box (x0, y0, x1, y1): (x0 >> 1, y0 >> 1, (x1 + 1) >> 1, (y1 + 1) >> 1), arithmetic shifts -- it contains every chroma
+    sample of every luma pixel of the box.  A luma box with a zero side gets an empty chroma box."""
+    x0, y0, x1, y1 = (int(v) for v in box)
+    if x1 <= x0 or y1 <= y0:
+        return (x0 >> 1, y0 >> 1, x0 >> 1, y0 >> 1)
+    return (x0 >> 1, y0 >> 1, (x1 + 1) >> 1, (y1 + 1) >> 1)
+
+
+def _plane_range(t: torch.Tensor) -> Tuple[int, int]:
+    last = sum((n - 1) * st for n, st in zip(t.shape, t.stride()))
+    return t.data_ptr(), t.data_ptr() + last + 1
+
+
+def anonymize_frame(frame: YUV420Frame, heads, method: str = "pixelate", region: str = "ellipse", *, margin: float = 0.1, cells: int = 8, strength: float = 0.1,
+                    color=(0, 0, 0), faces=None, owner=None, out: Optional[YUV420Frame] = None) -> YUV420Frame:
+    """``frame`` with every head hidden directly in its luma and chroma planes (csrc/yuv_anonymize.hip, libvghvideo.so; the module text and include/vgh_video.h
+    state the rule): no RGB image is made.  The arguments and their checks are those of ``anonymize.anonymize_heads``; ``color`` is RGB and converted by
+    ``rgb_to_yuv(color, frame.matrix, frame.full_range)``; ``region="mesh"`` (needs ``faces``) and ``owner=`` (int32 [H, W]) give the LUMA owner map.
+    ``out=None``: a new dense frame of the source's layout, matrix and range.  ``out=frame`` (or any frame whose three planes are the same memory with the same
+    pitch and step): IN PLACE -- only the samples of the heads are written, nothing is copied, and apart from clearing the owner map the work scales with the heads'
+    boxes, not with the frame.  Any other frame of the same size on the same device is written whole and must not overlap the source; its layout may differ
+    (NV12 in, I420 out).  Returns the frame written.  There is no CPU path for the samples."""
+    from . import _lib_video, anonymize as an
+    from ._lib import VghError
+    from .mesh_geometry import check_triangles, head_vertices, pixel_bounds, require_faces
+
+    an._check_choice(method, region)
+    if region == "mesh":
+        require_faces(faces)
+    rgb = an._check_color(color)
+    if not isinstance(frame, YUV420Frame):
+        raise ValueError(f"anonymize_frame: frame must be a YUV420Frame, got {type(frame).__name__}")
+    H, W, _ = frame.shape
+    y, u, v = rgb_to_yuv((rgb & 255, rgb >> 8 & 255, rgb >> 16), frame.matrix, frame.full_range)
+    n = len(heads)
+    if owner is not None and tuple(owner.shape) != (H, W):
+        raise ValueError(f"anonymize: owner must be int32 {(H, W)}, got {tuple(owner.shape)}")
+    if owner is not None and str(owner.dtype).replace("torch.", "") != "int32":
+        raise ValueError(f"anonymize: owner must be int32, got {owner.dtype}")
+    plan, tables = None, an.TapTables()  # one tap table for the call: the luma rows' tables first, the chroma rows' behind them
+    if region != "mesh" or n == 0:
+        plan = an.anonymize_plan((H, W), heads, method, "box" if n == 0 else region, margin, cells, strength, tables=tables)
+    else:
+        an.anonymize_plan((H, W), [], method, region, margin, cells, strength, bounds=np.zeros((0, 4)))  # the argument checks that need neither heads nor a GPU
+    if out is not None and not (isinstance(out, YUV420Frame) and out.shape == frame.shape and out.device == frame.device):
+        raise ValueError(f"anonymize_frame: out must be a YUV420Frame of {H} x {W} on {frame.device}; got {out!r}")
+    if not (torch.cuda.is_available() and frame.y.is_cuda):
+        raise VghError("anonymised frames need a GPU: the HIP kernels of libvghvideo.so are the only implementation of the samples")
+    lib = _lib_video.load()
+    dev = frame.device
+    if out is None:
+        out = frame._like()
+    for name, (s, sp, ss), (d, dp, ds) in zip("yuv", frame._layout(), out._layout()):
+        if d.data_ptr() == s.data_ptr() and dp == sp and ds == ss:
+            continue  # in place
+        d0, d1 = _plane_range(d)
+        for other in frame.planes:
+            s0, s1 = _plane_range(other)
+            if s0 < d1 and d0 < s1:
+                raise ValueError(f"anonymize_frame: plane {name} of out overlaps the source frame without being exactly its plane {name} (same memory, pitch and "
+                                 "step): pass out=frame for in place, or a frame elsewhere")
+    owner_dev = None
+    if plan is None:  # the mesh silhouettes: libvghvis.so paints them at the frame's size, Python hands the buffer over
+        from .visibility import head_visibility
+
+        verts = torch.from_numpy(head_vertices(heads)).to(dev)
+        tri = check_triangles(faces, verts.shape[1], "anonymize")
+        plan = an.anonymize_plan((H, W), heads, method, region, margin, cells, strength, bounds=pixel_bounds(verts, tri, H, W), tables=tables)
+        if owner is None:
+            owner_dev = head_visibility(heads, faces, H, W, occlusion="order", barycentric=False, to_host=False).head_index
+    if owner is not None:
+        owner_dev = owner.to(dev) if isinstance(owner, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(owner)).to(dev)
+    if owner_dev is not None:
+        owner_dev = owner_dev.contiguous()
+    # the chroma rows: the same formulas on the chroma boxes
+    luma_rows = plan.heads
+    corners = zip(luma_rows["x0"].tolist(), luma_rows["y0"].tolist(), luma_rows["x1"].tolist(), luma_rows["y1"].tolist())
+    chroma_rows, _ = an.plan_rows([chroma_box(b) for b in corners], method, int(cells), float(strength), tables)
+    taps = tables.taps()
+    job = _lib_video.AnonymizeJob()
+    for k, ((s, sp, ss), (d, dp, ds)) in enumerate(zip(frame._layout(), out._layout())):
+        p = job.planes[k]
+        p.src_dev, p.dst_dev, p.src_pitch, p.dst_pitch, p.src_step, p.dst_step = s.data_ptr(), d.data_ptr(), sp, dp, ss, ds
+    job.height, job.width, job.n_heads, job.method, job.color = H, W, n, plan.method, y | u << 8 | v << 16
+    job.region = _lib_video.REGION_MAP if owner_dev is not None else _lib_video.REGION_ELLIPSE if region == "ellipse" else _lib_video.REGION_BOX
+    if n:
+        job.luma_heads, job.chroma_heads = luma_rows.ctypes.data, chroma_rows.ctypes.data
+    if taps.size:
+        job.taps, job.n_taps = taps.ctypes.data, taps.size
+    if owner_dev is not None:
+        job.owner_dev = owner_dev.data_ptr()
+    need = int(lib.vghy_anonymize_workspace_bytes(job))
+    if need <= 0:
+        _lib_video.check(-1)  # raises with the library's own message
+    with torch.cuda.device(dev):
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)  # allocated, used and (by the caching allocator) reused in the order of this stream
+        _lib_video.check(lib.vghy_anonymize(job, workspace.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    return out

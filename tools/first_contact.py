@@ -15,7 +15,8 @@ check prints PASS / FAIL / SKIPPED with the number behind it, and the exit code 
                        cv2.getRotationMatrix2D + cv2.warpAffine, bit for bit (utils.py:93-117); PredictionResult.draw (csrc/draw.hip, OpenCV's rectangle / polylines /
                        circle restated) for "full", "bbox", "landmarks" and "points" against the reference's own loop of cv2 calls (draw_utils.py), bit for bit, with
                        the time that loop takes for the same heads.  Also REPORTS (does not require) the largest byte difference between video.YUV420Frame.to_rgb
-                       (bt601, limited range) and cv2.cvtColor(..., COLOR_YUV2RGB_NV12): that parity is unpinned.
+                       (bt601, limited range) and cv2.cvtColor(..., COLOR_YUV2RGB_NV12), and between video.YUV420Frame.from_rgb and cv2.cvtColor(..., COLOR_RGB2YUV_I420):
+                       those parities are unpinned.
   4. --images + weights (+ --pkl): bf16 / fp16 / int8 / fp8 against the fp16x3 parity mode on those photographs -- dense boxes IoU, scores, the kept detections'
                        parameters and vertices; int8 / fp8 calibrated on the same photographs.
   5. pycocotools     : wherever that package is installed, detection_metrics.average_precision (csrc/detection_ap.hip) against COCOeval(..., 'bbox') itself on a seeded set
@@ -162,6 +163,15 @@ def main():
                 d = np.abs(got.astype(np.int32) - cv2.cvtColor(surf, cv2.COLOR_YUV2RGB_NV12).astype(np.int32))
                 yworst, ybad, ytotal = max(yworst, int(d.max())), ybad + int((d > 0).sum()), ytotal + d.size
             print(f"[REPORT] YUV420Frame.to_rgb (bt601, limited) vs cv2 COLOR_YUV2RGB_NV12 (parity unpinned): max |diff| {yworst}, {ybad} of {ytotal} bytes differ", flush=True)
+            # YUV420Frame.from_rgb (the packer of include/vgh_video.h, bt601 limited range) against cv2.cvtColor(COLOR_RGB2YUV_I420): REPORTED as well -- cv2 has
+            # its own fixed-point coefficients and takes a block's chroma its own way
+            pworst, pbad, ptotal = 0, 0, 0
+            for h, w in ((480, 640), (1080, 1920), (2, 2)):
+                im = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+                got = np.concatenate([p.cpu().numpy().reshape(-1) for p in YUV420Frame.from_rgb(im, "i420", "bt601").planes])
+                d = np.abs(got.astype(np.int32) - cv2.cvtColor(im, cv2.COLOR_RGB2YUV_I420).reshape(-1).astype(np.int32))
+                pworst, pbad, ptotal = max(pworst, int(d.max())), pbad + int((d > 0).sum()), ptotal + d.size
+            print(f"[REPORT] YUV420Frame.from_rgb (bt601, limited, I420) vs cv2 COLOR_RGB2YUV_I420 (parity unpinned): max |diff| {pworst}, {pbad} of {ptotal} bytes differ", flush=True)
             # the warp of get_aligned_heads (csrc/aligned.hip, OpenCV's 8-bit bilinear warpAffine restated) against cv2.getRotationMatrix2D + cv2.warpAffine
             from head_detector_amd import aligned
 
