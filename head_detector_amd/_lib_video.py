@@ -1,30 +1,21 @@
 """ctypes binding of libvghvideo.so (include/vgh_video.h): heads anonymised in the planes of a YUV 4:2:0 frame, and RGB packed into such planes.  A library of
 its own: none of libvgh.so, libvghview.so, libvghvis.so, libvghtex.so, libvgheval.so, libvghmerge.so, libvghtrack.so and libvghanon.so knows of it, and their
-bindings do not load it; like them there is NO fallback: a missing library raises ``VghError``."""
+bindings do not load it; this one takes the constants of ``_lib_anon`` (importing that module loads no library: ``load()`` is lazy) and loads nothing but its
+own library.  Like them there is NO fallback: a missing library raises ``VghError``."""
 from __future__ import annotations
 
 import ctypes as C
 import os
 from typing import Optional
 
-import numpy as np
-
 from ._companion import load_library, raise_for
 from ._lib import VghError  # noqa: F401 (callers name it through this module)
+# The caps (VGHY_MAX_*, VGHY_TAP_SUM), the methods, the regions and the head row (vghy_head: one row of the job's ``luma_heads`` / ``chroma_heads`` arrays) are
+# those of vgh_anon.h, number for number, so that the plan of one serves the other: Python states them once.
+from ._lib_anon import HEAD_DTYPE, MAX_CELLS, MAX_COORD, MAX_HEADS, MAX_RADIUS, MAX_SIDE, METHODS, REGION_BOX, REGION_ELLIPSE, REGION_MAP, TAP_SUM  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libvghvideo.so")
-MAX_SIDE = 32767  # = VGHY_MAX_SIDE
-MAX_COORD = 16777216  # = VGHY_MAX_COORD
-MAX_HEADS = 65536  # = VGHY_MAX_HEADS
-MAX_CELLS = 64  # = VGHY_MAX_CELLS
-MAX_RADIUS = 1024  # = VGHY_MAX_RADIUS
-TAP_SUM = 65536  # = VGHY_TAP_SUM
-METHODS = {"fill": 0, "pixelate": 1, "blur": 2}  # = VGHY_METHOD_*
-REGION_BOX, REGION_ELLIPSE, REGION_MAP = 0, 1, 2  # = VGHY_REGION_*
-
-# vghy_head: one row of the job's ``luma_heads`` / ``chroma_heads`` arrays (eight int32)
-HEAD_DTYPE = np.dtype([(name, np.int32) for name in ("x0", "y0", "x1", "y1", "cell", "radius", "tap_offset", "reserved")])
 
 
 class Plane(C.Structure):

@@ -172,6 +172,41 @@ def _byte_range(t: torch.Tensor):
     return t.data_ptr(), t.data_ptr() + last + t.element_size()
 
 
+def _plan_on_host(shape, heads, method: str, region: str, margin, cells, strength, owner, tables=None) -> Optional[AnonymizePlan]:
+    """The front half that ``anonymize_heads`` and ``video.anonymize_frame`` share, without a GPU: the checks of ``owner`` against the (H, W) of ``shape``, and the
+    plan -- or, for ``region="mesh"`` with heads, None after the argument checks alone: their boxes are the meshes' pixel bounds, which ``_plan_on_device`` finds."""
+    n = len(heads)
+    if owner is not None and tuple(owner.shape) != tuple(shape[:2]):
+        raise ValueError(f"anonymize: owner must be int32 {tuple(shape[:2])}, got {tuple(owner.shape)}")
+    if owner is not None and str(owner.dtype).replace("torch.", "") != "int32":
+        raise ValueError(f"anonymize: owner must be int32, got {owner.dtype}")
+    if region != "mesh" or n == 0:
+        return anonymize_plan(shape, heads, method, "box" if n == 0 else region, margin, cells, strength, tables=tables)
+    anonymize_plan(shape, [], method, region, margin, cells, strength, bounds=np.zeros((0, 4)))  # the argument checks that need neither heads nor a GPU
+    return None
+
+
+def _plan_on_device(plan: Optional[AnonymizePlan], dev, shape, heads, method: str, region: str, margin, cells, strength, faces, owner, tables=None):
+    """The back half, on GPU ``dev``: -> (plan, owner_dev).  A plan that ``_plan_on_host`` left open is made from the meshes' pixel bounds, and the mesh silhouettes
+    are the owner map unless the caller brought one (libvghvis.so paints them, Python hands the buffer over); ``owner_dev`` is a contiguous int32 [H, W] tensor on
+    ``dev``, or None where the library paints the owner map from the boxes."""
+    H, W = int(shape[0]), int(shape[1])
+    owner_dev = None
+    if plan is None:
+        from .visibility import head_visibility
+
+        verts = torch.from_numpy(head_vertices(heads)).to(dev)
+        tri = check_triangles(faces, verts.shape[1], "anonymize")
+        plan = anonymize_plan(shape, heads, method, region, margin, cells, strength, bounds=pixel_bounds(verts, tri, H, W), tables=tables)
+        if owner is None:
+            owner_dev = head_visibility(heads, faces, H, W, occlusion="order", barycentric=False, to_host=False).head_index
+    if owner is not None:
+        owner_dev = owner.to(dev) if isinstance(owner, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(owner)).to(dev)
+    if owner_dev is not None:
+        owner_dev = owner_dev.contiguous()
+    return plan, owner_dev
+
+
 def anonymize_heads(image, heads, method: str = "pixelate", region: str = "ellipse", *, margin: float = 0.1, cells: int = 8, strength: float = 0.1, color=(0, 0, 0),
                     faces=None, owner=None, out=None, to_host: bool = True):
     """A NEW uint8 [H, W, 3] image: ``image`` with every head anonymised (the module text states the rules).  ``image`` is a NumPy array (uploaded once) or a
@@ -187,15 +222,7 @@ def anonymize_heads(image, heads, method: str = "pixelate", region: str = "ellip
     if len(shape) != 3 or shape[2] != 3:
         raise ValueError(f"anonymised images need a uint8 image [H,W,3]; got {shape}")
     n = len(heads)
-    if owner is not None and tuple(owner.shape) != shape[:2]:
-        raise ValueError(f"anonymize: owner must be int32 {shape[:2]}, got {tuple(owner.shape)}")
-    if owner is not None and str(owner.dtype).replace("torch.", "") != "int32":
-        raise ValueError(f"anonymize: owner must be int32, got {owner.dtype}")
-    plan = None
-    if region != "mesh" or n == 0:
-        plan = anonymize_plan(shape, heads, method, "box" if n == 0 else region, margin, cells, strength)
-    else:
-        anonymize_plan(shape, [], method, region, margin, cells, strength, bounds=np.zeros((0, 4)))  # the argument checks that need neither heads nor a GPU
+    plan = _plan_on_host(shape, heads, method, region, margin, cells, strength, owner)
     lib = _lib_anon.load()
     src = _device_image(image, "anonymised images")
     H, W = int(src.shape[0]), int(src.shape[1])
@@ -208,19 +235,7 @@ def anonymize_heads(image, heads, method: str = "pixelate", region: str = "ellip
         (s0, s1), (d0, d1) = _byte_range(src), _byte_range(out)
         if s0 < d1 and d0 < s1:
             raise ValueError("anonymize: out overlaps the source image (the source is never modified)")
-    owner_dev = None
-    if plan is None:  # the mesh silhouettes: libvghvis.so paints them, Python hands the buffer over
-        from .visibility import head_visibility
-
-        verts = torch.from_numpy(head_vertices(heads)).to(dev)
-        tri = check_triangles(faces, verts.shape[1], "anonymize")
-        plan = anonymize_plan(shape, heads, method, region, margin, cells, strength, bounds=pixel_bounds(verts, tri, H, W))
-        if owner is None:
-            owner_dev = head_visibility(heads, faces, H, W, occlusion="order", barycentric=False, to_host=False).head_index
-    if owner is not None:
-        owner_dev = owner.to(dev) if isinstance(owner, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(owner)).to(dev)
-    if owner_dev is not None:
-        owner_dev = owner_dev.contiguous()
+    plan, owner_dev = _plan_on_device(plan, dev, shape, heads, method, region, margin, cells, strength, faces, owner)
     job = _lib_anon.Job()
     job.src_dev, job.src_pitch_bytes, job.dst_dev = src.data_ptr(), (src.stride(0) if H > 1 else 3 * W), out.data_ptr()
     job.height, job.width, job.n_heads, job.method, job.color = H, W, n, plan.method, colour

@@ -27,6 +27,7 @@ class Companion(NamedTuple):
 
 HOST_HEADERS = ["companion_host.h"]  # the host plumbing of every companion (codes, message, check macros, staging, queue-then-record): header-only
 RASTER_HEADERS = HOST_HEADERS + ["tile_fold.h"]  # the tile-major triangle fold: header-only, compiled into each of the three libraries that rasterise
+ANON_HEADERS = HOST_HEADERS + ["head_rows.h"]  # the head rows of the two anonymisers (RGB images, YUV planes): header-only, compiled into each of the two
 COMPANIONS = [  # built in this order, before the core
     # benchmark metrics, mesh (Z_n, chamfer) and detection (COCO-style box AP): float64 in a stated operation order, so no contraction into fused
     # multiply-adds anywhere in this library
@@ -42,12 +43,12 @@ COMPANIONS = [  # built in this order, before the core
 # Libraries on the result side that compose the companions' outputs in Python (and link none of them): built like a companion, before the core
 APPLICATIONS = [
     # head anonymisation (pixelate, blur, fill): integer arithmetic only, equal bit for bit to its NumPy restatement
-    Companion("libvghanon.so", ["anonymize.hip"], HOST_HEADERS, "vgh_anon.h", [], "build_anon"),
+    Companion("libvghanon.so", ["anonymize.hip"], ANON_HEADERS, "vgh_anon.h", [], "build_anon"),
 ]
 # Libraries on the video side (frames in their own YUV planes): built like a companion, before the core
 VIDEO = [
     # heads anonymised in the planes of a YUV 4:2:0 frame, and RGB packed into such planes: integer arithmetic only, equal bit for bit to its NumPy restatement
-    Companion("libvghvideo.so", ["yuv_anonymize.hip", "yuv_pack.hip"], HOST_HEADERS, "vgh_video.h", [], "build_video"),
+    Companion("libvghvideo.so", ["yuv_anonymize.hip", "yuv_pack.hip"], ANON_HEADERS, "vgh_video.h", [], "build_video"),
 ]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]
 

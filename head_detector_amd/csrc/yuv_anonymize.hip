@@ -14,23 +14,25 @@
 // WRITE: write_kernel, one lane per sample of every head's clipped box, stores the value (fill: the colour) where the head owns the sample: the only pass
 // that writes a frame in place.  A plane that is out of place is copied first (copy_kernel, the one pass that walks a whole plane).
 // Heads x tiles, x cells and x row segments are enumerated through prefix sums made on the host; a workgroup finds its head by bisection.  Integer arithmetic
-// only.
+// only.  The head rows, their per-head checks and offsets, the bisection, the owner painter and the staged upload are csrc/head_rows.h, shared with
+// csrc/anonymize.hip; the checks of the frame, the workspace layout and every kernel that touches a sample are here.
 #include <string.h>
 
 #include <map>
 #include <mutex>
-#include <vector>
 
 #include "../../include/vgh_video.h"
 #include "companion_host.h"
+#include "head_rows.h"
 
 namespace {
 
-using namespace companion;
+using namespace head_rows;
 static_assert(VGHY_OK == OK && VGHY_ERR_INVALID == ERR_INVALID && VGHY_ERR_HIP == ERR_HIP && VGHY_ERR_NOMEM == ERR_NOMEM, "companion_host.h returns these codes");
+static_assert(VGHY_MAX_SIDE == MAX_SIDE && VGHY_MAX_COORD == MAX_COORD && VGHY_MAX_HEADS == MAX_HEADS && VGHY_MAX_CELLS == MAX_CELLS && VGHY_MAX_RADIUS == MAX_RADIUS &&
+                  VGHY_TAP_SUM == TAP_SUM && VGHY_METHOD_FILL == METHOD_FILL && VGHY_METHOD_PIXELATE == METHOD_PIXELATE && VGHY_METHOD_BLUR == METHOD_BLUR,
+              "head_rows.h plans with these caps and methods");
 
-constexpr int TILE_W = 64, TILE_H = 4;  // a tile of the owner painter, the vertical pass and the write pass: 256 lanes, one wave a row
-constexpr int SEGMENT = 256;            // samples of one row segment of the horizontal pass
 constexpr int LINE_SAMPLES = SEGMENT + 2 * VGHY_MAX_RADIUS;  // the segment and the widest halo in LDS (luma: 256 + 2 * 1024 bytes), so r is never chunked
 
 // One channel of a plane group as the kernels read it, and the group: NC channels of one width and height.
@@ -46,40 +48,6 @@ struct View {
     int32_t W, H;          // of the plane
     int32_t spair, dpair;  // NC = 2: 0 = two planes; 1 / 2 = c[0] / c[1] is the even, lower byte of interleaved pairs
 };
-
-// One head in one plane group.  (cx0, cy0, cx1, cy1) is the geometry box clipped to the plane, all 0 if nothing is left.  A sample's value lies at
-// values[val_at + ((y - vy0) / vdiv) * vstride + (x - vx0) / vdiv]: pixelate (x0, y0, cell, cells in a row), blur (cx0, cy0, 1, clipped width).
-struct HeadRow {
-    int32_t x0, y0, x1, y1;
-    int32_t cx0, cy0, cx1, cy1;
-    int32_t vx0, vy0, vdiv, vstride;
-    int32_t radius, tap_at, hy0, hy1;  // blur: h holds rows hy0 .. hy1 - 1 = the clipped box extended by r rows and clamped to the plane
-    int64_t val_at, h_at;              // in samples: NC bytes of the values, NC u16 of h each
-};
-static_assert(sizeof(HeadRow) == 80, "uploaded as it is");
-
-// the largest i in [0, n) with prefix[i] <= item; prefix[0] = 0 and item < prefix[n], so prefix[i + 1] > item: heads without items are stepped over
-__device__ __forceinline__ int head_of(const uint32_t* __restrict__ prefix, int n, uint32_t item) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (prefix[mid] <= item) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-__device__ __forceinline__ bool in_ellipse(const HeadRow& r, int x, int y) {
-    const int64_t wb = r.x1 - r.x0, hb = r.y1 - r.y0, ex = 2 * (int64_t)(x - r.x0) + 1 - wb, ey = 2 * (int64_t)(y - r.y0) + 1 - hb;
-    return ex * ex * hb * hb + ey * ey * wb * wb <= wb * wb * hb * hb;
-}
-
-// the sample of lane `threadIdx.x` in tile `t` of the head's clipped box; false = outside the box
-__device__ __forceinline__ bool tile_sample(const HeadRow& r, uint32_t t, int& x, int& y) {
-    const uint32_t across = (uint32_t)(r.cx1 - r.cx0 + TILE_W - 1) / TILE_W, ty = t / across, tx = t - ty * across;
-    x = r.cx0 + (int)tx * TILE_W + (int)(threadIdx.x & 63);
-    y = r.cy0 + (int)ty * TILE_H + (int)(threadIdx.x >> 6);
-    return x < r.cx1 && y < r.cy1;  // cx1 <= W and cy1 <= H of the plane: a sample that passes lies in the plane
-}
 
 template <int NC>
 __device__ __forceinline__ void load(const View<NC>& P, int x, int y, uint32_t (&v)[NC]) {
@@ -131,16 +99,6 @@ __device__ __forceinline__ bool owned_by(const int32_t* __restrict__ owner, int 
             }
         return o == i;
     }
-}
-
-// ---- owner (luma) ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void paint_owner_kernel(const HeadRow* __restrict__ rows, const uint32_t* __restrict__ tiles, int n, int32_t* __restrict__ owner, int W, int ellipse) {
-    const int i = head_of(tiles, n, blockIdx.x);
-    const HeadRow r = rows[i];
-    int x, y;
-    if (!tile_sample(r, blockIdx.x - tiles[i], x, y)) return;
-    if (ellipse && !in_ellipse(r, x, y)) return;
-    atomicMax(owner + (size_t)y * W + x, i);
 }
 
 // ---- pixelate -------------------------------------------------------------------------------------------------------------------------------
@@ -292,20 +250,12 @@ __global__ __launch_bounds__(256) void copy_kernel(const uint8_t* __restrict__ s
 }
 
 // ---- the host half: every check and every offset, no HIP call -----------------------------------------------------------------------------------
-struct GroupPlan {  // one plane group: luma, or chroma
-    std::vector<HeadRow> rows;
-    std::vector<uint32_t> tiles, cells, segments;  // prefix sums over the heads, n + 1 entries each
-    int64_t n_values = 0, n_h = 0;                 // samples
-    int64_t at_values = 0, at_h = 0;               // byte offsets in the workspace
-};
 struct Plan {
     GroupPlan luma, chroma;
-    int64_t total = 0;
+    int64_t values_l = 0, values_c = 0, h_l = 0, h_c = 0, total = 0;  // byte offsets in the workspace (the owner plane, if painted, is at 0)
     bool in_place[3] = {false, false, false};
     int spair = 0, dpair = 0;
 };
-
-int64_t up16(int64_t v) { return (v + 15) & ~(int64_t)15; }
 
 const char* const PLANE_NAMES[3] = {"Y", "U", "V"};
 
@@ -322,71 +272,6 @@ int pair_of(const void* u, const void* v, int64_t upitch, int64_t vpitch, int us
     if (b == a + 1 && !(a & 1)) return 1;
     if (a == b + 1 && !(b & 1)) return 2;
     return 0;
-}
-
-// the rows of one plane group (pw x ph samples): every per-head check, the clipped boxes and the offsets
-int plan_group(const vghy_anonymize_job& j, const vghy_head* heads, const char* kind, int64_t PW, int64_t PH, GroupPlan& p, const char* who) {
-    const int n = j.n_heads;
-    const bool blur = j.method == VGHY_METHOD_BLUR, pixelate = j.method == VGHY_METHOD_PIXELATE;
-    p.rows.assign((size_t)n, HeadRow{});
-    p.tiles.assign((size_t)n + 1, 0);
-    p.cells.assign((size_t)n + 1, 0);
-    p.segments.assign((size_t)n + 1, 0);
-    int64_t n_tiles = 0, n_cells = 0, n_segments = 0;
-    int32_t ok_at = -1, ok_radius = -1;  // the table checked last: heads usually share one
-    for (int i = 0; i < n; ++i) {
-        const vghy_head& g = heads[i];
-        HeadRow& r = p.rows[(size_t)i];
-        CH_REQUIRE(g.x0 > -VGHY_MAX_COORD && g.x0 < VGHY_MAX_COORD && g.y0 > -VGHY_MAX_COORD && g.y0 < VGHY_MAX_COORD, "%s: %s head %d: corner (%d, %d) outside +-2^24", who, kind, i, g.x0,
-                   g.y0);
-        const int64_t wb = (int64_t)g.x1 - g.x0, hb = (int64_t)g.y1 - g.y0;
-        CH_REQUIRE(wb >= 0 && hb >= 0 && wb <= VGHY_MAX_SIDE && hb <= VGHY_MAX_SIDE, "%s: %s head %d: box sides %lld x %lld outside 0 .. %d", who, kind, i, (long long)wb, (long long)hb,
-                   VGHY_MAX_SIDE);
-        CH_REQUIRE(g.reserved == 0, "%s: %s head %d: reserved is %d, not 0", who, kind, i, g.reserved);
-        r.x0 = g.x0, r.y0 = g.y0, r.x1 = g.x1, r.y1 = g.y1;
-        r.vdiv = 1;
-        const int cx0 = g.x0 > 0 ? g.x0 : 0, cy0 = g.y0 > 0 ? g.y0 : 0, cx1 = g.x1 < PW ? g.x1 : (int)PW, cy1 = g.y1 < PH ? g.y1 : (int)PH;
-        const bool empty = cx1 <= cx0 || cy1 <= cy0;
-        if (!empty) r.cx0 = cx0, r.cy0 = cy0, r.cx1 = cx1, r.cy1 = cy1;
-        const int64_t cw = r.cx1 - r.cx0, ch = r.cy1 - r.cy0;
-        if (pixelate) {
-            CH_REQUIRE(g.cell >= 1 && g.cell <= VGHY_MAX_SIDE, "%s: %s head %d: cell side %d outside 1 .. %d", who, kind, i, g.cell, VGHY_MAX_SIDE);
-            const int64_t across = (wb + g.cell - 1) / g.cell, down = (hb + g.cell - 1) / g.cell;
-            CH_REQUIRE(across <= VGHY_MAX_CELLS && down <= VGHY_MAX_CELLS, "%s: %s head %d: %lld x %lld cells of side %d exceed %d a side", who, kind, i, (long long)across, (long long)down,
-                       g.cell, VGHY_MAX_CELLS);
-            r.vx0 = g.x0, r.vy0 = g.y0, r.vdiv = g.cell, r.vstride = (int32_t)across, r.val_at = p.n_values;
-            if (!empty) n_cells += across * down, p.n_values += across * down;
-        }
-        if (blur) {
-            CH_REQUIRE(g.radius >= 0 && g.radius <= VGHY_MAX_RADIUS, "%s: %s head %d: radius %d outside 0 .. %d", who, kind, i, g.radius, VGHY_MAX_RADIUS);
-            CH_REQUIRE(g.tap_offset >= 0 && (int64_t)g.tap_offset + g.radius < j.n_taps, "%s: %s head %d: taps %d .. %lld outside the table of %d", who, kind, i, g.tap_offset,
-                       (long long)g.tap_offset + g.radius, j.n_taps);
-            if (g.tap_offset != ok_at || g.radius != ok_radius) {
-                int64_t sum = 0;
-                for (int k = 0; k <= g.radius; ++k) {
-                    const int32_t t = j.taps[g.tap_offset + k];
-                    CH_REQUIRE(t >= 0 && t <= VGHY_TAP_SUM, "%s: %s head %d: tap %d is %d, outside 0 .. %d", who, kind, i, k, t, VGHY_TAP_SUM);
-                    sum += k ? 2 * (int64_t)t : t;
-                }
-                CH_REQUIRE(sum == VGHY_TAP_SUM, "%s: %s head %d: tap sum %lld is not %d", who, kind, i, (long long)sum, VGHY_TAP_SUM);
-                ok_at = g.tap_offset, ok_radius = g.radius;
-            }
-            r.radius = g.radius, r.tap_at = g.tap_offset;
-            r.vx0 = r.cx0, r.vy0 = r.cy0, r.vdiv = 1, r.vstride = (int32_t)cw, r.val_at = p.n_values, r.h_at = p.n_h;
-            r.hy0 = r.cy0 - g.radius > 0 ? r.cy0 - g.radius : 0;
-            r.hy1 = r.cy1 + g.radius < PH ? r.cy1 + g.radius : (int)PH;
-            if (!empty) {
-                p.n_values += cw * ch;
-                p.n_h += (int64_t)(r.hy1 - r.hy0) * cw;
-                n_segments += (int64_t)(r.hy1 - r.hy0) * ((cw + SEGMENT - 1) / SEGMENT);
-            }
-        }
-        if (!empty) n_tiles += ((cw + TILE_W - 1) / TILE_W) * ((ch + TILE_H - 1) / TILE_H);
-        CH_REQUIRE(n_tiles <= INT32_MAX && n_cells <= INT32_MAX && n_segments <= INT32_MAX, "%s: %s head %d: the boxes so far exceed one launch (%lld tiles, %lld cells, %lld row segments)",
-                   who, kind, i, (long long)n_tiles, (long long)n_cells, (long long)n_segments);
-        p.tiles[(size_t)i + 1] = (uint32_t)n_tiles, p.cells[(size_t)i + 1] = (uint32_t)n_cells, p.segments[(size_t)i + 1] = (uint32_t)n_segments;
-    }
-    return OK;
 }
 
 // `who` words the messages: the two entry points share every check of the job
@@ -429,15 +314,15 @@ int make_plan(const vghy_anonymize_job* job, Plan& p, const char* who) {
     CH_REQUIRE(n == 0 || (j.luma_heads && j.chroma_heads), "%s: null heads (luma_heads %p, chroma_heads %p)", who, (const void*)j.luma_heads, (const void*)j.chroma_heads);
     CH_REQUIRE(j.n_taps >= 0, "%s: n_taps %d is negative", who, j.n_taps);
     if (blur && n) CH_REQUIRE(j.taps && j.n_taps >= 1, "%s: blur needs a tap table (taps %p, n_taps %d)", who, (const void*)j.taps, j.n_taps);
-    if (int rc = plan_group(j, j.luma_heads, "luma", W, H, p.luma, who)) return rc;
-    if (int rc = plan_group(j, j.chroma_heads, "chroma", CW, CH, p.chroma, who)) return rc;
+    if (int rc = plan_heads(j.luma_heads, n, j.method, j.taps, j.n_taps, W, H, p.luma, who, "luma head")) return rc;
+    if (int rc = plan_heads(j.chroma_heads, n, j.method, j.taps, j.n_taps, CW, CH, p.chroma, who, "chroma head")) return rc;
     p.spair = pair_of(j.planes[1].src_dev, j.planes[2].src_dev, j.planes[1].src_pitch, j.planes[2].src_pitch, j.planes[1].src_step, j.planes[2].src_step);
     p.dpair = pair_of(j.planes[1].dst_dev, j.planes[2].dst_dev, j.planes[1].dst_pitch, j.planes[2].dst_pitch, j.planes[1].dst_step, j.planes[2].dst_step);
-    p.luma.at_values = up16(j.region == VGHY_REGION_MAP ? 0 : 4 * H * W);
-    p.chroma.at_values = up16(p.luma.at_values + p.luma.n_values);
-    p.luma.at_h = up16(p.chroma.at_values + 2 * p.chroma.n_values);
-    p.chroma.at_h = up16(p.luma.at_h + 2 * p.luma.n_h);
-    p.total = up16(p.chroma.at_h + 4 * p.chroma.n_h);
+    p.values_l = up16(j.region == VGHY_REGION_MAP ? 0 : 4 * H * W);
+    p.values_c = up16(p.values_l + p.luma.n_values);
+    p.h_l = up16(p.values_c + 2 * p.chroma.n_values);
+    p.h_c = up16(p.h_l + 2 * p.luma.n_h);
+    p.total = up16(p.h_c + 4 * p.chroma.n_h);
     if (p.total < 16) p.total = 16;
     return OK;
 }
@@ -472,55 +357,39 @@ extern "C" VGHY_API int vghy_anonymize(const vghy_anonymize_job* job, void* work
     CH_HIP(hipGetDevice(&device));
     std::lock_guard<std::mutex> lock(g_mutex);
     Staging& s = g_staging[device];
-    // one upload: [luma rows | chroma rows | 2 x (tiles | cells | segments) | taps], each from a 16-byte boundary
-    const size_t prefix_bytes = ((size_t)n + 1) * 4, rows_bytes = align16((size_t)n * sizeof(HeadRow)), prefix_room = align16(prefix_bytes);
-    const size_t at_prefix = 2 * rows_bytes, at_taps = at_prefix + 6 * prefix_room, total = align16(at_taps + (blur ? (size_t)j.n_taps * 4 : 0));
+    // one upload: [luma: the rows and their prefix sums | chroma: the same | taps], each from a 16-byte boundary
+    const size_t at_taps = 2 * group_bytes(n), total = align16(at_taps + (blur ? (size_t)j.n_taps * 4 : 0));
     if (int rc = reserve(s, total, "anonymize")) return rc;  // also waits for this device's previous call
-    uint8_t* host = s.host;
-    const GroupPlan* groups[2] = {&p.luma, &p.chroma};
-    for (int g = 0; g < 2; ++g) {
-        if (n) memcpy(host + g * rows_bytes, groups[g]->rows.data(), (size_t)n * sizeof(HeadRow));
-        memcpy(host + at_prefix + (3 * g + 0) * prefix_room, groups[g]->tiles.data(), prefix_bytes);
-        memcpy(host + at_prefix + (3 * g + 1) * prefix_room, groups[g]->cells.data(), prefix_bytes);
-        memcpy(host + at_prefix + (3 * g + 2) * prefix_room, groups[g]->segments.data(), prefix_bytes);
-    }
-    if (blur && j.n_taps) memcpy(host + at_taps, j.taps, (size_t)j.n_taps * 4);
+    const GroupOnDevice gl = stage_group(p.luma, s, 0), gc = stage_group(p.chroma, s, group_bytes(n));
+    if (blur && j.n_taps) memcpy(s.host + at_taps, j.taps, (size_t)j.n_taps * 4);
     // from here on work is queued (companion_host.h, queue-then-record)
-    const uint8_t* d = s.dev;
-    const HeadRow* rows[2] = {(const HeadRow*)d, (const HeadRow*)(d + rows_bytes)};
-    const uint32_t *tiles[2], *cells[2], *segments[2];
-    for (int g = 0; g < 2; ++g) {
-        tiles[g] = (const uint32_t*)(d + at_prefix + (3 * g + 0) * prefix_room);
-        cells[g] = (const uint32_t*)(d + at_prefix + (3 * g + 1) * prefix_room);
-        segments[g] = (const uint32_t*)(d + at_prefix + (3 * g + 2) * prefix_room);
-    }
-    const int32_t* taps = (const int32_t*)(d + at_taps);
+    const int32_t* taps = (const int32_t*)(s.dev + at_taps);
     uint8_t* ws = (uint8_t*)workspace_dev;
     int32_t* painted = (int32_t*)ws;
     const int32_t* owner = paint ? painted : j.owner_dev;
     View<1> luma{{chan_of(j.planes[0])}, W, H, 0, 0};
     View<2> chroma{{chan_of(j.planes[1]), chan_of(j.planes[2])}, CW, CH, p.spair, p.dpair};
-    uint8_t *values_l = ws + p.luma.at_values, *values_c = ws + p.chroma.at_values;
-    uint16_t *h_l = (uint16_t*)(ws + p.luma.at_h), *h_c = (uint16_t*)(ws + p.chroma.at_h);
+    uint8_t *values_l = ws + p.values_l, *values_c = ws + p.values_c;
+    uint16_t *h_l = (uint16_t*)(ws + p.h_l), *h_c = (uint16_t*)(ws + p.h_c);
     const uint32_t tiles_l = p.luma.tiles[(size_t)n], tiles_c = p.chroma.tiles[(size_t)n];
     Queue q;
-    CH_QUEUE(q, hipMemcpyAsync(s.dev, host, total, hipMemcpyHostToDevice, st));
+    CH_QUEUE(q, hipMemcpyAsync(s.dev, s.host, total, hipMemcpyHostToDevice, st));
     if (paint) {
         CH_QUEUE(q, hipMemsetAsync(painted, 0xff, (size_t)W * (size_t)H * 4, st));  // -1 everywhere
-        if (tiles_l && q.ok()) hipLaunchKernelGGL(paint_owner_kernel, dim3(tiles_l), dim3(256), 0, st, rows[0], tiles[0], n, painted, W, (int)(j.region == VGHY_REGION_ELLIPSE));
+        if (tiles_l && q.ok()) hipLaunchKernelGGL(paint_owner_kernel, dim3(tiles_l), dim3(256), 0, st, gl.rows, gl.tiles, n, painted, W, (int)(j.region == VGHY_REGION_ELLIPSE));
     }
     if (pixelate && q.ok()) {
-        if (const uint32_t c = p.luma.cells[(size_t)n]) hipLaunchKernelGGL(cells_kernel<1>, dim3(c), dim3(256), 0, st, rows[0], cells[0], n, luma, values_l);
-        if (const uint32_t c = p.chroma.cells[(size_t)n]) hipLaunchKernelGGL(cells_kernel<2>, dim3(c), dim3(256), 0, st, rows[1], cells[1], n, chroma, values_c);
+        if (const uint32_t c = p.luma.cells[(size_t)n]) hipLaunchKernelGGL(cells_kernel<1>, dim3(c), dim3(256), 0, st, gl.rows, gl.cells, n, luma, values_l);
+        if (const uint32_t c = p.chroma.cells[(size_t)n]) hipLaunchKernelGGL(cells_kernel<2>, dim3(c), dim3(256), 0, st, gc.rows, gc.cells, n, chroma, values_c);
     }
     if (blur && q.ok()) {
         if (const uint32_t g = p.luma.segments[(size_t)n]) {
-            hipLaunchKernelGGL(blur_rows_kernel<1>, dim3(g), dim3(256), 0, st, rows[0], segments[0], n, taps, luma, h_l);
-            hipLaunchKernelGGL(blur_cols_kernel<1>, dim3(tiles_l), dim3(256), 0, st, rows[0], tiles[0], n, taps, owner, W, H, H, (const uint16_t*)h_l, values_l);
+            hipLaunchKernelGGL(blur_rows_kernel<1>, dim3(g), dim3(256), 0, st, gl.rows, gl.segments, n, taps, luma, h_l);
+            hipLaunchKernelGGL(blur_cols_kernel<1>, dim3(tiles_l), dim3(256), 0, st, gl.rows, gl.tiles, n, taps, owner, W, H, H, (const uint16_t*)h_l, values_l);
         }
         if (const uint32_t g = p.chroma.segments[(size_t)n]) {
-            hipLaunchKernelGGL(blur_rows_kernel<2>, dim3(g), dim3(256), 0, st, rows[1], segments[1], n, taps, chroma, h_c);
-            hipLaunchKernelGGL(blur_cols_kernel<2>, dim3(tiles_c), dim3(256), 0, st, rows[1], tiles[1], n, taps, owner, W, H, CH, (const uint16_t*)h_c, values_c);
+            hipLaunchKernelGGL(blur_rows_kernel<2>, dim3(g), dim3(256), 0, st, gc.rows, gc.segments, n, taps, chroma, h_c);
+            hipLaunchKernelGGL(blur_cols_kernel<2>, dim3(tiles_c), dim3(256), 0, st, gc.rows, gc.tiles, n, taps, owner, W, H, CH, (const uint16_t*)h_c, values_c);
         }
     }
     if (q.ok()) {  // the planes that are out of place: every sample copied, an interleaved pair that stays one as one plane of 2 CW bytes
@@ -534,8 +403,8 @@ extern "C" VGHY_API int vghy_anonymize(const vghy_anonymize_job* job, void* work
         }
     }
     if (q.ok()) {
-        if (tiles_l) hipLaunchKernelGGL(write_kernel<1>, dim3(tiles_l), dim3(256), 0, st, rows[0], tiles[0], n, owner, W, H, (const uint8_t*)values_l, fill, (uint32_t)j.color & 255u, luma);
-        if (tiles_c) hipLaunchKernelGGL(write_kernel<2>, dim3(tiles_c), dim3(256), 0, st, rows[1], tiles[1], n, owner, W, H, (const uint8_t*)values_c, fill, (uint32_t)j.color >> 8, chroma);
+        if (tiles_l) hipLaunchKernelGGL(write_kernel<1>, dim3(tiles_l), dim3(256), 0, st, gl.rows, gl.tiles, n, owner, W, H, (const uint8_t*)values_l, fill, (uint32_t)j.color & 255u, luma);
+        if (tiles_c) hipLaunchKernelGGL(write_kernel<2>, dim3(tiles_c), dim3(256), 0, st, gc.rows, gc.tiles, n, owner, W, H, (const uint8_t*)values_c, fill, (uint32_t)j.color >> 8, chroma);
     }
     return finish(q, s, true, st, "anonymize");
 }

@@ -363,7 +363,7 @@ def anonymize_frame(frame: YUV420Frame, heads, method: str = "pixelate", region:
     (NV12 in, I420 out).  Returns the frame written.  There is no CPU path for the samples."""
     from . import _lib_video, anonymize as an
     from ._lib import VghError
-    from .mesh_geometry import check_triangles, head_vertices, pixel_bounds, require_faces
+    from .mesh_geometry import require_faces
 
     an._check_choice(method, region)
     if region == "mesh":
@@ -374,15 +374,8 @@ def anonymize_frame(frame: YUV420Frame, heads, method: str = "pixelate", region:
     H, W, _ = frame.shape
     y, u, v = rgb_to_yuv((rgb & 255, rgb >> 8 & 255, rgb >> 16), frame.matrix, frame.full_range)
     n = len(heads)
-    if owner is not None and tuple(owner.shape) != (H, W):
-        raise ValueError(f"anonymize: owner must be int32 {(H, W)}, got {tuple(owner.shape)}")
-    if owner is not None and str(owner.dtype).replace("torch.", "") != "int32":
-        raise ValueError(f"anonymize: owner must be int32, got {owner.dtype}")
-    plan, tables = None, an.TapTables()  # one tap table for the call: the luma rows' tables first, the chroma rows' behind them
-    if region != "mesh" or n == 0:
-        plan = an.anonymize_plan((H, W), heads, method, "box" if n == 0 else region, margin, cells, strength, tables=tables)
-    else:
-        an.anonymize_plan((H, W), [], method, region, margin, cells, strength, bounds=np.zeros((0, 4)))  # the argument checks that need neither heads nor a GPU
+    tables = an.TapTables()  # one tap table for the call: the luma rows' tables first, the chroma rows' behind them
+    plan = an._plan_on_host((H, W), heads, method, region, margin, cells, strength, owner, tables)
     if out is not None and not (isinstance(out, YUV420Frame) and out.shape == frame.shape and out.device == frame.device):
         raise ValueError(f"anonymize_frame: out must be a YUV420Frame of {H} x {W} on {frame.device}; got {out!r}")
     if not (torch.cuda.is_available() and frame.y.is_cuda):
@@ -400,19 +393,7 @@ def anonymize_frame(frame: YUV420Frame, heads, method: str = "pixelate", region:
             if s0 < d1 and d0 < s1:
                 raise ValueError(f"anonymize_frame: plane {name} of out overlaps the source frame without being exactly its plane {name} (same memory, pitch and "
                                  "step): pass out=frame for in place, or a frame elsewhere")
-    owner_dev = None
-    if plan is None:  # the mesh silhouettes: libvghvis.so paints them at the frame's size, Python hands the buffer over
-        from .visibility import head_visibility
-
-        verts = torch.from_numpy(head_vertices(heads)).to(dev)
-        tri = check_triangles(faces, verts.shape[1], "anonymize")
-        plan = an.anonymize_plan((H, W), heads, method, region, margin, cells, strength, bounds=pixel_bounds(verts, tri, H, W), tables=tables)
-        if owner is None:
-            owner_dev = head_visibility(heads, faces, H, W, occlusion="order", barycentric=False, to_host=False).head_index
-    if owner is not None:
-        owner_dev = owner.to(dev) if isinstance(owner, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(owner)).to(dev)
-    if owner_dev is not None:
-        owner_dev = owner_dev.contiguous()
+    plan, owner_dev = an._plan_on_device(plan, dev, (H, W), heads, method, region, margin, cells, strength, faces, owner, tables)  # the silhouettes at the frame's size
     # the chroma rows: the same formulas on the chroma boxes
     luma_rows = plan.heads
     corners = zip(luma_rows["x0"].tolist(), luma_rows["y0"].tolist(), luma_rows["x1"].tolist(), luma_rows["y1"].tolist())

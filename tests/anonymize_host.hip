@@ -51,7 +51,7 @@ int main() {
     {
         Plan p;
         EXPECT(make_plan(&good, p, "t") == OK && p.rows.size() == 3 && p.tiles[3] == 1 * 10 + 1 * 10 && p.segments[3] == 42 + 40 && p.rows[1].cx0 == 0 && p.rows[1].cy0 == 0 && p.rows[1].hy0 == 0 &&
-               p.rows[1].hy1 == 40 && p.rows[0].hy0 == 9 && p.rows[0].hy1 == 51 && p.rows[2].cx1 == 0 && p.rows[1].h_at == 3 * 42 * 50 && p.rows[1].val_at == 2000);
+               p.rows[1].hy1 == 40 && p.rows[0].hy0 == 9 && p.rows[0].hy1 == 51 && p.rows[2].cx1 == 0 && p.rows[1].h_at == 42 * 50 && p.rows[1].val_at == 2000);
     }
 
     // refusals, each with its message, before anything is queued

@@ -147,12 +147,21 @@ def test_the_library_is_declared_in_the_build():
     from head_detector_amd import build
 
     assert len(build.COMPANIONS) == 6 and not [c for c in build.COMPANIONS if c.lib == "libvghanon.so"]
-    assert build.APPLICATIONS == [build.Companion("libvghanon.so", ["anonymize.hip"], build.HOST_HEADERS, "vgh_anon.h", [], "build_anon")]
+    assert build.ANON_HEADERS == build.HOST_HEADERS + ["head_rows.h"]
+    assert build.APPLICATIONS == [build.Companion("libvghanon.so", ["anonymize.hip"], build.ANON_HEADERS, "vgh_anon.h", [], "build_anon")]
     src = open(os.path.join(ROOT, "head_detector_amd", "csrc", "anonymize.hip")).read()
     assert '#include "companion_host.h"' in src and "static_assert(VGHAN_OK == OK && VGHAN_ERR_INVALID == ERR_INVALID && VGHAN_ERR_HIP == ERR_HIP && VGHAN_ERR_NOMEM == ERR_NOMEM," in src
-    for by_hand in ("hipEventRecord(", "hipEventSynchronize(", "hipHostMalloc(", "hipMalloc(", "set_error(const char", "g_error", "asm", "dlopen", "float", "double",
-                    "hipFuncSetAttribute", "extern __shared__"):
-        assert by_hand not in src, by_hand
+    # the head rows are csrc/head_rows.h's, shared with csrc/yuv_anonymize.hip: included, and defined here no longer
+    assert '#include "head_rows.h"' in src
+    for moved in ("struct HeadRow", "head_of(const uint32_t", "in_ellipse(const HeadRow", "void paint_owner_kernel(const HeadRow", "int64_t up16("):
+        assert moved not in src, moved
+    shared = open(os.path.join(ROOT, "head_detector_amd", "csrc", "head_rows.h")).read()
+    assert all(moved in shared for moved in ("struct HeadRow", "head_of(const uint32_t", "in_ellipse(const HeadRow", "void paint_owner_kernel(const HeadRow", "int64_t up16("))
+    assert '#include "companion_host.h"' in shared and "include/" not in shared and "vghan_" not in shared.lower() and "vghy_" not in shared.lower()  # no public header
+    for text in (src, shared):
+        for by_hand in ("hipEventRecord(", "hipEventSynchronize(", "hipHostMalloc(", "hipMalloc(", "set_error(const char", "g_error", "asm", "dlopen", "float", "double",
+                        "hipFuncSetAttribute", "extern __shared__"):
+            assert by_hand not in text, by_hand
     assert "head_detector_amd/build_anon/" in open(os.path.join(ROOT, ".gitignore")).read().split()
     # nobody else exports the prefix, and the other libraries keep their exports
     pkg = os.path.join(ROOT, "head_detector_amd")
