@@ -118,9 +118,9 @@ class HeadPlan:
         return (max(0, y1 - y0), max(0, x1 - x0), 3)
 
 
-def aligned_head_plan(image_shape: Sequence[int], heads, head_indices: np.ndarray) -> List[HeadPlan]:
+def aligned_head_plan(image_shape: Sequence[int], heads, head_indices: np.ndarray, offset=0.1) -> List[HeadPlan]:
     """detection_result.py:56-70 without the pixels: for every head whether it is rotated (``abs(yaw) < 60``), the matrix, the canvas bounds, the
-    rect and the final slice."""
+    rect and the final slice.  ``offset``: the margin of ``extend_bbox`` (the reference's 0.1)."""
     H, W = int(image_shape[0]), int(image_shape[1])
     plans = []
     for head in heads:
@@ -132,7 +132,7 @@ def aligned_head_plan(image_shape: Sequence[int], heads, head_indices: np.ndarra
         else:
             matrix, bounds = np.array([[1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]), (W, H)
         box = refined_head_bbox(vertices, head_indices)
-        x, y, w, h = (int(v) for v in extend_to_rect(extend_bbox([box.x, box.y, box.w, box.h], offset=0.1)))
+        x, y, w, h = (int(v) for v in extend_to_rect(extend_bbox([box.x, box.y, box.w, box.h], offset=offset)))
         y0, y1, _ = slice(y, y + h).indices(bounds[1])
         x0, x1, _ = slice(x, x + w).indices(bounds[0])
         plans.append(HeadPlan(rotated, matrix, bounds, (x, y, w, h), (x0, y0, x1, y1)))

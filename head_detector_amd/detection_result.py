@@ -15,7 +15,9 @@ texture map out of the image, the second paints textures back onto the heads; bo
 makes one from the template mesh).  ``compare_meshes`` judges the heads against ground-truth meshes with the reference's benchmark metrics (Z_n, chamfer;
 csrc/mesh_metrics.hip, libvgheval.so, ``head_detector_amd.mesh_metrics``).  ``detection_rows`` gives the boxes as the detection benchmarks take them
 (``head_detector_amd.detection_metrics``: COCO-style AP, csrc/detection_ap.hip).  ``anonymize`` returns the image with every head pixelated, blurred or filled, by
-box, ellipse or mesh silhouette (csrc/anonymize.hip, libvghanon.so, ``head_detector_amd.anonymize``): integer arithmetic only, a later head owns an overlap."""
+box, ellipse or mesh silhouette (csrc/anonymize.hip, libvghanon.so, ``head_detector_amd.anonymize``): integer arithmetic only, a later head owns an overlap.
+``get_head_tensors`` hands the heads to a next model: fixed-size, normalised crops of every head in one dense GPU tensor, cut from the image or from the video
+frame's own planes in one launch (csrc/head_tensors.hip, libvghcrop.so, ``head_detector_amd.head_tensors``)."""
 from __future__ import annotations
 
 import os
@@ -149,6 +151,17 @@ class PredictionResult:
         from .aligned import get_aligned_heads
 
         return get_aligned_heads(self.original_image, self.heads, self.head_indices, to_host=to_host)
+
+    def get_head_tensors(self, size: int = 224, **kw):
+        """``head_tensors.head_tensors(source, self.heads, size, **kw)``: every head as one ``size`` x ``size`` crop of ONE dense, normalised GPU tensor for a next
+        model ([n, 3, size, size] float32 by default; csrc/head_tensors.hip, libvghcrop.so), with the matrices back to image coordinates.  The source is the
+        ``source_frame`` if the result was made from a video frame (its YUV planes are used where they are: ``original_image`` may be None), otherwise the
+        ``original_image``.  ``aligned=True`` (the default: the geometry of ``get_aligned_heads``) needs ``head_indices`` -- the result's own unless given;
+        ``aligned=False`` needs no asset.  Keywords and errors: ``head_tensors.head_tensors``."""
+        from .head_tensors import head_tensors
+
+        kw.setdefault("head_indices", self.head_indices)
+        return head_tensors(self.source_frame if self.source_frame is not None else self.original_image, self.heads, size, **kw)
 
     def save_meshes(self, save_folder: str):
         """One Wavefront OBJ per head, 'v x y z' / 'f a b c' with 1-based faces (detection_result.py:22-35,73-78)."""
