@@ -1,5 +1,5 @@
 """In-tree build of libvgh.so, its companions libvghview.so, libvghvis.so, libvghtex.so, libvgheval.so, libvghmerge.so and libvghtrack.so, the application
-library libvghanon.so, the video library libvghvideo.so and the downstream library libvghcrop.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
+library libvghanon.so, the video library libvghvideo.so, the downstream library libvghcrop.so and the overlay library libvghosd.so (hipcc, gfx950 only). `python -m head_detector_amd.build`."""
 from __future__ import annotations
 
 import os
@@ -55,6 +55,11 @@ DOWNSTREAM = [
     # head tensors (fixed-size normalised crops of every head): integer arithmetic, then float32 in a stated operation order, equal bit for bit to its NumPy restatement
     Companion("libvghcrop.so", ["head_tensors.hip"], HOST_HEADERS + ["head_crop_rules.h"], "vgh_crop.h", ["-ffp-contract=off"], "build_crop"),
 ]
+# Libraries that show the result in the frame that goes on to an encoder: built like a companion, before the core
+OVERLAY = [
+    # on-screen display (bars, boxes, bitmap text in a frame's own YUV planes or an RGB image's bytes): integer arithmetic only, equal bit for bit to its NumPy restatement
+    Companion("libvghosd.so", ["osd.hip"], HOST_HEADERS + ["osd_rules.h"], "vgh_osd.h", [], "build_osd"),
+]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]
 
 
@@ -70,7 +75,7 @@ def _stale(lib: str, deps) -> bool:
 
 
 def _core_needs_build() -> bool:  # everything in csrc/ that no companion claims
-    claimed = {f for c in COMPANIONS + APPLICATIONS + VIDEO + DOWNSTREAM for f in c.sources + c.headers}
+    claimed = {f for c in COMPANIONS + APPLICATIONS + VIDEO + DOWNSTREAM + OVERLAY for f in c.sources + c.headers}
     return _stale(LIB, [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f not in claimed] + [os.path.join(HERE, "..", "include", "vgh.h")])
 
 
@@ -79,7 +84,7 @@ def _needs_build(c: Companion) -> bool:
 
 
 def needs_build() -> bool:
-    return _core_needs_build() or any(_needs_build(c) for c in COMPANIONS + APPLICATIONS + VIDEO + DOWNSTREAM)
+    return _core_needs_build() or any(_needs_build(c) for c in COMPANIONS + APPLICATIONS + VIDEO + DOWNSTREAM + OVERLAY)
 
 
 LIB_EXP = os.path.join(HERE, "libvgh_exp.so")  # -DVGH_EXPERIMENTS build (work-skipping switches, env-var knobs): tools/ only
@@ -90,7 +95,7 @@ def build_lib(force: bool = False, verbose: bool = True, experiments: bool = Fal
         return _build(os.path.join(HERE, "libvgh_var.so"), [f"-D{d}" for d in variant_defines], "build_var", verbose)
     if experiments:
         return _build(LIB_EXP, ["-DVGH_EXPERIMENTS"], "build_exp", verbose)
-    for c in COMPANIONS + APPLICATIONS + VIDEO + DOWNSTREAM:
+    for c in COMPANIONS + APPLICATIONS + VIDEO + DOWNSTREAM + OVERLAY:
         if force or _needs_build(c):
             _build(os.path.join(HERE, c.lib), ["-fvisibility=hidden", *c.flags], c.objdir, verbose, c.sources)
     if force or _core_needs_build():

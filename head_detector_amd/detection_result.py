@@ -17,7 +17,9 @@ csrc/mesh_metrics.hip, libvgheval.so, ``head_detector_amd.mesh_metrics``).  ``de
 (``head_detector_amd.detection_metrics``: COCO-style AP, csrc/detection_ap.hip).  ``anonymize`` returns the image with every head pixelated, blurred or filled, by
 box, ellipse or mesh silhouette (csrc/anonymize.hip, libvghanon.so, ``head_detector_amd.anonymize``): integer arithmetic only, a later head owns an overlap.
 ``get_head_tensors`` hands the heads to a next model: fixed-size, normalised crops of every head in one dense GPU tensor, cut from the image or from the video
-frame's own planes in one launch (csrc/head_tensors.hip, libvghcrop.so, ``head_detector_amd.head_tensors``)."""
+frame's own planes in one launch (csrc/head_tensors.hip, libvghcrop.so, ``head_detector_amd.head_tensors``).  ``draw_overlay`` shows the result where it goes on:
+boxes, label bars and bitmap text (track ids, scores) written into the video frame's own YUV planes or into the RGB image, in place if wanted (csrc/osd.hip,
+libvghosd.so, ``head_detector_amd.overlay``)."""
 from __future__ import annotations
 
 import os
@@ -162,6 +164,29 @@ class PredictionResult:
 
         kw.setdefault("head_indices", self.head_indices)
         return head_tensors(self.source_frame if self.source_frame is not None else self.original_image, self.heads, size, **kw)
+
+    def draw_overlay(self, *, out=None, to_host: bool = False, **plan_kw):
+        """``overlay.draw_heads(target, self.heads, out=out, **plan_kw)``: every head's box and, with ``labels="id"``, ``"score"``, ``"id+score"`` or one string
+        per head, its label bar and text, written with integer arithmetic into the surface itself (csrc/osd.hip, libvghosd.so; ``head_detector_amd.overlay``
+        states the rule and the keywords of ``head_overlay_plan``).  The target is the ``source_frame`` if the result was made from a video frame -- its YUV
+        planes are drawn in where they lie, ``original_image`` may be None (``rgb="none"``), ``out=self.source_frame`` is in place and a ``video.YUV420Frame``
+        is returned (with ``to_host=True`` its (y, u, v) planes as NumPy arrays) -- otherwise the ``original_image`` (a GPU ``torch.uint8`` tensor is returned, a
+        NumPy array with ``to_host=True``).  A
+        ``TrackedPredictionResult`` passes its ``track_ids`` and ``coasting`` by itself.  ``draw()`` remains the picture with the reference's look."""
+        from .overlay import draw_heads
+
+        if not isinstance(to_host, (bool, np.bool_)):
+            raise ValueError(f"draw_overlay: to_host must be True or False, got {to_host!r}")
+        for name in ("track_ids", "coasting"):
+            if getattr(self, name, None) is not None:
+                plan_kw.setdefault(name, getattr(self, name))
+        target = self.source_frame if self.source_frame is not None else self.original_image
+        if target is None:
+            raise ValueError("draw_overlay: the result has neither a source_frame nor an original_image to draw into")
+        drawn = draw_heads(target, self.heads, out=out, **plan_kw)
+        if to_host:
+            return tuple(p.cpu().numpy() for p in drawn.planes) if self.source_frame is not None else drawn.cpu().numpy()
+        return drawn
 
     def save_meshes(self, save_folder: str):
         """One Wavefront OBJ per head, 'v x y z' / 'f a b c' with 1-based faces (detection_result.py:22-35,73-78)."""
