@@ -28,6 +28,9 @@ class Companion(NamedTuple):
 HOST_HEADERS = ["companion_host.h"]  # the host plumbing of every companion (codes, message, check macros, staging, queue-then-record): header-only
 RASTER_HEADERS = HOST_HEADERS + ["tile_fold.h"]  # the tile-major triangle fold: header-only, compiled into each of the three libraries that rasterise
 ANON_HEADERS = HOST_HEADERS + ["head_rows.h"]  # the head rows of the two anonymisers (RGB images, YUV planes): header-only, compiled into each of the two
+# a frame's byte planes addressed in place (checks, overlap rule, pair access, copy): header-only, compiled into libvghvideo.so and libvghosd.so, the two
+# libraries that write such planes; the RGB anonymiser works on one packed image and does not take it
+PLANE_HEADERS = ["plane_views.h"]
 COMPANIONS = [  # built in this order, before the core
     # benchmark metrics, mesh (Z_n, chamfer) and detection (COCO-style box AP): float64 in a stated operation order, so no contraction into fused
     # multiply-adds anywhere in this library
@@ -48,7 +51,7 @@ APPLICATIONS = [
 # Libraries on the video side (frames in their own YUV planes): built like a companion, before the core
 VIDEO = [
     # heads anonymised in the planes of a YUV 4:2:0 frame, and RGB packed into such planes: integer arithmetic only, equal bit for bit to its NumPy restatement
-    Companion("libvghvideo.so", ["yuv_anonymize.hip", "yuv_pack.hip"], ANON_HEADERS, "vgh_video.h", [], "build_video"),
+    Companion("libvghvideo.so", ["yuv_anonymize.hip", "yuv_pack.hip"], ANON_HEADERS + PLANE_HEADERS, "vgh_video.h", [], "build_video"),
 ]
 # Libraries that hand the heads to the next network: built like a companion, before the core
 DOWNSTREAM = [
@@ -58,7 +61,7 @@ DOWNSTREAM = [
 # Libraries that show the result in the frame that goes on to an encoder: built like a companion, before the core
 OVERLAY = [
     # on-screen display (bars, boxes, bitmap text in a frame's own YUV planes or an RGB image's bytes): integer arithmetic only, equal bit for bit to its NumPy restatement
-    Companion("libvghosd.so", ["osd.hip"], HOST_HEADERS + ["osd_rules.h"], "vgh_osd.h", [], "build_osd"),
+    Companion("libvghosd.so", ["osd.hip"], HOST_HEADERS + ["osd_rules.h"] + PLANE_HEADERS, "vgh_osd.h", [], "build_osd"),
 ]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]
 

@@ -8,7 +8,8 @@
 // written by exactly one lane of exactly one item.  A plane that is out of place is copied first.
 // The (item, 16 x 16 tile) pairs are listed on the host and uploaded with the items, the codes and the font in ONE staging block; a workgroup is one tile of
 // one item, so the item's row is wave-uniform and no lane branches on its kind apart from its wave.  Integer arithmetic only.  The font, the coverage, the
-// blend, the grown box, the tile count, the workspace size and every check of a job are csrc/osd_rules.h's and exist nowhere else.
+// blend, the grown box, the tile count, the workspace size and every check of a job are csrc/osd_rules.h's and exist nowhere else; a plane's checks, the pair
+// test, the pair access and the strided copy kernel are csrc/plane_views.h's, shared with libvghvideo.so (header-only: nothing is linked).
 // Self-contained on purpose: no csrc/vgh_internal.h, no object of libvgh.so or of another companion, no other public header (csrc/companion_host.h is the host
 // plumbing the companion libraries' sources share); built with -fvisibility=hidden, only the vgho_* functions are exported.
 #include <string.h>
@@ -19,6 +20,7 @@
 #include "../../include/vgh_osd.h"
 #include "companion_host.h"
 #include "osd_rules.h"
+#include "plane_views.h"
 
 namespace {
 
@@ -33,16 +35,12 @@ struct Tile {
     uint32_t xy;  // tile column | tile row << 16, counted from the grown box's corner
 };
 
-// One plane as the write pass sees it, and the planes of one shift: they share their geometry.
-struct Chan {
-    const uint8_t* src;
-    uint8_t* dst;
-    int64_t spitch, dpitch;
-    int32_t sstep, dstep;
+// One plane as the write pass sees it (csrc/plane_views.h), and the planes of one shift: they share their geometry.
+struct Member : planes::Chan {
     int32_t plane;  // its index in the job: which colour byte of an item it takes
 };
 struct Group {
-    Chan c[VGHO_MAX_PLANES];
+    Member c[VGHO_MAX_PLANES];
     int32_t n;
     int32_t spair, dpair;  // n = 2: 0 = two planes; 1 / 2 = c[0] / c[1] is the even, lower byte of interleaved pairs that one 16-bit access reaches
 };
@@ -87,22 +85,10 @@ __global__ __launch_bounds__(256) void paint_kernel(const vgho_item* __restrict_
 // ---- write: one lane per sample of the planes of shift S ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ void blend_sample(const Group& G, const vgho_item& it, int x, int y) {
     uint32_t v[VGHO_MAX_PLANES];
-    if (G.n == 2 && G.spair) {  // one 16-bit access for the pair: the lower pointer and the pitch are even
-        const Chan& lo = G.c[G.spair - 1];
-        const uint32_t p = *reinterpret_cast<const uint16_t*>(lo.src + (int64_t)y * lo.spitch + 2 * (int64_t)x);
-        v[G.spair - 1] = p & 255u;
-        v[2 - G.spair] = p >> 8;
-    } else {
-        for (int c = 0; c < G.n; ++c) v[c] = G.c[c].src[(int64_t)y * G.c[c].spitch + (int64_t)x * G.c[c].sstep];
-    }
+    planes::load(G.c, G.n, x, y, G.spair, v);  // (a pair is set for n = 2 alone)
     const uint32_t colour = (uint32_t)it.color[0] | (uint32_t)it.color[1] << 8 | (uint32_t)it.color[2] << 16;
     for (int c = 0; c < G.n; ++c) v[c] = blend(v[c], (colour >> (8 * G.c[c].plane)) & 255u, (uint32_t)it.alpha);
-    if (G.n == 2 && G.dpair) {
-        const Chan& lo = G.c[G.dpair - 1];
-        *reinterpret_cast<uint16_t*>(lo.dst + (int64_t)y * lo.dpitch + 2 * (int64_t)x) = (uint16_t)(v[G.dpair - 1] | v[2 - G.dpair] << 8);
-    } else {
-        for (int c = 0; c < G.n; ++c) G.c[c].dst[(int64_t)y * G.c[c].dpitch + (int64_t)x * G.c[c].dstep] = (uint8_t)v[c];
-    }
+    planes::store(G.c, G.n, x, y, G.dpair, v);
 }
 
 // S = 0: 256 lanes, the tile's 16 x 16 positions.  S = 1: 64 lanes, its 8 x 8 samples (the tile's corner is even); a sample's keys are the positions
@@ -123,23 +109,6 @@ __global__ __launch_bounds__(256) void write_kernel(const vgho_item* __restrict_
             if (lx < W && ly < H) k = max(k, key[(size_t)ly * W + lx]);
         }
     if (k == (uint32_t)w.i + 1u) blend_sample(G, it, x, y);
-}
-
-// ---- copy: a plane that is out of place and not dense on both sides ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void copy_kernel(const uint8_t* __restrict__ src, int64_t spitch, int sstep, uint8_t* __restrict__ dst, int64_t dpitch, int dstep, int W) {
-    const int x0 = (int)(blockIdx.x * 256u + threadIdx.x) * 4, y = (int)blockIdx.y;
-    const uint8_t* s = src + (int64_t)y * spitch + (int64_t)x0 * sstep;
-    uint8_t* d = dst + (int64_t)y * dpitch + (int64_t)x0 * dstep;
-    for (int b = 0; b < 4 && x0 + b < W; ++b) d[(int64_t)b * dstep] = s[(int64_t)b * sstep];
-}
-
-// 1 / 2: planes a / b are the even, lower byte of interleaved pairs that one 16-bit access reaches; 0: handled as two planes
-int pair_of(const void* a, const void* b, int64_t apitch, int64_t bpitch, int astep, int bstep) {
-    if (astep != 2 || bstep != 2 || apitch != bpitch || (apitch & 1)) return 0;
-    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
-    if (q == p + 1 && !(p & 1)) return 1;
-    if (p == q + 1 && !(q & 1)) return 2;
-    return 0;
 }
 
 // The planes idx[0 .. n) (one shift, all out of place) as ONE dense copy: n >= 2 planes, n bytes between samples on both sides, their pointers the n
@@ -227,12 +196,12 @@ extern "C" VGHO_API int vgho_draw(const vgho_job* job, void* workspace_dev, void
         const vgho_plane& q = j.planes[k];
         Group& G = groups[q.shift];
         members[q.shift][G.n] = k;
-        G.c[G.n++] = Chan{q.src_dev, q.dst_dev, q.src_pitch, q.dst_pitch, q.src_step, q.dst_step, k};
+        G.c[G.n++] = Member{planes::chan_of(q), k};
     }
     for (Group& G : groups)
         if (G.n == 2) {
-            G.spair = pair_of(G.c[0].src, G.c[1].src, G.c[0].spitch, G.c[1].spitch, G.c[0].sstep, G.c[1].sstep);
-            G.dpair = pair_of(G.c[0].dst, G.c[1].dst, G.c[0].dpitch, G.c[1].dpitch, G.c[0].dstep, G.c[1].dstep);
+            G.spair = planes::pair_of(G.c[0].src, G.c[1].src, G.c[0].spitch, G.c[1].spitch, G.c[0].sstep, G.c[1].sstep);
+            G.dpair = planes::pair_of(G.c[0].dst, G.c[1].dst, G.c[0].dpitch, G.c[1].dpitch, G.c[0].dstep, G.c[1].dstep);
         }
     // from here on work is queued (companion_host.h, queue-then-record)
     Queue q;
@@ -254,7 +223,7 @@ extern "C" VGHO_API int vgho_draw(const vgho_job* job, void* workspace_dev, void
             if (p.src_step == 1 && p.dst_step == 1)
                 CH_QUEUE(q, hipMemcpy2DAsync(p.dst_dev, (size_t)p.dst_pitch, p.src_dev, (size_t)p.src_pitch, (size_t)pw, (size_t)ph, hipMemcpyDeviceToDevice, st));
             else if (q.ok())
-                hipLaunchKernelGGL(copy_kernel, dim3((unsigned)((pw + 1023) / 1024), (unsigned)ph), dim3(256), 0, st, p.src_dev, p.src_pitch, p.src_step, p.dst_dev, p.dst_pitch, p.dst_step, (int)pw);
+                hipLaunchKernelGGL(planes::copy_kernel,dim3((unsigned)((pw + 1023) / 1024), (unsigned)ph), dim3(256), 0, st, p.src_dev, p.src_pitch, p.src_step, p.dst_dev, p.dst_pitch, p.dst_step, (int)pw);
         }
     }
     if (n_tiles && q.ok()) {

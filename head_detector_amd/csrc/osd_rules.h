@@ -1,5 +1,6 @@
 // What the host half and the kernels of csrc/osd.hip (libvghosd.so, include/vgh_osd.h) must not hold twice: the font table, the coverage of an item, the
-// blend, the box-growing rules, the tile count, the workspace size and the validation of a job.
+// blend, the box-growing rules, the tile count, the workspace size and the validation of a job (the checks of a plane and the overlap rule inside it are
+// csrc/plane_views.h's host part, shared with libvghvideo.so).
 // HIP-free: plain C++ that tests/osd_host.hip compiles for the host alone under the sanitizers; under hipcc the functions are host and device functions.
 #pragma once
 #include <stddef.h>
@@ -7,6 +8,7 @@
 #include <stdio.h>
 
 #include "../../include/vgh_osd.h"
+#include "plane_views.h"
 
 #if defined(__HIPCC__)
 #define OSD_HD __host__ __device__ inline
@@ -131,21 +133,10 @@ inline int64_t tile_count(const vgho_item* items, int32_t n, int32_t W, int32_t 
 inline int64_t workspace_bytes(int32_t W, int32_t H) { return ((int64_t)4 * W * H + 15) & ~(int64_t)15; }
 
 // ---- validation ----------------------------------------------------------------------------------------------------------------------------------------------
-#define OSD_REFUSE(cond, ...)                      \
-    do {                                           \
-        if (!(cond)) {                             \
-            snprintf(msg, msg_bytes, __VA_ARGS__); \
-            return msg;                            \
-        }                                          \
-    } while (0)
+#define OSD_REFUSE(...) PLANES_REFUSE(__VA_ARGS__)  // the message into msg, and returned
 
-// the byte range [a, b) of a plane of pw x ph samples
-inline void plane_range(const uint8_t* p, int64_t pitch, int32_t step, int64_t pw, int64_t ph, uintptr_t& a, uintptr_t& b) {
-    a = (uintptr_t)p;
-    b = a + (uintptr_t)((ph - 1) * pitch + (pw - 1) * step + 1);
-}
-
-inline bool in_place(const vgho_plane& q) { return q.dst_dev == q.src_dev && q.dst_pitch == q.src_pitch && q.dst_step == q.src_step; }
+using planes::in_place;
+constexpr const char* PLANE_LABELS[VGHO_MAX_PLANES] = {"0", "1", "2"};
 
 // NULL for a job vgho_draw takes, otherwise the message of its first refusal (written to msg).  Reads host memory only; `who` words the message.
 inline const char* validate(const vgho_job* job, const char* who, char* msg, size_t msg_bytes) {
@@ -156,29 +147,15 @@ inline const char* validate(const vgho_job* job, const char* who, char* msg, siz
     OSD_REFUSE(j.n_items >= 0 && j.n_items <= VGHO_MAX_ITEMS, "%s: n_items %d outside 0 .. %d", who, j.n_items, VGHO_MAX_ITEMS);
     OSD_REFUSE(j.n_codes >= 0, "%s: n_codes %d is negative", who, j.n_codes);
     OSD_REFUSE(j.reserved == 0, "%s: reserved is %d, not 0", who, j.reserved);
-    uintptr_t s0[VGHO_MAX_PLANES], s1[VGHO_MAX_PLANES], d0[VGHO_MAX_PLANES], d1[VGHO_MAX_PLANES];
+    int64_t pw[VGHO_MAX_PLANES], ph[VGHO_MAX_PLANES];
     for (int k = 0; k < j.n_planes; ++k) {
         const vgho_plane& q = j.planes[k];
         OSD_REFUSE(q.shift == 0 || q.shift == 1, "%s: plane %d: shift %d is not 0 or 1", who, k, q.shift);
         OSD_REFUSE(q.reserved == 0, "%s: plane %d: reserved is %d, not 0", who, k, q.reserved);
-        OSD_REFUSE(q.src_dev && q.dst_dev, "%s: plane %d: null plane (src_dev %p, dst_dev %p)", who, k, (const void*)q.src_dev, (void*)q.dst_dev);
-        OSD_REFUSE(q.src_step >= 1 && q.src_step <= 3 && q.dst_step >= 1 && q.dst_step <= 3, "%s: plane %d: steps %d and %d are not 1, 2 or 3", who, k, q.src_step, q.dst_step);
-        const int64_t pw = plane_side(j.width, q.shift), ph = plane_side(j.height, q.shift);
-        OSD_REFUSE(q.src_pitch >= (pw - 1) * q.src_step + 1 && q.src_pitch <= ((int64_t)1 << 40), "%s: plane %d: src_pitch %lld outside %lld .. 2^40", who, k, (long long)q.src_pitch,
-                   (long long)((pw - 1) * q.src_step + 1));
-        OSD_REFUSE(q.dst_pitch >= (pw - 1) * q.dst_step + 1 && q.dst_pitch <= ((int64_t)1 << 40), "%s: plane %d: dst_pitch %lld outside %lld .. 2^40", who, k, (long long)q.dst_pitch,
-                   (long long)((pw - 1) * q.dst_step + 1));
-        plane_range(q.src_dev, q.src_pitch, q.src_step, pw, ph, s0[k], s1[k]);
-        plane_range(q.dst_dev, q.dst_pitch, q.dst_step, pw, ph, d0[k], d1[k]);
+        pw[k] = plane_side(j.width, q.shift), ph[k] = plane_side(j.height, q.shift);
+        if (const char* m = planes::check_plane(q, pw[k], 3, who, PLANE_LABELS[k], msg, msg_bytes)) return m;
     }
-    for (int k = 0; k < j.n_planes; ++k) {  // a destination plane is exactly its source plane, or overlaps no source plane
-        const vgho_plane& q = j.planes[k];
-        if (in_place(q)) continue;
-        OSD_REFUSE(q.dst_dev != q.src_dev, "%s: plane %d: the destination starts where the source does with another pitch or step (%lld and %d, not %lld and %d): in place means exactly the source plane",
-                   who, k, (long long)q.dst_pitch, q.dst_step, (long long)q.src_pitch, q.src_step);
-        for (int m = 0; m < j.n_planes; ++m)
-            OSD_REFUSE(d1[k] <= s0[m] || s1[m] <= d0[k], "%s: plane %d: the destination overlaps source plane %d without being exactly its own source plane", who, k, m);
-    }
+    if (const char* m = planes::check_overlap(j.planes, j.n_planes, pw, ph, who, PLANE_LABELS, msg, msg_bytes)) return m;
     if (j.n_items == 0) return nullptr;
     OSD_REFUSE(j.items, "%s: null items", who);
     for (int32_t i = 0; i < j.n_items; ++i) {

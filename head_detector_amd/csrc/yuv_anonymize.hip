@@ -12,10 +12,11 @@
 //   blur       blur_rows_kernel  one workgroup per 256-sample row segment: the source row and its 2 r halo in LDS, h = the u16 horizontal pass
 //              blur_cols_kernel  one lane per sample of the clipped box, a wave along a row: the vertical pass over h, for the samples the head owns
 // WRITE: write_kernel, one lane per sample of every head's clipped box, stores the value (fill: the colour) where the head owns the sample: the only pass
-// that writes a frame in place.  A plane that is out of place is copied first (copy_kernel, the one pass that walks a whole plane).
+// that writes a frame in place.  A plane that is out of place is copied first (planes::copy_kernel, the one pass that walks a whole plane).
 // Heads x tiles, x cells and x row segments are enumerated through prefix sums made on the host; a workgroup finds its head by bisection.  Integer arithmetic
 // only.  The head rows, their per-head checks and offsets, the bisection, the owner painter and the staged upload are csrc/head_rows.h, shared with
-// csrc/anonymize.hip; the checks of the frame, the workspace layout and every kernel that touches a sample are here.
+// csrc/anonymize.hip; a plane's checks, the overlap rule, the pair test, the pair access and the copy are csrc/plane_views.h, shared with csrc/osd.hip; the
+// other checks of the job, the workspace layout and every other kernel that touches a sample are here.
 #include <string.h>
 
 #include <map>
@@ -24,6 +25,7 @@
 #include "../../include/vgh_video.h"
 #include "companion_host.h"
 #include "head_rows.h"
+#include "plane_views.h"
 
 namespace {
 
@@ -35,49 +37,13 @@ static_assert(VGHY_MAX_SIDE == MAX_SIDE && VGHY_MAX_COORD == MAX_COORD && VGHY_M
 
 constexpr int LINE_SAMPLES = SEGMENT + 2 * VGHY_MAX_RADIUS;  // the segment and the widest halo in LDS (luma: 256 + 2 * 1024 bytes), so r is never chunked
 
-// One channel of a plane group as the kernels read it, and the group: NC channels of one width and height.
-struct Chan {
-    const uint8_t* src;
-    uint8_t* dst;
-    int64_t spitch, dpitch;
-    int32_t sstep, dstep;
-};
+// A plane group: NC channels (csrc/plane_views.h) of one width and height.
 template <int NC>
 struct View {
-    Chan c[NC];
+    planes::Chan c[NC];
     int32_t W, H;          // of the plane
     int32_t spair, dpair;  // NC = 2: 0 = two planes; 1 / 2 = c[0] / c[1] is the even, lower byte of interleaved pairs
 };
-
-template <int NC>
-__device__ __forceinline__ void load(const View<NC>& P, int x, int y, uint32_t (&v)[NC]) {
-    if constexpr (NC == 2) {
-        if (P.spair) {  // one 16-bit access for the (U, V) pair: the lower pointer and the pitch are even
-            const Chan& lo = P.c[P.spair - 1];
-            const uint32_t w = *reinterpret_cast<const uint16_t*>(lo.src + (int64_t)y * lo.spitch + 2 * (int64_t)x);
-            const uint32_t a = w & 255u, b = w >> 8;
-            v[0] = P.spair == 1 ? a : b;
-            v[1] = P.spair == 1 ? b : a;
-            return;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) v[c] = P.c[c].src[(int64_t)y * P.c[c].spitch + (int64_t)x * P.c[c].sstep];
-}
-
-template <int NC>
-__device__ __forceinline__ void store(const View<NC>& P, int x, int y, const uint32_t (&v)[NC]) {
-    if constexpr (NC == 2) {
-        if (P.dpair) {
-            const Chan& lo = P.c[P.dpair - 1];
-            const uint32_t a = P.dpair == 1 ? v[0] : v[1], b = P.dpair == 1 ? v[1] : v[0];
-            *reinterpret_cast<uint16_t*>(lo.dst + (int64_t)y * lo.dpitch + 2 * (int64_t)x) = (uint16_t)(a | b << 8);
-            return;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) P.c[c].dst[(int64_t)y * P.c[c].dpitch + (int64_t)x * P.c[c].dstep] = (uint8_t)v[c];
-}
 
 // Does head i own sample (x, y) of this plane group?  Luma: the owner plane itself.  Chroma: the maximum of the owners, -1 for every value outside [0, n), of
 // the luma pixels {2 y, 2 y + 1} x {2 x, 2 x + 1} that lie in the frame (LW x LH).
@@ -116,7 +82,7 @@ __global__ __launch_bounds__(256) void cells_kernel(const HeadRow* __restrict__ 
     for (int y = ay + (int)(threadIdx.x >> 6); y < by; y += 4)
         for (int x = ax + (int)(threadIdx.x & 63); x < bx; x += 64) {
             uint32_t v[NC];
-            load<NC>(P, x, y, v);
+            planes::load(P.c, NC, x, y, P.spair, v);
 #pragma unroll
             for (int c = 0; c < NC; ++c) a[c] += v[c];
         }
@@ -163,7 +129,7 @@ __global__ __launch_bounds__(256) void blur_rows_kernel(const HeadRow* __restric
     } else {
         for (int j = threadIdx.x; j < samples + 2 * rad; j += 256) {
             uint32_t v[NC];
-            load<NC>(P, min(max(sx - rad + j, 0), P.W - 1), y, v);
+            planes::load(P.c, NC, min(max(sx - rad + j, 0), P.W - 1), y, P.spair, v);
 #pragma unroll
             for (int c = 0; c < NC; ++c) line[j * NC + c] = (uint8_t)v[c];
         }
@@ -232,21 +198,7 @@ __global__ __launch_bounds__(256) void write_kernel(const HeadRow* __restrict__ 
 #pragma unroll
         for (int c = 0; c < NC; ++c) v[c] = p[c];
     }
-    store<NC>(P, x, y, v);
-}
-
-// ---- copy -----------------------------------------------------------------------------------------------------------------------------------
-// A plane that is out of place: every sample copied, four of a row per lane; one aligned dword where both sides are dense, aligned and whole.
-__global__ __launch_bounds__(256) void copy_kernel(const uint8_t* __restrict__ src, int64_t spitch, int sstep, uint8_t* __restrict__ dst, int64_t dpitch, int dstep, int W) {
-    const int x0 = (int)(blockIdx.x * 256u + threadIdx.x) * 4, y = (int)blockIdx.y;
-    if (x0 >= W) return;
-    const uint8_t* s = src + (int64_t)y * spitch + (int64_t)x0 * sstep;
-    uint8_t* d = dst + (int64_t)y * dpitch + (int64_t)x0 * dstep;
-    if (sstep == 1 && dstep == 1 && x0 + 4 <= W && (((uintptr_t)s | (uintptr_t)d) & 3) == 0) {
-        *reinterpret_cast<uint32_t*>(d) = *reinterpret_cast<const uint32_t*>(s);
-        return;
-    }
-    for (int b = 0; b < 4 && x0 + b < W; ++b) d[(int64_t)b * dstep] = s[(int64_t)b * sstep];
+    planes::store(P.c, NC, x, y, P.dpair, v);
 }
 
 // ---- the host half: every check and every offset, no HIP call -----------------------------------------------------------------------------------
@@ -259,49 +211,17 @@ struct Plan {
 
 const char* const PLANE_NAMES[3] = {"Y", "U", "V"};
 
-// the byte range of a plane of pw x ph samples
-void plane_range(const uint8_t* p, int64_t pitch, int step, int64_t pw, int64_t ph, uintptr_t& a, uintptr_t& b) {
-    a = (uintptr_t)p;
-    b = a + (uintptr_t)((ph - 1) * pitch + (pw - 1) * step + 1);
-}
-
-// 1 / 2: planes 1 / 2 are the even, lower byte of interleaved pairs that one 16-bit access reaches; 0: handled as two planes
-int pair_of(const void* u, const void* v, int64_t upitch, int64_t vpitch, int ustep, int vstep) {
-    if (ustep != 2 || vstep != 2 || upitch != vpitch || (upitch & 1)) return 0;
-    const uintptr_t a = (uintptr_t)u, b = (uintptr_t)v;
-    if (b == a + 1 && !(a & 1)) return 1;
-    if (a == b + 1 && !(b & 1)) return 2;
-    return 0;
-}
-
 // `who` words the messages: the two entry points share every check of the job
 int make_plan(const vghy_anonymize_job* job, Plan& p, const char* who) {
     CH_REQUIRE(job, "%s: null job", who);
     const vghy_anonymize_job& j = *job;
     CH_REQUIRE(j.height >= 1 && j.width >= 1 && j.height <= VGHY_MAX_SIDE && j.width <= VGHY_MAX_SIDE, "%s: frame %d x %d outside 1 .. %d", who, j.height, j.width, VGHY_MAX_SIDE);
     const int64_t H = j.height, W = j.width, CH = (H + 1) / 2, CW = (W + 1) / 2;
-    uintptr_t s0[3], s1[3], d0[3], d1[3];
-    for (int k = 0; k < 3; ++k) {
-        const vghy_plane& q = j.planes[k];
-        const int64_t pw = k ? CW : W, ph = k ? CH : H;
-        CH_REQUIRE(q.src_dev && q.dst_dev, "%s: plane %s: null plane (src_dev %p, dst_dev %p)", who, PLANE_NAMES[k], (const void*)q.src_dev, (void*)q.dst_dev);
-        CH_REQUIRE((q.src_step == 1 || q.src_step == 2) && (q.dst_step == 1 || q.dst_step == 2), "%s: plane %s: steps %d and %d are not 1 or 2", who, PLANE_NAMES[k], q.src_step, q.dst_step);
-        CH_REQUIRE(q.src_pitch >= (pw - 1) * q.src_step + 1 && q.src_pitch <= ((int64_t)1 << 40), "%s: plane %s: src_pitch %lld outside %lld .. 2^40", who, PLANE_NAMES[k],
-                   (long long)q.src_pitch, (long long)((pw - 1) * q.src_step + 1));
-        CH_REQUIRE(q.dst_pitch >= (pw - 1) * q.dst_step + 1 && q.dst_pitch <= ((int64_t)1 << 40), "%s: plane %s: dst_pitch %lld outside %lld .. 2^40", who, PLANE_NAMES[k],
-                   (long long)q.dst_pitch, (long long)((pw - 1) * q.dst_step + 1));
-        plane_range(q.src_dev, q.src_pitch, q.src_step, pw, ph, s0[k], s1[k]);
-        plane_range(q.dst_dev, q.dst_pitch, q.dst_step, pw, ph, d0[k], d1[k]);
-    }
-    for (int k = 0; k < 3; ++k) {  // a destination plane is exactly its source plane, or overlaps no source plane
-        const vghy_plane& q = j.planes[k];
-        p.in_place[k] = q.dst_dev == q.src_dev && q.dst_pitch == q.src_pitch && q.dst_step == q.src_step;
-        if (p.in_place[k]) continue;
-        CH_REQUIRE(q.dst_dev != q.src_dev, "%s: plane %s: the destination starts where the source does with another pitch or step (%lld and %d, not %lld and %d): in place means exactly the source plane",
-                   who, PLANE_NAMES[k], (long long)q.dst_pitch, q.dst_step, (long long)q.src_pitch, q.src_step);
-        for (int m = 0; m < 3; ++m)
-            CH_REQUIRE(d1[k] <= s0[m] || s1[m] <= d0[k], "%s: plane %s: the destination overlaps source plane %s without being exactly its own source plane", who, PLANE_NAMES[k], PLANE_NAMES[m]);
-    }
+    const int64_t pw[3] = {W, CW, CW}, ph[3] = {H, CH, CH};
+    char why[400];
+    for (int k = 0; k < 3; ++k) CH_REQUIRE(!planes::check_plane(j.planes[k], pw[k], 2, who, PLANE_NAMES[k], why, sizeof(why)), "%s", why);
+    CH_REQUIRE(!planes::check_overlap(j.planes, 3, pw, ph, who, PLANE_NAMES, why, sizeof(why)), "%s", why);
+    for (int k = 0; k < 3; ++k) p.in_place[k] = planes::in_place(j.planes[k]);
     CH_REQUIRE(j.n_heads >= 0 && j.n_heads <= VGHY_MAX_HEADS, "%s: n_heads %d outside 0 .. %d", who, j.n_heads, VGHY_MAX_HEADS);
     CH_REQUIRE(j.method >= VGHY_METHOD_FILL && j.method <= VGHY_METHOD_BLUR, "%s: unknown method %d", who, j.method);
     CH_REQUIRE(j.region >= VGHY_REGION_BOX && j.region <= VGHY_REGION_MAP, "%s: unknown region %d", who, j.region);
@@ -316,8 +236,8 @@ int make_plan(const vghy_anonymize_job* job, Plan& p, const char* who) {
     if (blur && n) CH_REQUIRE(j.taps && j.n_taps >= 1, "%s: blur needs a tap table (taps %p, n_taps %d)", who, (const void*)j.taps, j.n_taps);
     if (int rc = plan_heads(j.luma_heads, n, j.method, j.taps, j.n_taps, W, H, p.luma, who, "luma head")) return rc;
     if (int rc = plan_heads(j.chroma_heads, n, j.method, j.taps, j.n_taps, CW, CH, p.chroma, who, "chroma head")) return rc;
-    p.spair = pair_of(j.planes[1].src_dev, j.planes[2].src_dev, j.planes[1].src_pitch, j.planes[2].src_pitch, j.planes[1].src_step, j.planes[2].src_step);
-    p.dpair = pair_of(j.planes[1].dst_dev, j.planes[2].dst_dev, j.planes[1].dst_pitch, j.planes[2].dst_pitch, j.planes[1].dst_step, j.planes[2].dst_step);
+    p.spair = planes::pair_of(j.planes[1].src_dev, j.planes[2].src_dev, j.planes[1].src_pitch, j.planes[2].src_pitch, j.planes[1].src_step, j.planes[2].src_step);
+    p.dpair = planes::pair_of(j.planes[1].dst_dev, j.planes[2].dst_dev, j.planes[1].dst_pitch, j.planes[2].dst_pitch, j.planes[1].dst_step, j.planes[2].dst_step);
     p.values_l = up16(j.region == VGHY_REGION_MAP ? 0 : 4 * H * W);
     p.values_c = up16(p.values_l + p.luma.n_values);
     p.h_l = up16(p.values_c + 2 * p.chroma.n_values);
@@ -329,8 +249,6 @@ int make_plan(const vghy_anonymize_job* job, Plan& p, const char* who) {
 
 std::mutex g_mutex;
 std::map<int, Staging> g_staging;  // per device: the head rows, the prefix sums and the taps of one call
-
-Chan chan_of(const vghy_plane& q) { return Chan{q.src_dev, q.dst_dev, q.src_pitch, q.dst_pitch, q.src_step, q.dst_step}; }
 
 }  // namespace
 
@@ -367,8 +285,8 @@ extern "C" VGHY_API int vghy_anonymize(const vghy_anonymize_job* job, void* work
     uint8_t* ws = (uint8_t*)workspace_dev;
     int32_t* painted = (int32_t*)ws;
     const int32_t* owner = paint ? painted : j.owner_dev;
-    View<1> luma{{chan_of(j.planes[0])}, W, H, 0, 0};
-    View<2> chroma{{chan_of(j.planes[1]), chan_of(j.planes[2])}, CW, CH, p.spair, p.dpair};
+    View<1> luma{{planes::chan_of(j.planes[0])}, W, H, 0, 0};
+    View<2> chroma{{planes::chan_of(j.planes[1]), planes::chan_of(j.planes[2])}, CW, CH, p.spair, p.dpair};
     uint8_t *values_l = ws + p.values_l, *values_c = ws + p.values_c;
     uint16_t *h_l = (uint16_t*)(ws + p.h_l), *h_c = (uint16_t*)(ws + p.h_c);
     const uint32_t tiles_l = p.luma.tiles[(size_t)n], tiles_c = p.chroma.tiles[(size_t)n];
@@ -393,13 +311,13 @@ extern "C" VGHY_API int vghy_anonymize(const vghy_anonymize_job* job, void* work
         }
     }
     if (q.ok()) {  // the planes that are out of place: every sample copied, an interleaved pair that stays one as one plane of 2 CW bytes
-        if (!p.in_place[0]) hipLaunchKernelGGL(copy_kernel, dim3((W + 1023) / 1024, H), dim3(256), 0, st, luma.c[0].src, luma.c[0].spitch, 1 * luma.c[0].sstep, luma.c[0].dst, luma.c[0].dpitch, 1 * luma.c[0].dstep, W);
+        if (!p.in_place[0]) hipLaunchKernelGGL(planes::copy_kernel, dim3((W + 1023) / 1024, H), dim3(256), 0, st, luma.c[0].src, luma.c[0].spitch, 1 * luma.c[0].sstep, luma.c[0].dst, luma.c[0].dpitch, 1 * luma.c[0].dstep, W);
         if (!p.in_place[1] && !p.in_place[2] && p.spair && p.spair == p.dpair) {
-            const Chan& lo = chroma.c[p.spair - 1];
-            hipLaunchKernelGGL(copy_kernel, dim3((2 * CW + 1023) / 1024, CH), dim3(256), 0, st, lo.src, lo.spitch, 1, lo.dst, lo.dpitch, 1, 2 * CW);
+            const planes::Chan& lo = chroma.c[p.spair - 1];
+            hipLaunchKernelGGL(planes::copy_kernel, dim3((2 * CW + 1023) / 1024, CH), dim3(256), 0, st, lo.src, lo.spitch, 1, lo.dst, lo.dpitch, 1, 2 * CW);
         } else {
             for (int k = 0; k < 2; ++k)
-                if (!p.in_place[1 + k]) hipLaunchKernelGGL(copy_kernel, dim3((CW + 1023) / 1024, CH), dim3(256), 0, st, chroma.c[k].src, chroma.c[k].spitch, chroma.c[k].sstep, chroma.c[k].dst, chroma.c[k].dpitch, chroma.c[k].dstep, CW);
+                if (!p.in_place[1 + k]) hipLaunchKernelGGL(planes::copy_kernel, dim3((CW + 1023) / 1024, CH), dim3(256), 0, st, chroma.c[k].src, chroma.c[k].spitch, chroma.c[k].sstep, chroma.c[k].dst, chroma.c[k].dpitch, chroma.c[k].dstep, CW);
         }
     }
     if (q.ok()) {

@@ -4,6 +4,7 @@
 // the interleaved pair of one plane.  Nothing is staged or allocated.
 #include "../../include/vgh_video.h"
 #include "companion_host.h"
+#include "plane_views.h"
 
 namespace {
 
@@ -12,10 +13,8 @@ using namespace companion;
 struct PackArgs {
     const uint8_t* src;
     int64_t src_pitch;
-    uint8_t* dst[3];
-    int64_t pitch[3];
-    int32_t step[3];
-    int32_t pair;  // 0 = U and V are stored apart; 1 / 2 = U / V is the even, lower byte of interleaved pairs
+    planes::Chan y, c[2];  // the destination planes Y and (U, V); their source side is unused
+    int32_t pair;          // 0 = U and V are stored apart; 1 / 2 = U / V is the even, lower byte of interleaved pairs
     int32_t W, H, CW, CH;
     int32_t coef[9];
     int32_t y_offset;
@@ -36,19 +35,14 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a) {
             const uint8_t* p = a.src + (int64_t)y * a.src_pitch + (int64_t)x * 3;
             const int32_t r = p[0], g = p[1], b = p[2];
             sum[0] += r, sum[1] += g, sum[2] += b, ++m;
-            a.dst[0][(int64_t)y * a.pitch[0] + (int64_t)x * a.step[0]] = (uint8_t)clamp8(a.y_offset + ((a.coef[0] * r + a.coef[1] * g + a.coef[2] * b + 32768) >> 16));
+            a.y.dst[(int64_t)y * a.y.dpitch + (int64_t)x * a.y.dstep] = (uint8_t)clamp8(a.y_offset + ((a.coef[0] * r + a.coef[1] * g + a.coef[2] * b + 32768) >> 16));
         }
     }
     const int32_t rm = (2 * sum[0] + m) / (2 * m), gm = (2 * sum[1] + m) / (2 * m), bm = (2 * sum[2] + m) / (2 * m);
     const uint32_t u = clamp8(128 + ((a.coef[3] * rm + a.coef[4] * gm + a.coef[5] * bm + 32768) >> 16));
     const uint32_t v = clamp8(128 + ((a.coef[6] * rm + a.coef[7] * gm + a.coef[8] * bm + 32768) >> 16));
-    if (a.pair) {
-        uint8_t* lo = a.dst[a.pair] + (int64_t)cy * a.pitch[a.pair] + 2 * (int64_t)cx;
-        *reinterpret_cast<uint16_t*>(lo) = (uint16_t)(a.pair == 1 ? u | v << 8 : v | u << 8);
-    } else {
-        a.dst[1][(int64_t)cy * a.pitch[1] + (int64_t)cx * a.step[1]] = (uint8_t)u;
-        a.dst[2][(int64_t)cy * a.pitch[2] + (int64_t)cx * a.step[2]] = (uint8_t)v;
-    }
+    const uint32_t uv[2] = {u, v};
+    planes::store(a.c, 2, cx, cy, a.pair, uv);
 }
 
 const char* const PACK_PLANES[3] = {"Y", "U", "V"};
@@ -65,28 +59,24 @@ int pack_plan(const vghy_pack_job* job, PackArgs& a) {
     CH_REQUIRE(j.y_offset >= 0 && j.y_offset <= 255, "pack_rgb: y_offset %d outside 0 .. 255", j.y_offset);
     for (int k = 0; k < 9; ++k) CH_REQUIRE(j.coef[k] >= -(1 << 20) && j.coef[k] <= (1 << 20), "pack_rgb: coefficient %d is %d, beyond +-2^20", k, j.coef[k]);
     const uintptr_t s0 = (uintptr_t)j.src_dev, s1 = s0 + (uintptr_t)((H - 1) * j.src_pitch_bytes + W * 3);
+    char why[400];
     for (int k = 0; k < 3; ++k) {
         const vghy_plane& q = j.planes[k];
         const int64_t pw = k ? CW : W, ph = k ? CH : H;
         CH_REQUIRE(q.dst_dev, "pack_rgb: plane %s: null plane", PACK_PLANES[k]);
         CH_REQUIRE(q.src_dev == nullptr && q.src_pitch == 0 && q.src_step == 0, "pack_rgb: plane %s: the src_ fields of a destination plane are not 0", PACK_PLANES[k]);
         CH_REQUIRE(q.dst_step == 1 || q.dst_step == 2, "pack_rgb: plane %s: step %d is not 1 or 2", PACK_PLANES[k], q.dst_step);
-        CH_REQUIRE(q.dst_pitch >= (pw - 1) * q.dst_step + 1 && q.dst_pitch <= ((int64_t)1 << 40), "pack_rgb: plane %s: dst_pitch %lld outside %lld .. 2^40", PACK_PLANES[k],
-                   (long long)q.dst_pitch, (long long)((pw - 1) * q.dst_step + 1));
-        const uintptr_t d0 = (uintptr_t)q.dst_dev, d1 = d0 + (uintptr_t)((ph - 1) * q.dst_pitch + (pw - 1) * q.dst_step + 1);
+        CH_REQUIRE(!planes::check_pitch(q.dst_pitch, q.dst_step, pw, "pack_rgb", PACK_PLANES[k], "dst", why, sizeof(why)), "%s", why);
+        uintptr_t d0, d1;
+        planes::plane_range(q.dst_dev, q.dst_pitch, q.dst_step, pw, ph, d0, d1);
         CH_REQUIRE(d1 <= s0 || s1 <= d0, "pack_rgb: plane %s overlaps the source image (the source is never modified)", PACK_PLANES[k]);
-        a.dst[k] = q.dst_dev, a.pitch[k] = q.dst_pitch, a.step[k] = q.dst_step;
+        (k ? a.c[k - 1] : a.y) = planes::chan_of(q);
     }
     a.src = j.src_dev, a.src_pitch = j.src_pitch_bytes;
     a.W = (int32_t)W, a.H = (int32_t)H, a.CW = (int32_t)CW, a.CH = (int32_t)CH;
     for (int k = 0; k < 9; ++k) a.coef[k] = j.coef[k];
     a.y_offset = j.y_offset;
-    a.pair = 0;
-    if (a.step[1] == 2 && a.step[2] == 2 && a.pitch[1] == a.pitch[2] && !(a.pitch[1] & 1)) {
-        const uintptr_t u = (uintptr_t)a.dst[1], v = (uintptr_t)a.dst[2];
-        if (v == u + 1 && !(u & 1)) a.pair = 1;
-        if (u == v + 1 && !(v & 1)) a.pair = 2;
-    }
+    a.pair = planes::pair_of(a.c[0].dst, a.c[1].dst, a.c[0].dpitch, a.c[1].dpitch, a.c[0].dstep, a.c[1].dstep);
     return OK;
 }
 

@@ -184,28 +184,15 @@ def _need_gpu() -> None:
 
 
 def _render_frame(frame, items: Items, out):
-    from .video import YUV420Frame, _plane_range, rgb_to_yuv
+    from .video import _plane_pairs, rgb_to_yuv
 
     H, W, _ = frame.shape
-    if out is not None and not (isinstance(out, YUV420Frame) and out.shape == frame.shape and out.device == frame.device):
-        raise ValueError(f"render: out must be a YUV420Frame of {H} x {W} on {frame.device}; got {out!r}")
+    out, planes = _plane_pairs("render", frame, out)
     rows = items.rows(lambda c: rgb_to_yuv(c, (out or frame).matrix, (out or frame).full_range))
-    if not frame.y.is_cuda:
+    if planes is None:
         _need_gpu()
         raise VghError("overlays need a frame on a GPU: the HIP kernels of libvghosd.so are the only implementation of the samples")
-    if out is None:
-        out = frame._like()
-    planes = []
-    for k, (name, (s, sp, ss), (d, dp, ds)) in enumerate(zip("yuv", frame._layout(), out._layout())):
-        if not (d.data_ptr() == s.data_ptr() and dp == sp and ds == ss):
-            d0, d1 = _plane_range(d)
-            for other in frame.planes:
-                s0, s1 = _plane_range(other)
-                if s0 < d1 and d0 < s1:
-                    raise ValueError(f"render: plane {name} of out overlaps the source frame without being exactly its plane {name} (same memory, pitch and step): "
-                                     "pass out=frame for in place, or a frame elsewhere")
-        planes.append((s.data_ptr(), d.data_ptr(), sp, dp, ss, ds, 0 if k == 0 else 1))
-    _call(planes, H, W, rows, items.codes(), frame.device)
+    _call([(*row, 0 if k == 0 else 1) for k, row in enumerate(planes)], H, W, rows, items.codes(), frame.device)
     return out
 
 

@@ -352,6 +352,30 @@ def _plane_range(t: torch.Tensor) -> Tuple[int, int]:
     return t.data_ptr(), t.data_ptr() + last + 1
 
 
+def _plane_pairs(who: str, frame: YUV420Frame, out: Optional[YUV420Frame]):
+    """-> (out, rows): the frame a call of ``who`` writes (``out``, checked: a frame of ``frame``'s size on its device; ``None``: a new dense frame like ``frame``) and
+    its planes as include/vgh_video.h and include/vgh_osd.h describe one, (src pointer, dst pointer, src pitch, dst pitch, src step, dst step) each.  A plane of
+    ``out`` is exactly its plane of ``frame`` (in place) or overlaps no plane of ``frame``.  A frame that is not on a GPU: (out as given, None), for the caller's refusal."""
+    H, W, _ = frame.shape
+    if out is not None and not (isinstance(out, YUV420Frame) and out.shape == frame.shape and out.device == frame.device):
+        raise ValueError(f"{who}: out must be a YUV420Frame of {H} x {W} on {frame.device}; got {out!r}")
+    if not frame.y.is_cuda:
+        return out, None
+    if out is None:
+        out = frame._like()
+    rows = []
+    for name, (s, sp, ss), (d, dp, ds) in zip("yuv", frame._layout(), out._layout()):
+        if not (d.data_ptr() == s.data_ptr() and dp == sp and ds == ss):  # not in place
+            d0, d1 = _plane_range(d)
+            for other in frame.planes:
+                s0, s1 = _plane_range(other)
+                if s0 < d1 and d0 < s1:
+                    raise ValueError(f"{who}: plane {name} of out overlaps the source frame without being exactly its plane {name} (same memory, pitch and step): "
+                                     "pass out=frame for in place, or a frame elsewhere")
+        rows.append((s.data_ptr(), d.data_ptr(), sp, dp, ss, ds))
+    return out, rows
+
+
 def anonymize_frame(frame: YUV420Frame, heads, method: str = "pixelate", region: str = "ellipse", *, margin: float = 0.1, cells: int = 8, strength: float = 0.1,
                     color=(0, 0, 0), faces=None, owner=None, out: Optional[YUV420Frame] = None) -> YUV420Frame:
     """``frame`` with every head hidden directly in its luma and chroma planes (csrc/yuv_anonymize.hip, libvghvideo.so; the module text and include/vgh_video.h
@@ -376,23 +400,11 @@ def anonymize_frame(frame: YUV420Frame, heads, method: str = "pixelate", region:
     n = len(heads)
     tables = an.TapTables()  # one tap table for the call: the luma rows' tables first, the chroma rows' behind them
     plan = an._plan_on_host((H, W), heads, method, region, margin, cells, strength, owner, tables)
-    if out is not None and not (isinstance(out, YUV420Frame) and out.shape == frame.shape and out.device == frame.device):
-        raise ValueError(f"anonymize_frame: out must be a YUV420Frame of {H} x {W} on {frame.device}; got {out!r}")
-    if not (torch.cuda.is_available() and frame.y.is_cuda):
+    out, planes = _plane_pairs("anonymize_frame", frame, out)
+    if planes is None:
         raise VghError("anonymised frames need a GPU: the HIP kernels of libvghvideo.so are the only implementation of the samples")
     lib = _lib_video.load()
     dev = frame.device
-    if out is None:
-        out = frame._like()
-    for name, (s, sp, ss), (d, dp, ds) in zip("yuv", frame._layout(), out._layout()):
-        if d.data_ptr() == s.data_ptr() and dp == sp and ds == ss:
-            continue  # in place
-        d0, d1 = _plane_range(d)
-        for other in frame.planes:
-            s0, s1 = _plane_range(other)
-            if s0 < d1 and d0 < s1:
-                raise ValueError(f"anonymize_frame: plane {name} of out overlaps the source frame without being exactly its plane {name} (same memory, pitch and "
-                                 "step): pass out=frame for in place, or a frame elsewhere")
     plan, owner_dev = an._plan_on_device(plan, dev, (H, W), heads, method, region, margin, cells, strength, faces, owner, tables)  # the silhouettes at the frame's size
     # the chroma rows: the same formulas on the chroma boxes
     luma_rows = plan.heads
@@ -400,9 +412,8 @@ def anonymize_frame(frame: YUV420Frame, heads, method: str = "pixelate", region:
     chroma_rows, _ = an.plan_rows([chroma_box(b) for b in corners], method, int(cells), float(strength), tables)
     taps = tables.taps()
     job = _lib_video.AnonymizeJob()
-    for k, ((s, sp, ss), (d, dp, ds)) in enumerate(zip(frame._layout(), out._layout())):
-        p = job.planes[k]
-        p.src_dev, p.dst_dev, p.src_pitch, p.dst_pitch, p.src_step, p.dst_step = s.data_ptr(), d.data_ptr(), sp, dp, ss, ds
+    for p, row in zip(job.planes, planes):
+        p.src_dev, p.dst_dev, p.src_pitch, p.dst_pitch, p.src_step, p.dst_step = row
     job.height, job.width, job.n_heads, job.method, job.color = H, W, n, plan.method, y | u << 8 | v << 16
     job.region = _lib_video.REGION_MAP if owner_dev is not None else _lib_video.REGION_ELLIPSE if region == "ellipse" else _lib_video.REGION_BOX
     if n:

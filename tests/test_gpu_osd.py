@@ -241,3 +241,39 @@ def test_draw_overlay_on_a_detectors_and_a_trackers_result(gpu_lib, flame_model)
     want = restated(plan)
     assert tr.draw_overlay(labels="id", out=frame) is frame
     assert np.array_equal(buf.cpu().numpy(), yuv_ref.surface("nv12", *want, pitch=pitch, extra_rows=3)[0])
+
+
+def test_a_chroma_pair_at_an_odd_address_on_one_side_and_an_even_one_on_the_other(gpu_lib):
+    """5 x 7 (both sides odd), one item of each kind, through the C call.  The interleaved chroma plane of one surface starts at an odd byte, so its (U, V) views are
+    not the bytes of an aligned 16-bit pair and go byte by byte, while the other surface's are one 16-bit access: a pair on the source side alone, then on the
+    destination side alone, NV12 and NV21 (the lower byte is U, then V), and the odd surface in place.  Whole surfaces, sentinels included."""
+    h, w, pitch = 5, 7, 10
+    items = [ref.bar((0, 0, 4, 3), (200, 40, 90), 128), ref.rect((2, 1, 7, 5), (13, 250, 7), 1, 256), ref.text(1, -1, [2], (90, 91, 230), 1, 200)]
+    case = dict(shape=(h, w), items=items)
+    src = oc.content((h, w), "nv12", 31)
+    want = ref.render(src, (0, 1, 1), h, w, items)
+    assert not np.array_equal(want[1], src[1]) and not np.array_equal(want[2], src[2]) and want[1].shape == (3, 4)
+
+    def surface(planes, uv, v_first, seed):
+        first = [dict(offset=uv + k, pitch=pitch, step=2, shift=1, h=3, w=4) for k in range(2)]
+        geom = dict(size=uv + pitch * 3 + 8, planes=[dict(offset=0, pitch=pitch, step=1, shift=0, h=h, w=w)] + (first[::-1] if v_first else first))
+        buffer = np.random.default_rng(seed).integers(0, 256, geom["size"], dtype=np.uint8)
+        for view, plane in zip(oc.views(buffer, geom), planes):
+            view[...] = plane
+        return buffer, geom
+
+    for v_first in (False, True):
+        for src_uv, dst_uv in ((pitch * h + 1, pitch * h), (pitch * h, pitch * h + 1)):
+            host, geom = surface(src, src_uv, v_first, 5)
+            blank, dgeom = surface([np.zeros_like(p) for p in want], dst_uv, v_first, 6)
+            buf, out = torch.from_numpy(host).to(_dev()), torch.from_numpy(blank).to(_dev())
+            assert buf.data_ptr() % 2 == 0 and out.data_ptr() % 2 == 0  # so the parity of a plane's offset is the parity of its address
+            _c_call(case, buf, geom, out, dgeom, GARBAGE[0])
+            got, want_out = out.cpu().numpy(), surface(want, dst_uv, v_first, 6)[0]
+            assert np.array_equal(got, want_out), (v_first, src_uv, dst_uv, _first(got, want_out))
+            assert np.array_equal(buf.cpu().numpy(), host), (v_first, src_uv, dst_uv, "the source surface changed")
+        host, geom = surface(src, pitch * h + 1, v_first, 5)  # in place at the odd address: bytes on both sides
+        buf = torch.from_numpy(host).to(_dev())
+        _c_call(case, buf, geom, buf, geom, GARBAGE[1])
+        after, want_surface = buf.cpu().numpy(), surface(want, pitch * h + 1, v_first, 5)[0]
+        assert np.array_equal(after, want_surface), (v_first, "in place", _first(after, want_surface))

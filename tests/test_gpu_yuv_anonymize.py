@@ -287,3 +287,42 @@ def test_detector_and_tracker_remember_the_frame_without_an_rgb_copy(gpu_lib, fl
     want = yref.render_frame(y, u, v, boxes, ref.owner_map(h, w, boxes, "box"), "fill", color_yuv=(16, 128, 128))
     assert np.array_equal(buf.cpu().numpy(), yuv_ref.surface("nv12", *want, pitch=pitch, extra_rows=3)[0])
     assert tracker.update_batch([frame], rgb="host")[0].source_frame is frame
+
+
+def test_a_chroma_pair_at_an_odd_address_on_one_side_and_an_even_one_on_the_other(gpu_lib):
+    """5 x 7 (both sides odd), two heads, hand-made rows through the C call.  The interleaved chroma plane of one surface starts at an odd byte, so its (U, V)
+    views are not the bytes of an aligned 16-bit pair and go byte by byte, while the other surface's are one 16-bit access: a pair on the source side alone, then
+    on the destination side alone, NV12 and NV21 (the lower byte is U, then V), pixelate (the cell sums load) and blur (the row pass loads); every pass stores.
+    Whole surfaces, sentinels included."""
+    h, w, pitch = 5, 7, 10
+    boxes = dict(luma_boxes=[(0, 0, 4, 3), (3, 1, 7, 5)], chroma_boxes=[(0, 0, 2, 2), (1, 0, 4, 3)])
+    runs = {"pixelate": yc.raw_case((h, w), boxes["luma_boxes"], boxes["chroma_boxes"], "pixelate", "box", "nv12", luma_cell=[2, 3], chroma_cell=[2, 3], seed=21),
+            "blur": yc.raw_case((h, w), boxes["luma_boxes"], boxes["chroma_boxes"], "blur", "box", "nv12", luma_taps=[[32768, 16384], [65536]], chroma_taps=[[21846, 21845], [32768, 8192, 8192]],
+                                seed=21)}
+
+    def surface(planes, uv_offset, seed):
+        """(bytes, frame maker): sentinel bytes everywhere, the planes planted through CPU views of the layout."""
+        host = np.random.default_rng(seed).integers(0, 256, uv_offset + pitch * 3 + 8, dtype=np.uint8)
+
+        def frame(buffer):
+            return make(buffer, h, w, pitch=pitch, uv_offset=uv_offset)
+
+        for view, plane in zip(frame(torch.from_numpy(host)).planes, planes):
+            view.copy_(torch.from_numpy(np.array(plane)))  # (a copy: the expected planes are read-only)
+        return host, frame
+
+    for method, case in runs.items():
+        want = yc.expected(f"odd_pair_5x7_{method}", case)
+        planes = yc.planes_of(case)
+        assert not np.array_equal(want[1], planes[1]) and not np.array_equal(want[2], planes[2]) and want[1].shape == (3, 4), method
+        for make in (YUV420Frame.from_nv12, YUV420Frame.from_nv21):
+            for src_uv, dst_uv in ((pitch * h + 1, pitch * h), (pitch * h, pitch * h + 1)):
+                host, src_frame = surface(planes, src_uv, 5)
+                blank, dst_frame = surface(tuple(np.zeros_like(p) for p in want), dst_uv, 6)
+                buf, out = torch.from_numpy(host).to(_dev()), torch.from_numpy(blank).to(_dev())
+                src, dst = src_frame(buf), dst_frame(out)
+                assert min(src.u.data_ptr(), src.v.data_ptr()) % 2 == src_uv % 2 and min(dst.u.data_ptr(), dst.v.data_ptr()) % 2 == dst_uv % 2
+                _c_call(case, src, dst)
+                assert _same(_planes(dst), want), (method, make.__name__, src_uv, dst_uv, _where(_planes(dst), want))
+                assert np.array_equal(out.cpu().numpy(), surface(want, dst_uv, 6)[0]), (method, make.__name__, src_uv, dst_uv, "bytes outside the destination's samples were written")
+                assert np.array_equal(buf.cpu().numpy(), host), (method, make.__name__, src_uv, dst_uv, "the source surface changed")

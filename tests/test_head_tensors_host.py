@@ -90,7 +90,7 @@ def test_the_library_is_declared_in_the_build():
         ("libvghvis.so", ["visibility.hip"], ["companion_host.h", "tile_fold.h"], "vgh_vis.h", [], "build_vis"),
         ("libvghview.so", ["aligned.hip", "draw.hip", "mesh_render.hip"], ["companion_host.h", "tile_fold.h"], "vgh_view.h", [], "build_view")]
     assert build.APPLICATIONS == [build.Companion("libvghanon.so", ["anonymize.hip"], ["companion_host.h", "head_rows.h"], "vgh_anon.h", [], "build_anon")]
-    assert build.VIDEO == [build.Companion("libvghvideo.so", ["yuv_anonymize.hip", "yuv_pack.hip"], ["companion_host.h", "head_rows.h"], "vgh_video.h", [], "build_video")]
+    assert build.VIDEO == [build.Companion("libvghvideo.so", ["yuv_anonymize.hip", "yuv_pack.hip"], ["companion_host.h", "head_rows.h", "plane_views.h"], "vgh_video.h", [], "build_video")]
     assert "head_detector_amd/build_crop/" in open(os.path.join(ROOT, ".gitignore")).read().split()
     src = open(os.path.join(PKG, "csrc", "head_tensors.hip")).read()
     rules = open(os.path.join(PKG, "csrc", "head_crop_rules.h")).read()

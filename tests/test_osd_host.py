@@ -78,11 +78,11 @@ def test_osd_library_abi(tmp_path):
 def test_the_library_is_declared_in_the_build():
     from head_detector_amd import build
 
-    assert build.OVERLAY == [build.Companion("libvghosd.so", ["osd.hip"], build.HOST_HEADERS + ["osd_rules.h"], "vgh_osd.h", [], "build_osd")]
+    assert build.OVERLAY == [build.Companion("libvghosd.so", ["osd.hip"], ["companion_host.h", "osd_rules.h", "plane_views.h"], "vgh_osd.h", [], "build_osd")]
     # the four older lists are what they were
     assert [c.lib for c in build.COMPANIONS] == ["libvgheval.so", "libvghmerge.so", "libvghtrack.so", "libvghtex.so", "libvghvis.so", "libvghview.so"]
     assert build.APPLICATIONS == [build.Companion("libvghanon.so", ["anonymize.hip"], ["companion_host.h", "head_rows.h"], "vgh_anon.h", [], "build_anon")]
-    assert build.VIDEO == [build.Companion("libvghvideo.so", ["yuv_anonymize.hip", "yuv_pack.hip"], ["companion_host.h", "head_rows.h"], "vgh_video.h", [], "build_video")]
+    assert build.VIDEO == [build.Companion("libvghvideo.so", ["yuv_anonymize.hip", "yuv_pack.hip"], ["companion_host.h", "head_rows.h", "plane_views.h"], "vgh_video.h", [], "build_video")]
     assert build.DOWNSTREAM == [build.Companion("libvghcrop.so", ["head_tensors.hip"], ["companion_host.h", "head_crop_rules.h"], "vgh_crop.h", ["-ffp-contract=off"], "build_crop")]
     assert "head_detector_amd/build_osd/" in open(os.path.join(ROOT, ".gitignore")).read().split()
     every = build.COMPANIONS + build.APPLICATIONS + build.VIDEO + build.DOWNSTREAM + build.OVERLAY
@@ -107,10 +107,10 @@ def test_source_hygiene():
     src = open(os.path.join(PKG, "csrc", "osd.hip")).read()
     rules = open(os.path.join(PKG, "csrc", "osd_rules.h")).read()
     hdr = open(os.path.join(ROOT, "include", "vgh_osd.h")).read()
-    assert re.findall(r'#include "([^"]+)"', src) == ["../../include/vgh_osd.h", "companion_host.h", "osd_rules.h"]  # no other library's header
+    assert re.findall(r'#include "([^"]+)"', src) == ["../../include/vgh_osd.h", "companion_host.h", "osd_rules.h", "plane_views.h"]  # no other library's header
     assert "static_assert(VGHO_OK == OK && VGHO_ERR_INVALID == ERR_INVALID && VGHO_ERR_HIP == ERR_HIP && VGHO_ERR_NOMEM == ERR_NOMEM," in src
     # the rule header and the public header are HIP-free
-    assert re.findall(r"#include\s+(\S+)", rules) == ["<stddef.h>", "<stdint.h>", "<stdio.h>", '"../../include/vgh_osd.h"']
+    assert re.findall(r"#include\s+(\S+)", rules) == ["<stddef.h>", "<stdint.h>", "<stdio.h>", '"../../include/vgh_osd.h"', '"plane_views.h"']
     assert re.findall(r"#include\s+(\S+)", hdr) == ["<stdint.h>"]
     for text in (rules, hdr):
         assert not [w for w in ("hip/", "hipLaunchKernelGGL", "__global__", "hipMemcpy", "hipGetDevice", "threadIdx", "atomicMax") if w in text], "HIP-free"
@@ -118,6 +118,15 @@ def test_source_hygiene():
     for once in ("kFont[VGHO_GLYPHS][VGHO_GLYPH_ROWS] = {", "bool covers(", "uint32_t blend(", "Box grown_clipped(", "int64_t tile_count(", "int64_t workspace_bytes(", "const char* validate("):
         assert once in rules and once not in src, once
     assert "0x0e, 0x11" not in src and "0x0e, 0x11" not in hdr
+    # a frame's planes addressed in place are csrc/plane_views.h's, shared with libvghvideo.so: generic (no public header, neither library's prefix), its host
+    # part without the runtime
+    shared = open(os.path.join(PKG, "csrc", "plane_views.h")).read()
+    video = [open(os.path.join(PKG, "csrc", f)).read() for f in ("yuv_anonymize.hip", "yuv_pack.hip")]
+    for once in ("struct Chan", "int pair_of(", "void plane_range(", "void copy_kernel(", "reinterpret_cast<const uint16_t*>", "bool in_place(", "null plane (src_dev",
+                 "the destination overlaps source plane", "in place means exactly the source plane"):
+        assert once in shared and not [t for t in (src, rules, *video) if once in t], once
+    assert re.findall(r"#include\s+(\S+)", shared) == ["<stddef.h>", "<stdint.h>", "<stdio.h>"]
+    assert "hip/" not in shared and "vgho_" not in shared.lower() and "vghy_" not in shared.lower() and "namespace planes {" in shared
     for by_hand in ("float", "double", "asm", "dlopen", "hipMalloc(", "hipHostMalloc(", "hipEventRecord(", "hipEventSynchronize(", "set_error(const char", "g_error", "__shared__",
                     "hipMemset"):
         assert by_hand not in src and by_hand not in rules and by_hand not in hdr, by_hand

@@ -236,21 +236,30 @@ def test_the_library_is_declared_in_the_build():
     from head_detector_amd import build
 
     assert build.ANON_HEADERS == build.HOST_HEADERS + ["head_rows.h"]
-    assert build.VIDEO == [build.Companion("libvghvideo.so", list(SOURCES), build.ANON_HEADERS, "vgh_video.h", [], "build_video")]
+    assert build.PLANE_HEADERS == ["plane_views.h"]
+    assert build.VIDEO == [build.Companion("libvghvideo.so", list(SOURCES), build.HOST_HEADERS + ["head_rows.h", "plane_views.h"], "vgh_video.h", [], "build_video")]
     # the two older lists are as they were
     assert [c.lib for c in build.COMPANIONS] == ["libvgheval.so", "libvghmerge.so", "libvghtrack.so", "libvghtex.so", "libvghvis.so", "libvghview.so"]
     assert build.APPLICATIONS == [build.Companion("libvghanon.so", ["anonymize.hip"], build.ANON_HEADERS, "vgh_anon.h", [], "build_anon")]
-    # the core does not take the new sources, or the header the two anonymisers share, for its own
+    # the core does not take the new sources, or the headers they share with the RGB anonymiser and with the overlay, for its own
     core = {f for f in os.listdir(build.CSRC)} - {f for c in build.COMPANIONS + build.APPLICATIONS + build.VIDEO for f in c.sources + c.headers}
-    assert not core & (set(SOURCES) | {"head_rows.h"}) and set(build.SOURCES) <= core
+    assert not core & (set(SOURCES) | {"head_rows.h", "plane_views.h"}) and set(build.SOURCES) <= core
     # the head rows are csrc/head_rows.h's, shared with csrc/anonymize.hip: included, and defined here no longer
     anon = open(os.path.join(build.CSRC, SOURCES[0])).read()
     assert '#include "head_rows.h"' in anon
     for moved in ("struct HeadRow", "head_of(const uint32_t", "in_ellipse(const HeadRow", "void paint_owner_kernel(const HeadRow", "int64_t up16("):
         assert moved not in anon, moved
-    for name in SOURCES + ("head_rows.h",):
+    # a frame's planes addressed in place are csrc/plane_views.h's, shared with csrc/osd.hip: included by both sources, and defined here no longer
+    shared = open(os.path.join(build.CSRC, "plane_views.h")).read()
+    for name in SOURCES:
+        src = open(os.path.join(build.CSRC, name)).read()
+        assert '#include "plane_views.h"' in src
+        for moved in ("struct Chan", "int pair_of(", "void plane_range(", "void copy_kernel(", "reinterpret_cast<const uint16_t*>", "null plane (src_dev", "the destination overlaps source plane"):
+            assert moved in shared and moved not in src, (name, moved)
+    assert "hip/" not in shared and "include/" not in shared and "vgho_" not in shared.lower() and "vghy_" not in shared.lower()
+    for name in SOURCES + ("head_rows.h", "plane_views.h"):
         src = open(os.path.join(ROOT, "head_detector_amd", "csrc", name)).read()
-        assert '#include "companion_host.h"' in src and ('#include "../../include/vgh_video.h"' in src or name == "head_rows.h")
+        assert name == "plane_views.h" or ('#include "companion_host.h"' in src and ('#include "../../include/vgh_video.h"' in src or name == "head_rows.h"))
         # no floating point, no inline assembly, static LDS only, all host plumbing from companion_host.h, nothing of the other libraries
         for by_hand in ("hipEventRecord(", "hipEventSynchronize(", "hipHostMalloc(", "hipMalloc(", "set_error(const char", "g_error", "asm", "dlopen", "float", "double",
                         "hipFuncSetAttribute", "extern __shared__", "vgh_anon.h", "vgh.h", "vghan_"):

@@ -166,11 +166,11 @@ int main() {
     for (int k = 0; k < 9; ++k) pack.coef[k] = k709[k];
     {
         PackArgs a;
-        EXPECT(pack_plan(&pack, a) == OK && a.pair == 2 && a.W == 100 && a.H == 97 && a.CW == 50 && a.CH == 49 && a.coef[8] == -2639 && a.y_offset == 16 && a.dst[0] == out);
+        EXPECT(pack_plan(&pack, a) == OK && a.pair == 2 && a.W == 100 && a.H == 97 && a.CW == 50 && a.CH == 49 && a.coef[8] == -2639 && a.y_offset == 16 && a.y.dst == out);
         vghy_pack_job planar = pack;
         planar.planes[1] = {nullptr, out + 10240, 0, 50, 0, 1};
         planar.planes[2] = {nullptr, out + 10240 + 2450, 0, 50, 0, 1};
-        EXPECT(pack_plan(&planar, a) == OK && a.pair == 0 && a.step[2] == 1);
+        EXPECT(pack_plan(&planar, a) == OK && a.pair == 0 && a.c[1].dstep == 1);
     }
     EXPECT(vghy_pack_rgb(nullptr, nullptr) == VGHY_ERR_INVALID && strstr(vghy_last_error(), "null job"));
 #define PACK_REFUSED(change, words)     \
