@@ -46,8 +46,12 @@ static_assert(DT_LDS <= 160 * 1024, "one workgroup per CU");
 // of 64 cycles per tile.  A u8 pixel is an exact bf16, so the stem is ALSO an exact-product bf16 GEMM once the weights are split: w / 255 = hi + mid + lo, three bf16 values
 // carrying 24 significant bits.  Per 16 pixels: 3 cout tiles x 3 splits = 9 v_mfma_f32_16x16x32_bf16 of 16 cycles (K = 27 in ONE instruction, no cout padding), fp32 accumulate,
 // lo -> mid -> hi.  Every product is exact; what differs from the reference's fmaf chain is the order of the fp32 additions and where / 255 is rounded (the weights instead
-// of the pixels): ~1e-7 relative before the ONE rounding to bf16, i.e. a flipped bf16 ulp in ~1e-4 of the stem values (tests/test_gpu_parity.py::test_b2b_pairs_equal_their_two_launches; the
-// whole stem -> downsample -> conv1|conv2 chain against its reference in tests/test_gpu_tuned_ops.py and tests/test_gpu_offpath_ops.py).
+// of the pixels): ~1e-7 relative before the ONE rounding to bf16, i.e. a bf16 value on the other side of a rounding boundary wherever the sum lies that close to one.  How often
+// depends on the operands: on the `chain` case of tests/stem_pair_exact_cases.py (integer sums, a tenth of them exact ties or zeros, which the stem kernel's own rounding errors then
+// decide) the stem kernel's tensor differs from the exactly rounded one in 0.7 - 1.0 % of its values (tests/test_gpu_stem_pair_exact.py, set_b2b(3)); with random weights it is rare.
+// Held TO THE BIT on exact-arithmetic operands -- every border kind, several tiles per workgroup, two lanes -- by tests/test_gpu_stem_pair_exact.py; to tolerances by
+// tests/test_gpu_parity.py::test_b2b_pairs_equal_their_two_launches and, as the whole stem -> downsample -> conv1|conv2 chain against its reference, by tests/test_gpu_tuned_ops.py and
+// tests/test_gpu_offpath_ops.py.
 // K slots are assigned so that a lane's 8 B values are 16 contiguous bytes of the patch (a kernel row's first 8 of 9 (kx, ci) values); the three ninth values ride in the
 // fourth k group.  The image patch sits in LDS as bf16 NHWC rows (35 x 105 values at a 216-byte pitch), converted by the loader wave (v_cvt_f32_ubyte, upper half stored).
 constexpr int ST_IW = 35, ST_RP = 216;      // image patch: 35 x 35 pixels x 3 bf16 channels, row pitch in bytes

@@ -123,7 +123,8 @@ static void net_b2b_fields(ConvArgs& a, const ConvArgs& a2) {  // the second con
 }
 
 // forwards of u8 images run the stem conv inside the stage-1 pair's launch (ds_b2b.hip, "u" tile): the default b2b mode, the pair found and on its persistent tile.
-// The stem is then a bf16 x 3 split GEMM on the matrix cores -- exact products, another fp32 summation order: a flipped bf16 ulp in ~4e-5 of the stem values;
+// The stem is then a bf16 x 3 split GEMM on the matrix cores -- exact products, another fp32 summation order: a bf16 value across a rounding boundary where the sum lies within ~1e-7 of one (0.7 - 1.0 % of the stem values
+// on the tie-rich `chain` case of tests/stem_pair_exact_cases.py, measured by tests/test_gpu_stem_pair_exact.py; rare with random weights);
 // vgh_net_set_b2b(n, 3) keeps the stem launch and with it the bit-identity of every mode
 static bool stem_in_pair_launch(const vgh_net* n) { return n->fuse_b2b == 1 && n->stem_pair >= 0 && n->stem3_ok == 1 && n->ops[n->stem_pair + 1].b2b == 1; }
 
