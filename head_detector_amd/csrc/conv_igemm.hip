@@ -16,6 +16,8 @@
 //   LDS-DMA destination is lane-linear, the swizzle is applied on the SOURCE side: per-lane gather
 //   address for activations (which also implements im2col + zero padding), host pre-swizzled image for
 //   weights (vgh_pack_conv_weights_host).
+#include <string>
+
 #include "conv_kernels.inc"
 #include "conv_cfg_list.h"
 
@@ -437,11 +439,8 @@ int vgh_conv_prepare(ConvArgs& a) {
 
 int vgh_conv_pick_auto(const ConvArgs& a) { return a.split ? vgh_conv_split_pick(a) : vgh_conv_pick_cfg(a); }
 
-int vgh_launch_conv(const ConvArgs& a0, int force_cfg, hipStream_t stream) {
-    ConvArgs a = a0;
-    if (int rc = vgh_conv_prepare(a)) return rc;
-    if (a.P == 0) return VGH_OK;
-    if (a.split) return vgh_launch_conv_split(a, force_cfg, stream);  // parity modes: own tile set (conv_split.hip)
+// the tile a launch of the PREPARED bf16 conv `a` runs on: the forced one, its fall-backs, a q tile's p twin -- the one place that decides it
+static int resolve_cfg(const ConvArgs& a, int force_cfg, int* out) {
     int cfg = force_cfg >= 0 ? force_cfg : vgh_conv_pick_cfg(a);
     VGH_REQUIRE(cfg < kNumCfgs, "conv: cfg %d out of range", cfg);
     if (!cfg_ok_for(cfg, a)) {
@@ -456,12 +455,34 @@ int vgh_launch_conv(const ConvArgs& a0, int force_cfg, hipStream_t stream) {
         VGH_REQUIRE(t >= 0, "conv: cfg %s has no fallback tile", g_cfgs[cfg].name);
         cfg = t;
     }
+    *out = cfg;
+    return VGH_OK;
+}
+
+int vgh_launch_conv(const ConvArgs& a0, int force_cfg, hipStream_t stream) {
+    ConvArgs a = a0;
+    if (int rc = vgh_conv_prepare(a)) return rc;
+    if (a.P == 0) return VGH_OK;
+    if (a.split) return vgh_launch_conv_split(a, force_cfg, stream);  // parity modes: own tile set (conv_split.hip)
+    int cfg;
+    if (int rc = resolve_cfg(a, force_cfg, &cfg)) return rc;
     const CfgEntry& e = g_cfgs[cfg];
     TileGrid grid;
     VGH_REQUIRE(tile_grid(e.family, e.BP, e.BC, e.TW, e.TH, a, &grid), "conv: too many tiles");
     if (int rc = e.launch(a, grid, e.lds, stream)) return rc;
     VGH_HIP(hipGetLastError());
     return VGH_OK;
+}
+
+// the summation chain (conv_tiles.h, chain_code) of the tile vgh_launch_conv(a0, force_cfg) would run this bf16 conv on; -1: unknown, or no tile
+int vgh_conv_chain(const ConvArgs& a0, int force_cfg) {
+    // a probe, not a launch: whatever the rules below report while it runs is taken back, so that a forward which then succeeds leaves vgh_last_error as it was
+    const std::string before = vgh_last_error();
+    ConvArgs a = a0;
+    int cfg = -1, code = -1;
+    if (!vgh_conv_prepare(a) && a.P != 0 && !a.split && !a.in_fp8 && !a.out_fp8 && !a.out_f32 && !resolve_cfg(a, force_cfg, &cfg)) code = chain_code(g_cfgs[cfg].family);
+    if (before != vgh_last_error()) vgh_set_error("%s", before.c_str());
+    return code;
 }
 
 // ---- back-to-back GEMM (conv_kernels.inc, T2 > 0): a conv whose 96 output channels fit ONE cout tile, fused with the 1x1 conv that is its only reader ----

@@ -60,6 +60,35 @@ inline bool tile_class_admits(TileFamily f, int BC, int ksize, int stride, int c
     return !(c.max_cout_pad && cout_pad > c.max_cout_pad);
 }
 
+// ---- the summation chain of a family's bf16 3x3 / stride-1 tiles: what decides every bit of an output element.  All of them issue v_mfma_f32_32x32x16_bf16 with the
+//      weights as A and the pixels as B, one 32-channel block of one tap per pair of MFMAs; they differ in the order of those pairs and in where the bias enters.
+//      The survivor kernel of postproc.hip walks the same chain for a single pixel (an output element depends on its own weight row and pixel column only). ----
+struct ChainTrait {
+    int known;       // 0: the chain of this family is not reproduced anywhere else -- its ops always run densely
+    int tap_major;   // 1: k-blocks in packed-weight order, tap-major over ascending channel blocks; 0: channel-block-major with the nine taps (ky, then kx) inside
+    int bias_first;  // 1: the accumulator starts at the bias; 0: it starts at zero and the bias is added in fp32 afterwards
+};  // (in every family lane half `hi` of MFMA h = 0 / 1 of a 32-channel block holds channels 8 (2 h + hi) .. + 7: nothing to record)
+constexpr ChainTrait kChainTrait[kNumTileFamilies] = {
+    {1, 1, 0},  // Igemm (conv_kernels.inc, stage_load: channel block fastest, then kx, then ky; k-blocks past the end are zeros)
+    {1, 0, 0},  // Patch (conv3x3_patch_kernel: steps (cb, ky), sub-steps (kx, h); bias in the epilogue)
+    {1, 0, 1},  // PatchPipe (conv3x3_patch3_kernel: the same steps, the bias as the C input of the first MFMA)
+    {0, 0, 0},  // Stream (1x1 only)
+    {0, 0, 0},  // PatchS2
+    {1, 0, 1},  // PingPongG (conv_pp.hip: for cb, for tap, two MFMAs; PP_INIT_ROWS)
+    {1, 0, 1},  // PingPongH
+    {1, 0, 1},  // PingPongS (pixels of an overlap column are computed twice with the same chain)
+    {0, 0, 0},  // R
+    {0, 0, 0},  // W
+    {0, 0, 0},  // SplitIgemm
+    {0, 0, 0},  // SplitPatch
+    {0, 0, 0},  // PingPongF16
+};
+// the chain as one small code for the survivor kernel: -1 unknown, else bit 0 = tap_major, bit 1 = bias_first
+inline int chain_code(TileFamily f) {
+    const ChainTrait& c = kChainTrait[(int)f];
+    return c.known ? (c.tap_major | (c.bias_first << 1)) : -1;
+}
+
 // ---- launch-level predicates of single families (`a` prepared) ----
 // the ping-pong tiles' epilogue addresses the output and residual tensors through buffer descriptors: 32-bit byte offsets
 inline int vgh_conv_pp_fits(const ConvArgs& a) {

@@ -31,6 +31,8 @@ struct vgh_detector {
     // lazy FLAME gather (r06, vgh_detector_set_lazy_flame): the candidate stage gathers boxes only; the 413-vectors of the SURVIVORS are built by the select from the
     // prediction buffers (106 MB of candidate vectors per 64 images for ~3 survivors per image otherwise).
     bool lazy_flame = false;
+    // (The net's plan also marks the 3x3 towers in front of those convs, tower_plan.h: a deferring forward skips them as well where it can, and the select then starts
+    // from the towers' root tensor, vgh_survivor_towers.  The detector keeps no state for it: the net says per generation what it left pending.)
     // deferred FLAME predictions: the net's plan marks the 1x1 convs that write the FLAME channels of every level's prediction rows as deferrable, and together they
     // write exactly those channels (rows_ok, decided at create).  The lazy gather then turns the net's defer switch on: its forwards skip those convs, and the select
     // computes the survivors' rows from the convs' inputs (vgh_survivor_rows) instead of reading dense prediction rows.  Every eager stage runs the pending convs first.
@@ -361,7 +363,20 @@ static int select_on(vgh_detector* d, int B, float conf_thr, float iou_thr, vgh_
         if ((rc = vgh_net_run_deferred(d->net, stream))) return rc;
     // the survivors' rows are computed from the towers' outputs where this generation's forward left the prediction convs pending; where it ran them (the switch was
     // off then, or an eager stage has run them since) the dense rows are complete and are read as before
-    const bool rows = lazy && d->rows_on() && vgh_net_deferred_pending(d->net);
+    bool rows = lazy && d->rows_on() && vgh_net_deferred_pending(d->net);
+    // ... and from the root windows of the towers where that forward skipped the towers as well (tower_plan.h): one tree per level, with the summation chains the
+    // forward resolved.  A tree the survivor kernel cannot walk (none is expected: the forward skips towers only on known chains) sends the select back to dense rows.
+    vgh_tower_tree trees[VGH_MAX_LEVELS];
+    const bool towers = rows && vgh_net_towers_pending(d->net);
+    if (towers) {
+        bool ok = true;
+        for (int l = 0; l < c.n_levels && ok; ++l)
+            ok = vgh_net_tower_tree(d->net, c.level_buf[l], &trees[l]) == 0 && vgh_tower_tree_ok(trees[l], c.shape_live + c.expr_live + 13);
+        if (!ok) {
+            if ((rc = vgh_net_run_deferred(d->net, stream))) return rc;
+            rows = false;
+        }
+    }
     if (c.keep_k <= 1024) {  // r06: NMS + compaction + head list as one launch
         vgh_head_level lv[VGH_MAX_LEVELS];
         for (int l = 0; l < c.n_levels; ++l) {
@@ -375,7 +390,9 @@ static int select_on(vgh_detector* d, int B, float conf_thr, float iou_thr, vgh_
                                  o->scores_dev, o->flame_dev, capacity, want_heads ? d->head_row : nullptr, himg, o->n_heads_dev, d->ticket, lazy ? lv : nullptr,
                                  c.n_levels, lazy ? d->idx : nullptr, c.shape_live, c.expr_live, stream, rows)))
             return rc;
-        if (rows)
+        if (rows && towers) {
+            if ((rc = vgh_survivor_towers(lv, c.n_levels, trees, B, c.pre_k, c.keep_k, d->idx, d->keep_idx, o->counts_dev, c.shape_live, c.expr_live, o->flame_dev, stream))) return rc;
+        } else if (rows)
             if ((rc = vgh_survivor_rows(lv, c.n_levels, d->row_ops, d->n_row_ops, B, c.pre_k, c.keep_k, d->idx, d->keep_idx, o->counts_dev, c.shape_live, c.expr_live, o->flame_dev,
                                         stream)))
                 return rc;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "net_plan.h"
+#include "tower_plan.h"
 #include "per_device.h"
 #include "vgh_internal.h"
 
@@ -34,6 +35,7 @@ struct NetOp {
     float* gscale = nullptr;   // device [cout_pad] (NetPlan::Op::gscale), else nullptr
     float* dvec = nullptr;     // device [cout_pad] (NetPlan::Op::dvec), else nullptr
     int overhang_ok = 0, b2b = 0, deferrable = 0;  // as planned (NetPlan::Op)
+    int tower = 0, writes_tower_root = 0;          // as planned (tower_plan.h): 1 + the op's tree / the op writes a tree's root window
     hipEvent_t ev_done = nullptr;  // recorded behind this op when the plan says a later op waits for it (NetPlan::Op::ev_done), else nullptr
 };
 
@@ -75,6 +77,16 @@ struct vgh_net {
     // inputs (the last tensors of the FLAME towers) stay intact in the arena until the next forward.  `skipping`: true while such a forward queues its ops
     DeferState defer;
     bool skipping = false;
+    // deferred towers (tower_plan.h): a deferring forward also skips the tower-deferrable ops when every one of them would run on a tile whose summation chain the
+    // survivor kernel reproduces (conv_tiles.h, kChainTrait) -- decided per forward, for its batch and lanes, by the launcher's own tile resolution; else it runs them
+    bool skipping_towers = false;   // true while such a forward queues its ops
+    std::vector<int> tower_chain;   // per op: the chain code of the pending generation (valid where defer.towers)
+    std::vector<TowerTree> trees;   // NetPlan::towers.trees
+    bool guard_roots = false;       // the forward in front of the one being queued skipped its towers: selects of it read the trees' roots (writes_guarded)
+    bool prev_towers = false;       // ... as left by the latest forward, replay or profile, for the next one
+    bool graph_skips_towers = false;
+    int graph_lanes = 1;
+    std::vector<int> graph_chain;   // tower_chain as the capture resolved it
     bool graph_skips = false;  // what the captured graph does, whatever the switch says at replay
     int graph_B = 0;
     hipStream_t last_stream = nullptr;  // the caller's stream of the latest forward / replay: where vgh_net_buffer queues convs that forward left pending
@@ -165,6 +177,7 @@ static int net_run_op(vgh_net* n, const NetOp& op, const void* image0, int fmt, 
             if ((fused || stem3) && op_index == n->stem_pair + 1) return VGH_OK;  // ran inside the stem's launch
             if (n->fuse_b2b && op.b2b == 2) return VGH_OK;             // ran inside the previous conv's launch
             if (n->skipping && op.deferrable) return VGH_OK;           // left pending for vgh_net_run_deferred
+            if (n->skipping_towers && op.tower) return VGH_OK;         // its tower too: the select walks it for the survivors alone
             ConvArgs a;
             if (int rc = net_conv_args(n, op, B, at, &a)) return rc;
             a.grid_share = share;
@@ -238,8 +251,43 @@ int vgh_net_lane_streams(vgh_net* n, hipStream_t main, hipStream_t* out) {
 // MFMA-bound 3x3 conv of the other) instead of two copies of the same one.
 static std::atomic<int> g_lane_lag{0};
 
+// the ONE rule for how many batch lanes a forward of B images runs on (1: the whole batch on the caller's stream)
+static int forward_lanes(const vgh_net* n, int B) { return (n->nsplit > 1 && B > 1) ? (n->nsplit < B ? n->nsplit : B) : 1; }
+
+// The prediction guard (overlap mode): what a select of the PREVIOUS forward may still be reading on another stream.  The fp32 prediction buffers always; and, where
+// that previous forward skipped its towers, the root windows of the trees, which such a select reads in their place (`guard_roots`: what the previous forward did,
+// whatever this one does -- the switch may have been turned in between, or this batch may resolve to a tile without a chain trait).  The roots' writers stand in
+// front of the first fp32 conv, so the wait moves up to them.  A forward behind one that ran its towers waits exactly where it always did.
+static bool writes_guarded(const vgh_net* n, const NetOp& op) {
+    if (op.d.kind == VGH_OP_CONV && n->bufs[op.d.out_buf].is_f32 == VGH_FMT_F32) return true;
+    return n->guard_roots && op.writes_tower_root;
+}
+
+// The chain codes of the tower-deferrable ops for a forward of B images on L lanes: every op resolved as the launcher would, per lane.  false: there are no such ops,
+// or one of them would run on a tile whose chain is unknown, or on different chains in different lanes -- the forward then runs its towers.
+static bool tower_chains(vgh_net* n, int B, int L, std::vector<int>* chain) {
+    chain->assign(n->ops.size(), -1);
+    if (n->trees.empty() || B < 1) return false;
+    for (size_t i = 0; i < n->ops.size(); ++i) {
+        const NetOp& op = n->ops[i];
+        if (!op.tower) continue;
+        int lane = 0;
+        const int bad = for_each_lane(B, L, [&](int nb, int at) {
+            ConvArgs a;
+            if (net_conv_args(n, op, nb, at, &a)) return 1;
+            a.fallback_cfg1 = op.auto_cfg + 1;
+            const int c = vgh_conv_chain(a, op.d.force_cfg >= 0 ? op.d.force_cfg : op.auto_cfg);
+            if (c < 0 || (lane++ > 0 && c != (*chain)[i])) return 1;
+            (*chain)[i] = c;
+            return 0;
+        });
+        if (bad) return false;
+    }
+    return true;
+}
+
 static int net_forward_split(vgh_net* n, const void* image_dev, int image_fmt, int B, hipStream_t main) {
-    const int L = n->nsplit < B ? n->nsplit : B;
+    const int L = forward_lanes(n, B);
     int at[vgh_net::kLanes + 1];
     at[0] = 0;
     for (int l = 0; l < L; ++l) at[l + 1] = at[l] + rows_of_lane(B, L, l);
@@ -262,7 +310,7 @@ static int net_forward_split(vgh_net* n, const void* image_dev, int image_fmt, i
             const NetOp& op = *seq[i];
             hipStream_t st = l == 0 ? main : n->side[l];
             if (lag > 0 && l > 0 && i == 0) VGH_HIP(hipStreamWaitEvent(st, n->ev_lag[l - 1], 0));  // recorded below, `lag` ops into lane l-1
-            if (guard_pending[l] && op.d.kind == VGH_OP_CONV && n->bufs[op.d.out_buf].is_f32 == VGH_FMT_F32) {
+            if (guard_pending[l] && writes_guarded(n, op)) {
                 VGH_HIP(hipStreamWaitEvent(st, n->pred_guard, 0));
                 guard_pending[l] = false;
             }
@@ -374,6 +422,8 @@ int vgh_net_create(int device, int image_size, int max_batch, const vgh_buf_desc
         vgh_set_error("%s", plan.err);
         return rc;
     }
+    TowerPlan towers;  // the second mark of the defer switch (tower_plan.h)
+    net_plan_towers(bufs, ops, n_ops, &plan, &towers);
     VGH_HIP(hipSetDevice(device));
     // ---- allocate: from here on the guard destroys the half-built net on every early return (vgh_net_destroy takes null pointers and events) ----
     std::unique_ptr<vgh_net, NetDestroy> guard(new vgh_net());
@@ -407,6 +457,8 @@ int vgh_net_create(int device, int image_size, int max_batch, const vgh_buf_desc
         op.overhang_ok = po.overhang_ok;
         op.b2b = po.b2b;
         op.deferrable = po.deferrable;
+        op.tower = po.tower;
+        op.writes_tower_root = po.writes_tower_root;
         if (ops[i].kind == VGH_OP_CONV || ops[i].kind == VGH_OP_STEM) {
             op.wf32 = (float*)(n->wblob + po.w);  // conv: the same storage as wpack, bf16 image (throughput mode) or dense fp32 (parity mode)
             op.bias = (float*)(n->wblob + po.bias);
@@ -427,6 +479,8 @@ int vgh_net_create(int device, int image_size, int max_batch, const vgh_buf_desc
         if (int rc = vgh_conv_prepare(ref)) return rc;
         op.auto_cfg = vgh_conv_pick_auto(ref);
     }
+    n->trees = towers.trees;
+    n->tower_chain.assign(n->ops.size(), -1);
     // ---- the stem + the stage-1 pair as one launch ("u" tile): decided once, from the pair's descriptor ----
     if (n->stem_pair >= 0 && n->stem_pair + 2 < (int)n->ops.size() && n->ops[n->stem_pair + 1].b2b == 1 && image_size % 32 == 0) {
         ConvArgs a, a2;
@@ -470,19 +524,28 @@ int vgh_net_forward(vgh_net* n, const void* image_dev, int image_fmt, int B, voi
     // the main stream at the end (also valid under stream capture: the graph gets parallel branches).
     hipStream_t main = (hipStream_t)stream;
     ++n->generation;  // before anything is queued: a forward that fails half-way has touched the prediction buffers too
-    n->defer.forward(B, n->defer.skip());
+    {
+        std::vector<int> chain;
+        const int L = forward_lanes(n, B);
+        const bool towers = n->defer.skip() && tower_chains(n, B, L, &chain);
+        n->guard_roots = n->prev_towers;  // (sticky: vgh_net_run_deferred clears defer.towers, but a select queued before it may still be reading the roots)
+        n->prev_towers = towers;
+        n->defer.forward(B, n->defer.skip(), towers, L);
+        if (towers) n->tower_chain.swap(chain);
+    }
     n->last_stream = main;
     struct Skipping {  // cleared on every return path
         vgh_net* n;
-        ~Skipping() { n->skipping = false; }
+        ~Skipping() { n->skipping = n->skipping_towers = false; }
     } skipping{n};
     n->skipping = n->defer.pending;
+    n->skipping_towers = n->defer.towers;
     if (int rc = ensure_lanes(n, main)) return rc;
-    if (n->nsplit > 1 && B > 1) return net_forward_split(n, image_dev, image_fmt, B, main);
+    if (forward_lanes(n, B) > 1) return net_forward_split(n, image_dev, image_fmt, B, main);
     bool pending[vgh_net::kLanes] = {false, false, false, false}, used[vgh_net::kLanes] = {false, false, false, false};
     bool guard_pending = n->pred_guard != nullptr;
     for (const NetOp& op : n->ops) {
-        if (guard_pending && op.d.kind == VGH_OP_CONV && n->bufs[op.d.out_buf].is_f32 == VGH_FMT_F32) {
+        if (guard_pending && writes_guarded(n, op)) {
             // every stream that may run a prediction conv waits (main; the lanes inherit it through the fork / their own wait)
             VGH_HIP(hipStreamWaitEvent(main, n->pred_guard, 0));
             for (int l = 1; l < vgh_net::kLanes; ++l)
@@ -524,6 +587,7 @@ int vgh_net_profile(vgh_net* n, const void* image_dev, int image_fmt, int B, voi
     hipStream_t st = (hipStream_t)stream;
     ++n->generation;
     n->defer.forward(B, false);  // the profiler runs every op: dense prediction buffers, nothing pending
+    n->prev_towers = false;
     if (int rc = ensure_lanes(n, st)) return rc;
     const size_t m = n->ops.size();
     struct Events {  // destroyed on every return path
@@ -536,7 +600,7 @@ int vgh_net_profile(vgh_net* n, const void* image_dev, int image_fmt, int B, voi
     std::vector<hipEvent_t>& ev = events.v;
     for (auto& e : ev) VGH_HIP(hipEventCreate(&e));
     VGH_HIP(hipEventRecord(ev[0], st));
-    const int L = (n->nsplit > 1 && B > 1) ? (n->nsplit < B ? n->nsplit : B) : 1;
+    const int L = forward_lanes(n, B);
     for (size_t i = 0; i < m; ++i) {
         if (L == 1) {
             if (int rc = net_run_op(n, n->ops[i], image_dev, image_fmt, B, 0, st)) return rc;
@@ -582,6 +646,9 @@ int vgh_net_capture(vgh_net* n, const void* image_dev, int image_fmt, int B, voi
     VGH_HIP(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
     int rc = vgh_net_forward(n, image_dev, image_fmt, B, stream);
     n->graph_skips = n->defer.pending;
+    n->graph_skips_towers = n->defer.towers;
+    n->graph_lanes = n->defer.lanes;
+    n->graph_chain = n->tower_chain;
     n->graph_B = B;
     n->defer.forward(0, false);  // the recording pass ran nothing: no tower outputs of this generation to run deferred ops on
     hipError_t e = hipStreamEndCapture(st, &n->graph);
@@ -595,7 +662,9 @@ int vgh_net_forward_graph(vgh_net* n, void* stream) {
     VGH_REQUIRE(n && n->graph_exec, "net_forward_graph: call vgh_net_capture first");
     VGH_REQUIRE(!n->pred_guard, "net_forward_graph: a prediction guard event is set (detector overlap mode); use vgh_net_forward");
     ++n->generation;
-    n->defer.forward(n->graph_B, n->graph_skips);
+    n->defer.forward(n->graph_B, n->graph_skips, n->graph_skips_towers, n->graph_lanes);
+    n->prev_towers = n->graph_skips_towers;
+    if (n->graph_skips_towers) n->tower_chain = n->graph_chain;
     n->last_stream = (hipStream_t)stream;
     VGH_HIP(hipGraphLaunch(n->graph_exec, (hipStream_t)stream));
     return VGH_OK;
@@ -609,17 +678,24 @@ int vgh_net_set_defer(vgh_net* n, int on) {
 
 int vgh_net_run_deferred(vgh_net* n, void* stream) {
     VGH_REQUIRE(n, "net_run_deferred: null handle");
+    const bool towers = n->defer.towers;
+    const int L = n->defer.lanes;
     const int B = n->defer.take();
     if (B == 0) return VGH_OK;
-    // one launch per op for the whole batch, on the stream the forward was joined into: the op's tile is the one chosen for the arena batch (NetOp::auto_cfg),
-    // so the rows are the bits a forward that runs the op itself writes, whatever its batch split
-    for (const NetOp& op : n->ops)
+    // every pending op in program order, on the stream the forward was joined into: the towers first -- on the forward's own sub-batches, so each runs on the tile
+    // (and summation chain) it would have had there -- then the prediction convs, one launch per op for the whole batch: a 1x1's chain is the same on every tile of
+    // the table, so the rows are the bits a forward that runs the op itself writes, whatever its batch split
+    for (const NetOp& op : n->ops) {
+        if (towers && op.tower)
+            if (int rc = for_each_lane(B, L, [&](int nb, int at) { return net_run_op(n, op, nullptr, VGH_IMG_U8_NHWC, nb, at, (hipStream_t)stream); })) return rc;
         if (op.deferrable)
             if (int rc = net_run_op(n, op, nullptr, VGH_IMG_U8_NHWC, B, 0, (hipStream_t)stream)) return rc;
+    }
     return VGH_OK;
 }
 
 int vgh_net_deferred_pending(vgh_net* n) { return n && n->defer.pending ? 1 : 0; }
+int vgh_net_towers_pending(vgh_net* n) { return n && n->defer.pending && n->defer.towers ? 1 : 0; }
 
 void* vgh_net_buffer_ptr(vgh_net* n, int buf_id) { return (n && buf_id >= 0 && buf_id < (int)n->buf_ptr.size()) ? n->buf_ptr[buf_id] : nullptr; }
 // dense buffers are handed out complete: convs that the latest forward left pending (vgh_net_set_defer) and that write this buffer are queued first, behind that forward
@@ -627,7 +703,7 @@ void* vgh_net_buffer(vgh_net* n, int buf_id) {
     void* p = vgh_net_buffer_ptr(n, buf_id);
     if (p && n->defer.pending)
         for (const NetOp& op : n->ops)
-            if (op.deferrable && op.d.out_buf == buf_id) {
+            if ((op.deferrable || (n->defer.towers && op.tower)) && op.d.out_buf == buf_id) {
                 if (vgh_net_run_deferred(n, n->last_stream)) return nullptr;  // (vgh_last_error says why)
                 break;
             }
@@ -693,6 +769,39 @@ int vgh_net_row_ops(vgh_net* n, int out_buf, vgh_row_op* out, int max_ops) {
         out[k++] = vgh_row_op{(const uint16_t*)n->buf_ptr[op.d.in_buf], op.wpack, op.bias, ib.pitch, op.d.in_coff, op.d.cin / 32, op.d.cout_pad, op.d.cout_store, op.d.out_coff, op.d.act};
     }
     return k;
+}
+int vgh_net_tower_tree(vgh_net* n, int out_buf, vgh_tower_tree* t) {
+    if (!n || !t || !n->defer.pending || !n->defer.towers) return -1;
+    for (const TowerTree& tr : n->trees) {
+        if (tr.pred_buf != out_buf) continue;
+        memset(t, 0, sizeof(*t));
+        const vgh_buf_desc& rb = n->bufs[tr.root_buf];
+        t->root = (const uint16_t*)n->buf_ptr[tr.root_buf];
+        t->root_pitch = rb.pitch;
+        t->root_c0 = tr.root_c0;
+        t->root_c = tr.root_c1 - tr.root_c0;
+        t->depth = tr.depth;
+        if (tr.depth < 1 || tr.depth > kMaxTowerDepth) return -1;
+        t->chan[0] = t->root_c;
+        for (int l = 1; l <= tr.depth; ++l) t->chan[l] = n->bufs[tr.bufs[l]].pitch;
+        int k = 0;
+        for (size_t j = 0; j < tr.ops.size(); ++j) {
+            const NetOp& op = n->ops[tr.ops[j]];
+            const int chain = n->tower_chain[tr.ops[j]];
+            if (chain < 0 || k == kMaxTreeOps) return -1;
+            // layer 1 reads the root window, kept per survivor from channel root_c0 on
+            t->op[k++] = vgh_tree_op{op.wpack, op.bias, tr.layer[j], op.d.in_coff - (tr.layer[j] == 1 ? tr.root_c0 : 0), op.d.cin / 32, op.d.cout_pad, op.d.cout_store, op.d.out_coff, op.d.act,
+                                     op.d.grp_cout, op.d.grp_in_stride, chain};
+        }
+        for (const NetOp& op : n->ops) {
+            if (!op.deferrable || op.d.out_buf != out_buf) continue;
+            if (k == kMaxTreeOps || op.d.in_buf != tr.bufs[tr.depth]) return -1;
+            t->op[k++] = vgh_tree_op{op.wpack, op.bias, tr.depth + 1, op.d.in_coff, op.d.cin / 32, op.d.cout_pad, op.d.cout_store, op.d.out_coff, op.d.act, 0, 0, 1};
+        }
+        t->n_ops = k;
+        return 0;
+    }
+    return -1;
 }
 int vgh_net_max_batch(vgh_net* n) { return n ? n->max_batch : 0; }
 int vgh_net_device(vgh_net* n) { return n ? n->device : 0; }

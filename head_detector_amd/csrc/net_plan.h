@@ -20,6 +20,18 @@ inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 // the ONE place that splits a batch over lanes: the rows of lane l when B images run on L lanes (the first B % L lanes take one more)
 inline int rows_of_lane(int B, int L, int l) { return B / L + (l < B % L ? 1 : 0); }
 
+// the sub-batches of B images on L lanes, in lane order: fn(rows, first row); stops at the first non-zero result and returns it
+template <class F>
+inline int for_each_lane(int B, int L, F&& fn) {
+    int at = 0;
+    for (int l = 0; l < L; ++l) {
+        const int nb = rows_of_lane(B, L, l);
+        if (int rc = fn(nb, at)) return rc;
+        at += nb;
+    }
+    return 0;
+}
+
 // ---- descriptor -> ConvArgs: every numeric field of a conv launch, for the executor (vgh_op_desc + its buffers) and for vgh_conv2d (vgh_conv_call); both
 //      descriptors name the shared fields alike.  The caller binds the pointers and out_scale afterwards. ----
 struct ConvGeom {
@@ -128,14 +140,19 @@ struct DeferState {
     bool on = false;       // vgh_net_set_defer
     bool pending = false;  // the current generation's deferrable ops have not run
     int B = 0;             // images of that forward
+    bool towers = false;   // ... and neither have its tower-deferrable ops (tower_plan.h); never set without `pending`
+    int lanes = 1;         // batch lanes of that forward: the pending tower ops run on the same sub-batches, hence on the same tiles
     bool skip() const { return on; }  // does a forward queued now skip the deferrable ops?
-    void forward(int batch, bool skipped) {
+    void forward(int batch, bool skipped, bool skipped_towers = false, int batch_lanes = 1) {
         pending = skipped;
         B = skipped ? batch : 0;
+        towers = skipped && skipped_towers;
+        lanes = towers ? batch_lanes : 1;
     }
     int take() {  // the batch to run the deferred ops for, 0 = nothing pending; clears the mark
         const int b = pending ? B : 0;
         pending = false;
+        towers = false;
         B = 0;
         return b;
     }
@@ -153,6 +170,8 @@ struct NetPlan {
         int overhang_ok = 0;         // the K window is wider than the input buffer's pitch, over weight columns verified to be exactly zero
         int ev_done = 0;             // a later op names this one as its producer (vgh_op_desc.lane bits 8+): an event is recorded behind it
         int deferrable = 0;          // a prediction 1x1 conv whose fp32 rows only the post-network stages read (net_op_deferrable): a deferring forward skips it
+        int tower = 0;               // 1 + its tree: a 3x3 conv in front of deferrable convs whose output only they (or other such convs) read: skipped too (tower_plan.h fills it)
+        int writes_tower_root = 0;   // the op writes the root window of a tower tree (tower_plan.h)
     };
     std::vector<Op> ops;
     int64_t wds = -1;         // -DVGH_EXPERIMENTS builds: the stage-1 downsample's second weight image (stem_ds.hip), else -1

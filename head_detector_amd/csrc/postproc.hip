@@ -5,6 +5,7 @@
 // Reference: yolo_head_training/yolo_head/yolo_head_ndfl_heads.py:143-172 (decode + fix-up),
 // yolo_head_dfl_head.py:162-184 (activations, zero pad, channel order), yolo_heads.py:63-86 (top-k),
 // head_detector/utils.py:159-194 + torchvision.ops.nms (conf filter, NMS, keep-100).
+#include "per_device.h"
 #include "vgh_internal.h"
 
 namespace {
@@ -534,6 +535,147 @@ __global__ __launch_bounds__(256) void survivor_rows_kernel(const RowOps R, int 
     }
 }
 
+// ---- ... and from the ROOT of the FLAME towers, where the forward skipped the 3x3 towers in front of those convs as well (tower_plan.h) -------------------------
+// A survivor's prediction row depends on the (2 depth + 1)^2 window of the towers' root tensor around its anchor only.  One workgroup per survivor stages that
+// window in LDS (positions outside the map as zeros) and walks the level's tree: layer t turns tensor t - 1 into tensor t, one ring smaller, as bf16 in LDS -- and a
+// position of tensor t that lies outside the map is stored as ZERO, not as the value computed from padding: it is the next layer's zero padding.  The prediction
+// 1x1 convs then read the single pixel left, as survivor_rows_kernel does.
+// Bit for bit what the dense ops write.  Every 3x3 tile of the table issues the same v_mfma_f32_32x32x16_bf16 per (tap, 32-channel block, 16-channel half) with the
+// same eight channels per lane half; an output element depends on its weight row and pixel column only, so which pixels share an MFMA does not matter.  What does
+// differ between families is the ORDER of the (tap, channel block) pairs and where the bias enters (conv_tiles.h, kChainTrait): the op carries the code of the tile
+// the dense launch would have run on (vgh_tree_op::chain), resolved by the launcher's own rule for the pending forward.  Padding taps contribute exact zeros in both.
+// Cost: ~37 M MACs and ~4 MB of weights out of L2 per survivor on the L net; sized for a few hundred survivors per forward (one workgroup each, all resident at
+// once).  At capacity (B x keep_k survivors) the workgroups run in rounds of one per CU: the dense towers are cheaper there (vgh_detector_set_lazy_flame(d, 2)).
+struct TowerArgs {
+    Levels L;
+    vgh_tower_tree t[MAX_LEVELS];
+    int off[MAX_LEVELS][5];  // vgh_tower_lds
+};
+static_assert(sizeof(TowerArgs) <= 4000, "kernel arguments: 4 KB");
+
+// grid (keep_k, B), 512 threads: block (j, b) takes survivor j of image b and leaves at once when the image has fewer.  Lane & 31 = the pixel of the layer's output
+// window (in every wave), the eight waves share the (op, 32-cout tile, 32-pixel group) units of a layer.  Every barrier is reached by the whole block: the loop
+// bounds depend on the survivor's level alone.
+__global__ __launch_bounds__(512) void survivor_towers_kernel(const TowerArgs T, int n_in, int keep_k, const int32_t* __restrict__ idx, const int32_t* __restrict__ keep_idx,
+                                                              const int32_t* __restrict__ counts, int S, int E, float* __restrict__ out) {
+    extern __shared__ __attribute__((aligned(16))) char tw_smem[];
+    const int b = blockIdx.y, j = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kept = min(max(counts[b], 0), keep_k);
+    if (j >= kept) return;  // (block-uniform)
+    const Levels& L = T.L;
+    const int A = L.start[L.n];
+    const int pos = min(max(keep_idx[(int64_t)b * keep_k + j], 0), n_in - 1);
+    const int a = min(max(idx[(int64_t)b * n_in + pos], 0), A - 1);
+    const int l = __builtin_amdgcn_readfirstlane(find_level(L, a));
+    const int p = a - L.start[l];
+    const int H = L.h[l], W = L.w[l];
+    const int ay = p / W, ax = p - ay * W;
+    const vgh_tower_tree& t = T.t[l];
+    const int D = t.depth;
+    float* const row = (float*)(tw_smem + T.off[l][D + 1]);
+    {  // the root window, [2 D + 1]^2 pixels x root_c channels, 16 bytes at a time; the prediction row starts as zeros
+        const int side = 2 * D + 1, cpp = t.root_c >> 3, pitch = t.chan[0] + 8;
+        const uint16_t* const src = t.root + (int64_t)b * H * W * t.root_pitch + t.root_c0;
+        for (int i = tid; i < side * side * cpp; i += 512) {
+            const int px = i / cpp, ch = i - px * cpp;
+            const int wy = px / side, wx = px - wy * side;
+            const int iy = ay - D + wy, ix = ax - D + wx;
+            bf16x8_t v;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = (__bf16)0.0f;
+            if ((unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W) v = *(const bf16x8_t*)(src + ((int64_t)iy * W + ix) * t.root_pitch + ch * 8);
+            *(bf16x8_t*)(tw_smem + T.off[l][0] + ((int64_t)px * pitch + ch * 8) * 2) = v;
+        }
+        for (int i = tid; i < ROW_W; i += 512) row[i] = 0.0f;
+    }
+    __syncthreads();
+    const int n32 = lane & 31, hi = lane >> 5;
+    for (int lay = 1; lay <= D + 1; ++lay) {
+        const bool conv3 = lay <= D;
+        const int so = conv3 ? 2 * (D - lay) + 1 : 1, si = conv3 ? so + 2 : 1, npix = so * so, ngrp = (npix + 31) >> 5, taps = conv3 ? 9 : 1;
+        const int pin = t.chan[lay - 1] + 8;
+        const char* const xin = tw_smem + T.off[l][lay - 1];
+        int units = 0;
+        for (int k = 0; k < t.n_ops; ++k)
+            if (t.op[k].layer == lay) units += (t.op[k].cout_pad >> 5) * ngrp;
+        for (int u = w; u < units; u += 8) {  // (wave-uniform)
+            int k = 0, r = u;
+            while (true) {
+                const int n = t.op[k].layer == lay ? (t.op[k].cout_pad >> 5) * ngrp : 0;
+                if (r < n) break;
+                r -= n;
+                ++k;
+            }
+            const vgh_tree_op& o = t.op[k];
+            const int ct = r / ngrp, g = r - ct * ngrp;
+            const int px = g * 32 + n32;
+            const bool valid = px < npix;
+            const int oy = valid ? px / so : 0, ox = valid ? px - oy * so : 0;
+            const int co = ct * 32 + n32;  // this lane's weight row of the A fragments
+            const int in_coff = o.in_coff + (o.grp_cout ? (ct * 32 / o.grp_cout) * o.grp_in_stride : 0);
+            const uint16_t* const wr = o.wpack + (int64_t)co * 32;
+            const int sw = (co >> 2) & 3;  // the packed image stores logical 16-byte chunk c of a row in slot c ^ ((row >> 2) & 3)
+            const bool tap_major = (o.chain & 1) || !conv3, bias_first = (o.chain & 2) && conv3;
+            f32x16_t acc;
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[q * 4 + e] = bias_first ? o.bias[ct * 32 + q * 8 + hi * 4 + e] : 0.0f;  // accumulator register 4 q + e of lane (pixel, half hi)
+            const int nk = taps * o.cblocks;
+            for (int s = 0; s < nk; ++s) {
+                int tap, cb;
+                if (tap_major) {
+                    tap = s / o.cblocks;
+                    cb = s - tap * o.cblocks;
+                } else {
+                    cb = s / 9;
+                    tap = s - cb * 9;
+                }
+                const int ky = tap / 3, kx = tap - ky * 3;
+                const char* const xr = xin + ((int64_t)((oy + ky) * si + ox + kx) * pin + in_coff + cb * 32 + hi * 8) * 2;
+                const uint16_t* const wk = wr + (int64_t)(tap * o.cblocks + cb) * o.cout_pad * 32;
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const bf16x8_t af = *(const bf16x8_t*)(wk + ((2 * h + hi) ^ sw) * 8);
+                    bf16x8_t bf;
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) bf[e] = (__bf16)0.0f;
+                    if (valid) bf = *(const bf16x8_t*)(xr + h * 32);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf, acc, 0, 0, 0);
+                }
+            }
+            const float act_lo = o.act == VGH_ACT_RELU ? 0.0f : __builtin_nanf("");  // (conv_kernels.inc, act_bound)
+            if (conv3) {
+                const int my = ay - (D - lay) + oy, mx = ax - (D - lay) + ox;
+                const bool inside = (unsigned)my < (unsigned)H && (unsigned)mx < (unsigned)W;
+                char* const xo = tw_smem + T.off[l][lay] + ((int64_t)px * (t.chan[lay] + 8) + o.out_coff) * 2;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int c = ct * 32 + q * 8 + hi * 4;
+                    bf16x4_t v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = (__bf16)(inside ? fmaxf(bias_first ? acc[q * 4 + e] : acc[q * 4 + e] + o.bias[c + e], act_lo) : 0.0f);
+                    if (valid && c < o.cout_store) *(bf16x4_t*)(xo + c * 2) = v;  // (cout_store is a multiple of 4: vgh_conv_prepare)
+                }
+            } else {
+                const int oc = o.out_coff - VGH_PRED_FLAME_OFF;
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int c = ct * 32 + q * 8 + hi * 4 + e;
+                        if (n32 == 0 && c < o.cout_store) row[oc + c] = fmaxf(acc[q * 4 + e] + o.bias[c], act_lo);
+                    }
+            }
+        }
+        __syncthreads();
+    }
+    const float st = (float)L.stride[l];
+    const int64_t orow = (int64_t)b * keep_k + j;
+    for (int c = tid; c < VGH_NUM_FLAME_PARAMS; c += 512) out[orow * VGH_NUM_FLAME_PARAMS + c] = flame_channel(row, c, S, E, ax, ay, st);
+}
+
 int make_levels(const vgh_head_level* levels, int n_levels, Levels* L) {
     VGH_REQUIRE(n_levels >= 1 && n_levels <= MAX_LEVELS, "head: n_levels=%d out of range", n_levels);
     L->n = n_levels;
@@ -657,6 +799,29 @@ int vgh_survivor_rows(const vgh_head_level* levels, int n_levels, const vgh_row_
     if (B == 0) return VGH_OK;
     hipLaunchKernelGGL(survivor_rows_kernel, dim3((keep_k + 31) / 32, B), dim3(256), 0, (hipStream_t)stream, R, n_in, keep_k, idx_dev, keep_idx_dev, counts_dev, shape_c, expr_c,
                        out_dev);
+    VGH_HIP(hipGetLastError());
+    return VGH_OK;
+}
+
+int vgh_survivor_towers(const vgh_head_level* levels, int n_levels, const vgh_tower_tree* trees, int B, int n_in, int keep_k, const int32_t* idx_dev,
+                        const int32_t* keep_idx_dev, const int32_t* counts_dev, int shape_c, int expr_c, float* out_dev, void* stream) {
+    VGH_REQUIRE(levels && trees && idx_dev && keep_idx_dev && counts_dev && out_dev, "survivor_towers: null argument");
+    VGH_REQUIRE(n_in >= 1 && keep_k >= 1 && keep_k <= n_in && keep_k <= 65535 && B <= 65535, "survivor_towers: n_in=%d / keep_k=%d / B=%d", n_in, keep_k, B);
+    VGH_REQUIRE(shape_c >= 0 && shape_c <= 300 && expr_c >= 0 && expr_c <= 100, "survivor_towers: bad live channel counts");
+    TowerArgs T;
+    memset(&T, 0, sizeof(T));
+    if (int rc = make_levels(levels, n_levels, &T.L)) return rc;
+    int lds = 0;
+    for (int l = 0; l < n_levels; ++l) {
+        VGH_REQUIRE(vgh_tower_tree_ok(trees[l], shape_c + expr_c + 13), "survivor_towers: the tree of level %d cannot be walked per survivor", l);
+        T.t[l] = trees[l];
+        const int bytes = vgh_tower_lds(trees[l], T.off[l]);
+        lds = bytes > lds ? bytes : lds;
+    }
+    if (B == 0) return VGH_OK;
+    static PerDevice opted_in;  // (the largest walk vgh_tower_tree_ok admits: one opt-in per device serves every tree)
+    if (lds > 64 * 1024) VGH_HIP(opt_in_dynamic_lds(opted_in, 144 * 1024, survivor_towers_kernel));
+    hipLaunchKernelGGL(survivor_towers_kernel, dim3(keep_k, B), dim3(512), lds, (hipStream_t)stream, T, n_in, keep_k, idx_dev, keep_idx_dev, counts_dev, shape_c, expr_c, out_dev);
     VGH_HIP(hipGetLastError());
     return VGH_OK;
 }

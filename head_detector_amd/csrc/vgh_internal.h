@@ -112,6 +112,8 @@ int vgh_conv_prepare(ConvArgs& a);
 // automatic tile of a PREPARED descriptor: index into the bf16 table (a.split == 0) or into conv_split.hip's table
 int vgh_conv_pick_auto(const ConvArgs& a);
 int vgh_conv_split_pick(const ConvArgs& a);
+// the summation chain (conv_tiles.h, chain_code) of the tile that vgh_launch_conv(a, force_cfg) runs this bf16 conv on; -1: a family whose chain nothing else reproduces
+int vgh_conv_chain(const ConvArgs& a, int force_cfg);
 // host-side weight packing: dense [cout_pad][ks][ks][cin] f32 -> wpack bf16 image
 void vgh_pack_conv_weights_host(const float* w, int cout_pad, int ksize, int cin, uint16_t* dst);
 // the packing loop of every 16-bit weight image: dense [cout_pad][ks][ks][cin] -> dst[kb][cout][slot][8] with slot = chunk ^ ((cout>>2)&3), kb = (ky*ks + kx)*(cin/32) + cb,
@@ -205,6 +207,68 @@ extern "C" __attribute__((visibility("hidden"))) int vgh_net_row_ops(vgh_net* n,
 // out_dev [B, keep_k, 413]: the fixed-up vectors (gather_kernel's arithmetic); rows at and past the count are not written
 int vgh_survivor_rows(const vgh_head_level* levels, int n_levels, const vgh_row_op* ops /*[n_levels][kMaxRowOps]*/, const int* n_ops, int B, int n_in, int keep_k,
                       const int32_t* idx_dev, const int32_t* keep_idx_dev, const int32_t* counts_dev, int shape_c, int expr_c, float* out_dev, void* stream);
+
+// ---- deferred FLAME towers: the 3x3 convs in front of the deferred prediction convs (tower_plan.h), walked per survivor by postproc.hip ----
+constexpr int kMaxTreeOps = 12;  // tower ops (kMaxTowerOps) + prediction convs (kMaxRowOps) of one level
+struct vgh_tree_op {
+    const uint16_t* wpack;  // packed weights, [tap * cblocks + cb][cout_pad][32]
+    const float* bias;      // [cout_pad]
+    int layer;              // 1 .. depth: a 3x3 conv from tensor layer - 1 to tensor layer; depth + 1: a prediction 1x1 conv from tensor depth to the fp32 row
+    int in_coff, cblocks, cout_pad, cout_store, out_coff, act;  // out_coff: channel of the output tensor / of the prediction row
+    int grp_cout, grp_in_stride;  // grouped conv (0: dense): cout group g reads the input window at in_coff + g * grp_in_stride
+    int chain;              // conv_tiles.h chain_code of the tile the dense op would have run on (bit 0 tap-major, bit 1 bias first); prediction convs: 1
+};
+struct vgh_tower_tree {
+    const uint16_t* root;   // bf16 root tensor, batch row 0
+    int root_pitch, root_c0, root_c;  // its pitch and the channel window [c0, c0 + c) the first layer reads
+    int depth;              // 3x3 layers: the root window of a survivor is (2 depth + 1)^2 pixels
+    int chan[4];            // channels of tensor t as kept per survivor (t = 0: root_c; t >= 1: the pitch of the layer's buffer)
+    int n_ops;
+    vgh_tree_op op[kMaxTreeOps];  // program order: layers ascend, prediction convs last
+};
+// LDS of a survivor's walk: tensor t (t = 0 .. depth) as [(2 (depth - t) + 1)^2 pixels][chan[t] + 8] bf16 (8 channels of padding per pixel keep the 16-byte fragment
+// reads of neighbouring pixels on different banks), then the fp32 prediction row.  off[t]: byte offset of tensor t, off[depth + 1]: of the row; returns the total
+static inline int vgh_tower_lds(const vgh_tower_tree& t, int* off) {
+    int at = 0;
+    for (int l = 0; l <= t.depth; ++l) {
+        const int side = 2 * (t.depth - l) + 1;
+        if (off) off[l] = at;
+        at += (side * side * (t.chan[l] + 8) * 2 + 15) / 16 * 16;
+    }
+    if (off) off[t.depth + 1] = at;
+    return at + 416 * 4;
+}
+// what the survivor kernel asks of a tree: windows inside their tensors, 16-byte aligned fragment reads, whole 32-cout weight tiles, the prediction convs inside the
+// `width` FLAME channels of the row, and a walk that fits the LDS of a workgroup
+static inline bool vgh_tower_tree_ok(const vgh_tower_tree& t, int width) {
+    if (!t.root || t.depth < 1 || t.depth > 3 || t.n_ops < 2 || t.n_ops > kMaxTreeOps || t.root_pitch % 8 || t.root_c0 % 8 || t.root_c < 32 || t.root_c % 8 || t.root_c0 + t.root_c > t.root_pitch) return false;
+    for (int l = 0; l <= t.depth; ++l)
+        if (t.chan[l] < 32 || t.chan[l] % 8) return false;
+    int last = 1;
+    for (int k = 0; k < t.n_ops; ++k) {
+        const vgh_tree_op& o = t.op[k];
+        if (!o.wpack || !o.bias || o.layer < last || o.layer > t.depth + 1 || o.cblocks < 1 || o.cout_pad < 32 || o.cout_pad % 32 || o.cout_store < 1 || o.cout_store > o.cout_pad) return false;
+        if (o.chain < 0 || o.chain > 3 || o.act == VGH_ACT_SILU || o.in_coff < 0 || o.in_coff % 8 || o.grp_in_stride % 8 || o.grp_in_stride < 0) return false;
+        if (o.grp_cout && (o.grp_cout % 32 || o.cout_pad % o.grp_cout)) return false;
+        const int groups = o.grp_cout ? o.cout_pad / o.grp_cout : 1;
+        if (o.in_coff + (groups - 1) * o.grp_in_stride + 32 * o.cblocks > t.chan[o.layer - 1]) return false;
+        if (o.layer <= t.depth) {
+            if (o.out_coff < 0 || o.out_coff + o.cout_store > t.chan[o.layer]) return false;
+        } else if (o.grp_cout || o.out_coff < VGH_PRED_FLAME_OFF || o.out_coff - VGH_PRED_FLAME_OFF + o.cout_store > width || width > 413) {
+            return false;
+        }
+        last = o.layer;
+    }
+    return last == t.depth + 1 && vgh_tower_lds(t, nullptr) <= 144 * 1024;
+}
+// net.hip: the tree in front of prediction buffer `out_buf` with the chains of the forward that left it pending; 0 and *t filled, or -1: no tree, nothing pending, or an
+// op of it on a tile whose chain is unknown (the caller then runs the pending ops densely)
+extern "C" __attribute__((visibility("hidden"))) int vgh_net_tower_tree(vgh_net* n, int out_buf, vgh_tower_tree* t);
+// 1: the latest forward left tower ops pending (it skipped them), 0: it ran them or only the prediction convs are pending
+extern "C" __attribute__((visibility("hidden"))) int vgh_net_towers_pending(vgh_net* n);
+// postproc.hip: as vgh_survivor_rows, from the root windows: one workgroup per survivor walks its level's tree
+int vgh_survivor_towers(const vgh_head_level* levels, int n_levels, const vgh_tower_tree* trees /*[n_levels]*/, int B, int n_in, int keep_k, const int32_t* idx_dev,
+                        const int32_t* keep_idx_dev, const int32_t* counts_dev, int shape_c, int expr_c, float* out_dev, void* stream);
 
 // letterbox.hip: the batched letterbox of VGH_IMG_U8_RAW / VGH_IMG_YUV420_RAW, owned by a detector (canvas [arena_batch, S, S, 3] + two pinned / device staging slots)
 struct vgh_lb_batch;
