@@ -15,6 +15,8 @@ VGH_OP_STEM, VGH_OP_CONV, VGH_OP_SPP_POOL, VGH_OP_FORK = 0, 1, 2, 3
 VGH_ACT_NONE, VGH_ACT_RELU, VGH_ACT_SILU = 0, 1, 2
 VGH_IMG_F32_NCHW, VGH_IMG_U8_NHWC, VGH_IMG_U8_RAW, VGH_IMG_YUV420_RAW = 0, 1, 2, 3
 RAW_FORMATS = (VGH_IMG_U8_RAW, VGH_IMG_YUV420_RAW)  # `images_dev` is a HOST array of descriptors; letterboxed on the device by vgh_detect
+VGH_IMG_YUV420P16_RAW = 4  # 10- / 12-bit frames in 16-bit words: added within ABI 8, like format 3
+DESCRIPTOR_FORMATS = RAW_FORMATS + (VGH_IMG_YUV420P16_RAW,)  # every format whose `images_dev` is a HOST array of descriptors
 VGH_FMT_BF16, VGH_FMT_F32, VGH_FMT_BF16X2, VGH_FMT_F16X2, VGH_FMT_FP8, VGH_FMT_F16, VGH_FMT_I8 = 0, 1, 2, 3, 4, 5, 6
 NUM_FLAME_PARAMS = 413
 
@@ -70,6 +72,14 @@ class Yuv420Image(C.Structure):
     _fields_ = [("y_dev", C.c_void_p), ("u_dev", C.c_void_p), ("v_dev", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("y_pitch_bytes", C.c_int64),
                 ("uv_pitch_bytes", C.c_int64), ("chroma_step", C.c_int32), ("y_offset", C.c_int32), ("cy", C.c_int32), ("crv", C.c_int32), ("cgu", C.c_int32),
                 ("cgv", C.c_int32), ("cbu", C.c_int32)]
+
+
+class Yuv420P16Image(C.Structure):
+    """vgh_yuv420p16_image: one 10- or 12-bit YUV 4:2:0 frame of a VGH_IMG_YUV420P16_RAW batch, 16-bit words (the conversion rule is stated in include/vgh.h);
+    ``chroma_step`` and both pitches in BYTES."""
+    _fields_ = [("y_dev", C.c_void_p), ("u_dev", C.c_void_p), ("v_dev", C.c_void_p), ("h", C.c_int32), ("w", C.c_int32), ("y_pitch_bytes", C.c_int64),
+                ("uv_pitch_bytes", C.c_int64), ("chroma_step", C.c_int32), ("bit_depth", C.c_int32), ("shift", C.c_int32), ("y_offset", C.c_int32), ("cy", C.c_int32),
+                ("crv", C.c_int32), ("cgu", C.c_int32), ("cgv", C.c_int32), ("cbu", C.c_int32)]
 
 
 class HeadLevel(C.Structure):

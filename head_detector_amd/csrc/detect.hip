@@ -229,9 +229,10 @@ void vgh_detector_destroy(vgh_detector* d) {
 int vgh_detector_candidates(vgh_detector* d, const void* images_dev, int image_fmt, int B, void* stream) {
     VGH_REQUIRE(d && images_dev, "detector_candidates: null argument");
     VGH_REQUIRE(B >= 1 && B <= d->cfg.max_batch, "detector_candidates: batch %d outside 1..%d", B, d->cfg.max_batch);
-    VGH_REQUIRE(image_fmt == VGH_IMG_F32_NCHW || image_fmt == VGH_IMG_U8_NHWC || image_fmt == VGH_IMG_U8_RAW || image_fmt == VGH_IMG_YUV420_RAW,
+    VGH_REQUIRE(image_fmt == VGH_IMG_F32_NCHW || image_fmt == VGH_IMG_U8_NHWC || image_fmt == VGH_IMG_U8_RAW || image_fmt == VGH_IMG_YUV420_RAW ||
+                    image_fmt == VGH_IMG_YUV420P16_RAW,
                 "detector_candidates: unknown image format %d", image_fmt);
-    const bool raw = image_fmt == VGH_IMG_U8_RAW || image_fmt == VGH_IMG_YUV420_RAW;  // images_dev: HOST array of B vgh_raw_image / vgh_yuv420_image
+    const bool raw = image_fmt == VGH_IMG_U8_RAW || image_fmt == VGH_IMG_YUV420_RAW || image_fmt == VGH_IMG_YUV420P16_RAW;  // images_dev: HOST array of B vgh_raw_image / vgh_yuv420_image / vgh_yuv420p16_image
     if (raw)
         if (int rc = vgh_lb_prepare(&d->lb, d->S, d->cfg.max_batch, d->arena_batch, image_fmt, images_dev, B)) return rc;
     const int fmt = raw ? VGH_IMG_U8_NHWC : image_fmt;  // RAW: the network reads the letterboxed canvas

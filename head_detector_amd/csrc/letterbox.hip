@@ -8,6 +8,7 @@
 // PARITY UNPINNED against cv2 itself (absent from this image); bit-exact against oracle/letterbox_oracle.py.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <map>
 #include <new>
 #include <vector>
@@ -77,6 +78,37 @@ struct LbYuvImage : LbGeom {
     }
 };
 
+// Deep YUV 4:2:0 (VGH_IMG_YUV420P16_RAW: 10 or 12 significant bits in 16-bit words): LbYuvImage's fetch with 16-bit loads, a shift and a mask in front of the rule of
+// include/vgh.h (vgh_yuv420p16_image); the tap is clamped to BYTES before it is weighted, so everything behind the fetch is the 8-bit path.  The host half
+// (set_source) has turned the descriptor's depth into mask / half / round / rshift and its chroma step into words; pointers and pitches are even (check_source), so
+// every load is an aligned 16-bit load.  Chroma coordinates derive from the CLAMPED luma coordinates, as above.
+typedef const __attribute__((address_space(1))) uint16_t* gwords;
+
+struct LbYuv16Image : LbGeom {
+    const uint16_t *y, *u, *v;
+    int64_t y_pitch, uv_pitch;  // bytes
+    int32_t chroma_step;        // WORDS between chroma samples of a row: 1 or 2
+    int32_t shift, mask, half, round, rshift;  // sample = (word >> shift) & mask; half = 2^(D-1), round = 2^(D+7), rshift = D + 8
+    int32_t y_offset, cy, crv, cgu, cgv, cbu;
+    struct Row {
+        gwords y, u, v;
+    };
+    __device__ __forceinline__ int col(int x) const { return x; }
+    __device__ __forceinline__ Row row(int yy) const {
+        const size_t c = (size_t)(yy >> 1) * uv_pitch;
+        return Row{(gwords)((gbytes)gmem(y) + (size_t)yy * y_pitch), (gwords)((gbytes)gmem(u) + c), (gwords)((gbytes)gmem(v) + c)};
+    }
+    __device__ __forceinline__ void tap(const Row& p, int x, int& r, int& g, int& b) const {
+        const int cx = (x >> 1) * chroma_step;
+        const int yv = ((int)p.y[x] >> shift) & mask, uv = ((int)p.u[cx] >> shift) & mask, vv = ((int)p.v[cx] >> shift) & mask;
+        const int l = cy * (yv - y_offset) + round, d = uv - half, e = vv - half;
+        // as in LbYuvImage: each channel shifted and clamped into an int of its own, no clamp-and-pack chain (see the note at the end of letterbox_pixel)
+        r = min(max((l + crv * e) >> rshift, 0), 255);
+        g = min(max((l + cgu * d + cgv * e) >> rshift, 0), 255);
+        b = min(max((l + cbu * d) >> rshift, 0), 255);
+    }
+};
+
 // Canvas pixel (x, y) as r | g << 8 | b << 16: the per-pixel arithmetic of ALL letterbox kernels (they cannot drift apart); generic over the tap fetch.
 template <typename Img>
 __device__ __forceinline__ uint32_t letterbox_pixel(const Img& a, int x, int y) {
@@ -129,7 +161,7 @@ __global__ __launch_bounds__(256) void letterbox_kernel(LbImage a, uint8_t* dst,
     o[2] = (uint8_t)(rgb >> 16);
 }
 
-// VGH_IMG_U8_RAW / VGH_IMG_YUV420_RAW: every image of an arena chunk in one launch, canvas [n, S, S, 3]; one instantiation per source format (a call has ONE format,
+// VGH_IMG_U8_RAW / VGH_IMG_YUV420_RAW / VGH_IMG_YUV420P16_RAW: every image of an arena chunk in one launch, canvas [n, S, S, 3]; one instantiation per source format (a call has ONE format,
 // so no lane branches on it).  blockIdx.z = image (its descriptor is wave-uniform: scalar loads); one pixel per lane as in letterbox_kernel.  The RGB kernel is bound
 // by the 128 byte gathers per pixel, not by its stores: four pixels per lane with one 3-dword store measured 1.70 ms per 64 mixed photographs against 1.16 ms for this
 // form (profiles/raw_letterbox_l64.txt).
@@ -173,9 +205,9 @@ extern "C" int vgh_letterbox(const uint8_t* src_dev, int src_h, int src_w, int s
     return VGH_OK;
 }
 
-// ---- VGH_IMG_U8_RAW / VGH_IMG_YUV420_RAW: the detector's batched letterbox (include/vgh.h, vgh_detect) -------------------------------------
+// ---- VGH_IMG_U8_RAW / VGH_IMG_YUV420_RAW / VGH_IMG_YUV420P16_RAW: the detector's batched letterbox (include/vgh.h, vgh_detect) -------------------------------------
 // The host validates the B descriptors, builds (or finds in its cache) the per-axis tables and packs, for every arena chunk, the chunk's
-// LbImage (or LbYuvImage) descriptors and tables into a pinned staging slot: ONE async copy and ONE letterbox_batch_kernel launch per chunk.  The first slot
+// LbImage (or LbYuvImage, or LbYuv16Image) descriptors and tables into a pinned staging slot: ONE async copy and ONE letterbox_batch_kernel launch per chunk.  The first slot
 // region also holds the un-pad table [max_batch, 3] of the whole call, so it travels with the first chunk's copy.
 //
 // Two slots, alternating per call.  A slot is free again once its last device reader has run: the letterbox launches of its call (on the
@@ -223,9 +255,9 @@ int lb_create(int S, int max_batch, int arena_batch, vgh_lb_batch** out) {
     lb->S = S;
     lb->max_batch = max_batch;
     lb->arena_batch = arena_batch;
-    // per image at most one descriptor (the larger of the two source formats') + 16 bytes of descriptor region and two axes of <= S entries (4 + 16 bytes, 16-byte
-    // aligned): a slot serves either format, so nothing is allocated when the format changes between calls
-    const size_t desc_bytes = sizeof(LbImage) > sizeof(LbYuvImage) ? sizeof(LbImage) : sizeof(LbYuvImage);
+    // per image at most one descriptor (the largest of the three source formats') + 16 bytes of descriptor region and two axes of <= S entries (4 + 16 bytes, 16-byte
+    // aligned): a slot serves every format, so nothing is allocated when the format changes between calls
+    const size_t desc_bytes = std::max({sizeof(LbImage), sizeof(LbYuvImage), sizeof(LbYuv16Image)});
     lb->slot_bytes = align16((size_t)max_batch * 12) + (size_t)max_batch * (desc_bytes + 16 + 2 * (align16((size_t)4 * S) + (size_t)16 * S));
     const size_t canvas_bytes = (size_t)arena_batch * S * S * 3;
     bool ok = hipMalloc((void**)&lb->canvas, canvas_bytes) == hipSuccess;
@@ -267,6 +299,26 @@ void set_source(LbYuvImage& a, const vgh_yuv420_image& im) {
     a.cbu = im.cbu;
 }
 
+void set_source(LbYuv16Image& a, const vgh_yuv420p16_image& im) {
+    a.y = im.y_dev;
+    a.u = im.u_dev;
+    a.v = im.v_dev;
+    a.y_pitch = im.y_pitch_bytes;
+    a.uv_pitch = im.uv_pitch_bytes;
+    a.chroma_step = im.chroma_step / 2;  // bytes -> words
+    a.shift = im.shift;
+    a.mask = (1 << im.bit_depth) - 1;
+    a.half = 1 << (im.bit_depth - 1);
+    a.round = 1 << (im.bit_depth + 7);
+    a.rshift = im.bit_depth + 8;
+    a.y_offset = im.y_offset;
+    a.cy = im.cy;
+    a.crv = im.crv;
+    a.cgu = im.cgu;
+    a.cgv = im.cgv;
+    a.cbu = im.cbu;
+}
+
 int check_source(const vgh_raw_image& im, int i) {
     VGH_REQUIRE(im.data_dev, "detector_candidates: image %d: null data_dev", i);
     VGH_REQUIRE(im.h >= 1 && im.w >= 1, "detector_candidates: image %d: empty (%d x %d)", i, im.h, im.w);
@@ -289,6 +341,27 @@ int check_source(const vgh_yuv420_image& im, int i) {
     static const char* const names[5] = {"cy", "crv", "cgu", "cgv", "cbu"};
     for (int k = 0; k < 5; ++k)
         VGH_REQUIRE(coef[k] >= -(1 << 20) && coef[k] <= (1 << 20), "detector_candidates: image %d: coefficient %s = %d outside +-2^20", i, names[k], coef[k]);
+    return VGH_OK;
+}
+
+int check_source(const vgh_yuv420p16_image& im, int i) {
+    VGH_REQUIRE(im.y_dev && im.u_dev && im.v_dev, "detector_candidates: image %d: null plane (y_dev, u_dev and v_dev are all needed)", i);
+    VGH_REQUIRE(im.h >= 1 && im.w >= 1, "detector_candidates: image %d: empty (%d x %d)", i, im.h, im.w);
+    VGH_REQUIRE((((uintptr_t)im.y_dev | (uintptr_t)im.u_dev | (uintptr_t)im.v_dev) & 1) == 0, "detector_candidates: image %d: odd plane pointer (y_dev, u_dev and v_dev address 16-bit words)", i);
+    VGH_REQUIRE(im.chroma_step == 2 || im.chroma_step == 4, "detector_candidates: image %d: chroma_step %d bytes (2 = planar, 4 = interleaved)", i, im.chroma_step);
+    VGH_REQUIRE((im.y_pitch_bytes & 1) == 0 && im.y_pitch_bytes >= 2 * (int64_t)im.w, "detector_candidates: image %d: y_pitch_bytes %lld is odd or < 2 * w = %lld", i,
+                (long long)im.y_pitch_bytes, 2 * (long long)im.w);
+    const int64_t crow = (int64_t)im.chroma_step * (((int64_t)im.w + 1) / 2);
+    VGH_REQUIRE((im.uv_pitch_bytes & 1) == 0 && im.uv_pitch_bytes >= crow, "detector_candidates: image %d: uv_pitch_bytes %lld is odd or < chroma_step * ((w + 1) / 2) = %lld", i,
+                (long long)im.uv_pitch_bytes, (long long)crow);
+    VGH_REQUIRE(im.bit_depth == 10 || im.bit_depth == 12, "detector_candidates: image %d: bit_depth %d (10 or 12)", i, im.bit_depth);
+    VGH_REQUIRE(im.shift >= 0 && im.shift <= 16 - im.bit_depth, "detector_candidates: image %d: shift %d outside 0..%d (16 - bit_depth)", i, im.shift, 16 - im.bit_depth);
+    VGH_REQUIRE(im.y_offset >= 0 && im.y_offset < (1 << im.bit_depth), "detector_candidates: image %d: y_offset %d outside 0..%d", i, im.y_offset, (1 << im.bit_depth) - 1);
+    VGH_REQUIRE(im.cy >= 0 && im.cy <= (1 << 17), "detector_candidates: image %d: coefficient cy = %d outside 0..2^17", i, im.cy);
+    const int32_t coef[4] = {im.crv, im.cgu, im.cgv, im.cbu};
+    static const char* const names[4] = {"crv", "cgu", "cgv", "cbu"};
+    for (int k = 0; k < 4; ++k)
+        VGH_REQUIRE(coef[k] >= -(1 << 18) && coef[k] <= (1 << 18), "detector_candidates: image %d: coefficient %s = %d outside +-2^18", i, names[k], coef[k]);
     return VGH_OK;
 }
 
@@ -364,6 +437,7 @@ void launch_batch(const vgh_lb_batch* lb, int k, int chunk, int n, hipStream_t s
 
 int vgh_lb_prepare(vgh_lb_batch** plb, int S, int max_batch, int arena_batch, int image_fmt, const void* imgs, int B) {
     if (image_fmt == VGH_IMG_YUV420_RAW) return lb_prepare<LbYuvImage>(plb, S, max_batch, arena_batch, image_fmt, (const vgh_yuv420_image*)imgs, B);
+    if (image_fmt == VGH_IMG_YUV420P16_RAW) return lb_prepare<LbYuv16Image>(plb, S, max_batch, arena_batch, image_fmt, (const vgh_yuv420p16_image*)imgs, B);
     VGH_REQUIRE(image_fmt == VGH_IMG_U8_RAW, "letterbox: image format %d is not a raw format", image_fmt);
     return lb_prepare<LbImage>(plb, S, max_batch, arena_batch, image_fmt, (const vgh_raw_image*)imgs, B);
 }
@@ -375,6 +449,8 @@ int vgh_lb_chunk(vgh_lb_batch* lb, int chunk, int n, hipStream_t stream) {
     VGH_HIP(hipMemcpyAsync(lb->dev[k] + from, lb->host[k] + from, to - from, hipMemcpyHostToDevice, stream));
     if (lb->fmt == VGH_IMG_YUV420_RAW)
         launch_batch<LbYuvImage>(lb, k, chunk, n, stream);
+    else if (lb->fmt == VGH_IMG_YUV420P16_RAW)
+        launch_batch<LbYuv16Image>(lb, k, chunk, n, stream);
     else
         launch_batch<LbImage>(lb, k, chunk, n, stream);
     VGH_HIP(hipGetLastError());

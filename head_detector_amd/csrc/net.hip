@@ -398,7 +398,7 @@ static void pack_weights(const NetPlan& plan, const vgh_buf_desc* bufs, const vg
 
 // a network runs on a canvas; `who` names the entry point in the message
 static int require_canvas(const char* who, int image_fmt) {
-    VGH_REQUIRE(image_fmt == VGH_IMG_F32_NCHW || image_fmt == VGH_IMG_U8_NHWC, "%s: image format %d is not a canvas (VGH_IMG_U8_RAW and VGH_IMG_YUV420_RAW are letterboxed by vgh_detect)", who, image_fmt);
+    VGH_REQUIRE(image_fmt == VGH_IMG_F32_NCHW || image_fmt == VGH_IMG_U8_NHWC, "%s: image format %d is not a canvas (VGH_IMG_U8_RAW, VGH_IMG_YUV420_RAW and VGH_IMG_YUV420P16_RAW are letterboxed by vgh_detect)", who, image_fmt);
     return VGH_OK;
 }
 

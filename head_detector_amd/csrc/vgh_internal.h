@@ -270,7 +270,7 @@ extern "C" __attribute__((visibility("hidden"))) int vgh_net_towers_pending(vgh_
 int vgh_survivor_towers(const vgh_head_level* levels, int n_levels, const vgh_tower_tree* trees /*[n_levels]*/, int B, int n_in, int keep_k, const int32_t* idx_dev,
                         const int32_t* keep_idx_dev, const int32_t* counts_dev, int shape_c, int expr_c, float* out_dev, void* stream);
 
-// letterbox.hip: the batched letterbox of VGH_IMG_U8_RAW / VGH_IMG_YUV420_RAW, owned by a detector (canvas [arena_batch, S, S, 3] + two pinned / device staging slots)
+// letterbox.hip: the batched letterbox of VGH_IMG_U8_RAW / VGH_IMG_YUV420_RAW / VGH_IMG_YUV420P16_RAW, owned by a detector (canvas [arena_batch, S, S, 3] + two pinned / device staging slots)
 struct vgh_lb_batch;
 // Validates the B descriptors (VGH_ERR_INVALID naming the image; nothing allocated or queued) and packs their tables + the un-pad table into the
 // next staging slot; *lb (NULL before the first RAW call) is created here.

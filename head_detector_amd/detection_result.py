@@ -34,7 +34,7 @@ class PredictionResult:
     def __init__(self, original_image: np.ndarray, heads: List[HeadMetadata], faces: Optional[np.ndarray] = None, pncc_processor=None, *,
                  head_indices: Optional[np.ndarray] = None, triangles: Optional[np.ndarray] = None, face_indices: Optional[np.ndarray] = None, source_frame=None):
         self.original_image = original_image  # (None for a frame input with rgb="none": no RGB copy was made)
-        self.source_frame = source_frame  # the video.YUV420Frame the result was made from, or None (an RGB input)
+        self.source_frame = source_frame  # the video.YUV420Frame / YUV420Frame16 the result was made from, or None (an RGB input)
         self.heads = heads
         self._faces = faces  # [F,3] 0-based triangle indices of the FLAME mesh
         self.pncc_processor = pncc_processor  # head_detector_amd.pncc.PNCCProcessor or None (no mesh assets supplied)
@@ -78,11 +78,13 @@ class PredictionResult:
         """``video.anonymize_frame(self.source_frame, self.heads, ...)``: every head hidden directly in the luma and chroma planes of the YUV 4:2:0 frame the
         result was made from (csrc/yuv_anonymize.hip, libvghvideo.so), with the keywords of ``anonymize``; no RGB image is made or needed (``rgb="none"``).
         ``out=None``: a new frame; ``out=self.source_frame``: in place; another ``video.YUV420Frame`` of the same size: written whole.  Returns the frame
-        written.  ValueError if the result was not made from a frame: use ``anonymize()`` then."""
+        written.  ValueError if the result was not made from a frame: use ``anonymize()`` then; and if the frame is a deep ``video.YUV420Frame16``: pass
+        ``source_frame.to_8bit()`` to ``video.anonymize_frame``."""
         if self.source_frame is None:
             raise ValueError("anonymize_frame: this result was not made from a video.YUV420Frame (source_frame is None); use anonymize() on its RGB original_image")
-        from .video import anonymize_frame
+        from .video import anonymize_frame, require_8bit_frame
 
+        require_8bit_frame("anonymize_frame", self.source_frame)
         return anonymize_frame(self.source_frame, self.heads, method, region, margin=margin, cells=cells, strength=strength, color=color,
                                faces=self._faces if faces is None else faces, out=out)
 
@@ -159,11 +161,19 @@ class PredictionResult:
         model ([n, 3, size, size] float32 by default; csrc/head_tensors.hip, libvghcrop.so), with the matrices back to image coordinates.  The source is the
         ``source_frame`` if the result was made from a video frame (its YUV planes are used where they are: ``original_image`` may be None), otherwise the
         ``original_image``.  ``aligned=True`` (the default: the geometry of ``get_aligned_heads``) needs ``head_indices`` -- the result's own unless given;
-        ``aligned=False`` needs no asset.  Keywords and errors: ``head_tensors.head_tensors``."""
+        ``aligned=False`` needs no asset.  A deep ``video.YUV420Frame16`` is not a source: the ``original_image`` is used, and without one (``rgb="none"``) a
+        ValueError names ``source_frame.to_8bit()``.  Keywords and errors: ``head_tensors.head_tensors``."""
         from .head_tensors import head_tensors
 
+        from .video import YUV420Frame16, require_8bit_frame
+
         kw.setdefault("head_indices", self.head_indices)
-        return head_tensors(self.source_frame if self.source_frame is not None else self.original_image, self.heads, size, **kw)
+        source = self.source_frame
+        if isinstance(source, YUV420Frame16):  # the crops are cut from 8-bit planes: the RGB original if there is one
+            if self.original_image is None:
+                require_8bit_frame("get_head_tensors", source)
+            source = None
+        return head_tensors(source if source is not None else self.original_image, self.heads, size, **kw)
 
     def draw_overlay(self, *, out=None, to_host: bool = False, **plan_kw):
         """``overlay.draw_heads(target, self.heads, out=out, **plan_kw)``: every head's box and, with ``labels="id"``, ``"score"``, ``"id+score"`` or one string
@@ -180,6 +190,9 @@ class PredictionResult:
         for name in ("track_ids", "coasting"):
             if getattr(self, name, None) is not None:
                 plan_kw.setdefault(name, getattr(self, name))
+        from .video import require_8bit_frame
+
+        require_8bit_frame("draw_overlay", self.source_frame)
         target = self.source_frame if self.source_frame is not None else self.original_image
         if target is None:
             raise ValueError("draw_overlay: the result has neither a source_frame nor an original_image to draw into")

@@ -266,15 +266,16 @@ class HeadDetector:
         """Batched twin of ``__call__`` (what yolo_heads_post_prediction_callback.py:41-99 does for a batch): the images, of any sizes, go through
         ONE fused device call (vgh_detect with VGH_IMG_U8_RAW: batched letterbox -> net -> top-k -> NMS per image -> FLAME decode + un-pad + head
         pose of every survivor); only the final per-head Python objects are built on the host.  Needs ``max_batch >= len(images)``.
-        Video frames: a list of ``video.YUV420Frame`` (all of them frames) goes through the same call as VGH_IMG_YUV420_RAW; each result's ``original_image`` is the
+        Video frames: a list of ``video.YUV420Frame`` (all of them; or all of them 10- / 12-bit ``video.YUV420Frame16``) goes through the same call as VGH_IMG_YUV420_RAW
+        (VGH_IMG_YUV420P16_RAW); each result's ``original_image`` is the
         frame's ``to_rgb()``, a NumPy array, or with ``rgb="device"`` a GPU tensor (which ``draw(..., to_host=False)`` and the other device helpers take as it is), or
         with ``rgb="none"`` None: no RGB copy is made, the mode for video loops that only use ``source_frame`` (``anonymize_frame``).  ``source_frame`` is the frame."""
         if len(images) > self._max_batch:
             raise ValueError(f"detect_batch: {len(images)} images exceed max_batch={self._max_batch} (pass max_batch= to HeadDetector)")
         from .letterbox import geometry
-        from .video import YUV420Frame, frame_rgb
+        from .video import FRAME_TYPES, frame_rgb
 
-        frames = any(isinstance(im, YUV420Frame) for im in images)
+        frames = any(isinstance(im, FRAME_TYPES) for im in images)
         if rgb != "host" and not frames:
             raise ValueError(f"rgb={rgb!r} applies to YUV420Frame inputs only")
         originals = list(images) if frames else [self._convert_image(im) for im in images]
@@ -332,9 +333,9 @@ class HeadDetector:
         (``sliced.to_whole_image_params``); head pose as ``__call__`` computes it.  With only the whole-image tile (``tile_sizes=()``) the heads are those of
         ``__call__``.  -> PredictionResult, or (PredictionResult, sliced.SliceInfo) with ``return_info``."""
         from . import sliced
-        from .video import YUV420Frame
+        from .video import FRAME_TYPES
 
-        if isinstance(image, YUV420Frame):
+        if isinstance(image, FRAME_TYPES):
             raise TypeError("detect_sliced takes an RGB image: its tiles are pitched sub-views of the photograph, which a 4:2:0 frame's half-size chroma planes cannot "
                             "give at odd offsets; pass frame.to_rgb()")
         original = self._convert_image(image)
@@ -384,13 +385,13 @@ class HeadDetector:
         return result, sliced.SliceInfo(plan=plan, head_tile=tile_of, status_counts=dict(zip(sliced.STATUS_NAMES, tally)), n_kept_uncapped=int(merged.n_kept_uncapped.item()))
 
     def __call__(self, image: Union[str, "np.ndarray", Any], confidence_threshold: float = 0.5, *, rgb: str = "host") -> PredictionResult:
-        """``image``: a path, a PIL image, an HWC uint8 array, or a ``video.YUV420Frame`` (NV12 / NV21 / I420, converted inside the device letterbox; the result is
+        """``image``: a path, a PIL image, an HWC uint8 array, or a ``video.YUV420Frame`` (NV12 / NV21 / I420) or ``video.YUV420Frame16`` (P010 / I010, 10 or 12 bits), converted inside the device letterbox (the result is
         that of the frame's ``to_rgb()`` image, which becomes ``original_image``: on the host, or with ``rgb="device"`` as a GPU tensor; ``rgb="none"`` makes no RGB
         copy, ``original_image`` is None.  The frame itself is the result's ``source_frame``, which ``anonymize_frame`` works on)."""
-        from .video import YUV420Frame, frame_rgb
+        from .video import FRAME_TYPES, frame_rgb
 
-        source_frame = image if isinstance(image, YUV420Frame) else None
-        if isinstance(image, YUV420Frame):
+        source_frame = image if isinstance(image, FRAME_TYPES) else None
+        if source_frame is not None:
             from .letterbox import geometry
 
             _, _, pad_x, pad_y, scale = geometry(image.shape[0], image.shape[1], self._image_size)

@@ -245,19 +245,33 @@ class VGHeadsEngine:
     def _images_arg(self, images) -> Tuple[int, int, int]:
         """(B, image format, pointer for vgh_detector_candidates): a canvas batch (``_check_images``), or a list of GPU uint8 tensors [h, w, C >= 3] of any size
         (VGH_IMG_U8_RAW, letterboxed on the device; rows may be padded: strides (pitch, C, 1)) -> a host array of vgh_raw_image kept alive on the engine; or a list of
-        video.YUV420Frame (VGH_IMG_YUV420_RAW: converted while letterboxed) -> a host array of vgh_yuv420_image.  A list holds one kind or the other."""
+        video.YUV420Frame (VGH_IMG_YUV420_RAW: converted while letterboxed) -> a host array of vgh_yuv420_image; or a list of video.YUV420Frame16 (VGH_IMG_YUV420P16_RAW:
+        10- / 12-bit frames, likewise) -> a host array of vgh_yuv420p16_image.  A list holds one kind only."""
         if isinstance(images, torch.Tensor):
             B, fmt = self._check_images(images)
             return B, fmt, images.data_ptr()
-        from .video import YUV420Frame
+        from .video import YUV420Frame, YUV420Frame16
 
         B = len(images)
         if not 1 <= B <= self.max_batch:
             raise ValueError(f"raw image batch of {B} outside 1..max_batch={self.max_batch}")
-        n_frames = sum(isinstance(t, YUV420Frame) for t in images)
+        n_frames, n_deep = sum(isinstance(t, YUV420Frame) for t in images), sum(isinstance(t, YUV420Frame16) for t in images)
+        if n_frames not in (0, B) or n_deep not in (0, B):
+            raise ValueError(f"a batch holds YUV420Frames, YUV420Frame16s or RGB tensors, not both ({n_frames} of {B} are 8-bit frames, {n_deep} deep frames): one call has one "
+                             "image format; convert with frame.to_rgb()")
+        if n_deep:
+            arr = (_lib.Yuv420P16Image * B)()
+            for i, f in enumerate(images):
+                if f.device != self.device:
+                    raise ValueError(f"frame {i}: its planes are on {f.device}, the engine is on {self.device}")
+                h, w, _ = f.shape
+                arr[i] = _lib.Yuv420P16Image(f.y.data_ptr(), f.u.data_ptr(), f.v.data_ptr(), h, w, 2 * f.y_pitch, 2 * f.uv_pitch, 2 * f.chroma_step, f.bit_depth, f.shift,
+                                             *f.coefficients)
+                for t in f.planes:
+                    t.record_stream(self.stream)  # read asynchronously by the letterbox on the engine stream
+            self._raw_arg = arr
+            return B, _lib.VGH_IMG_YUV420P16_RAW, C.addressof(arr)
         if n_frames:
-            if n_frames != B:
-                raise ValueError(f"a batch holds YUV420Frames or RGB tensors, not both ({n_frames} of {B} are frames): one call has one image format; convert with frame.to_rgb()")
             arr = (_lib.Yuv420Image * B)()
             for i, f in enumerate(images):
                 if f.device != self.device:
@@ -417,7 +431,7 @@ class VGHeadsEngine:
         (a batch that runs in several arena chunks gathers eagerly whatever the flag says).  ``images`` may be a list of raw images (see ``detect``)."""
         self.stream.wait_stream(torch.cuda.current_stream(self.device))
         B, fmt, ptr = self._images_arg(images)
-        if use_graph and B <= self.arena_batch and fmt not in _lib.RAW_FORMATS:
+        if use_graph and B <= self.arena_batch and fmt not in _lib.DESCRIPTOR_FORMATS:
             self.forward_net(images, True)
             self.candidates(B, lazy_flame=lazy_flame)
             return B
@@ -495,7 +509,8 @@ class VGHeadsEngine:
         ``images``: a letterboxed canvas batch (f32 [B,3,S,S] / u8 [B,S,S,3]), or a LIST of GPU uint8 tensors [h, w, C >= 3] of any size (VGH_IMG_U8_RAW:
         letterboxed on the device as detector.py:40-52 does; the boxes stay in the padded S-space, the FLAME outputs are un-padded with the letterbox
         geometry -- ``raw_unpad()`` -- unless ``unpad`` is given), or a LIST of ``video.YUV420Frame`` (VGH_IMG_YUV420_RAW: NV12 / NV21 / I420 video frames,
-        converted to RGB inside the letterbox; the result is that of the frames' ``to_rgb()`` images).
+        converted to RGB inside the letterbox; the result is that of the frames' ``to_rgb()`` images), or a LIST of ``video.YUV420Frame16``
+        (VGH_IMG_YUV420P16_RAW: 10- / 12-bit P010 / I010 frames, likewise).
         ``unpad`` [B,3] = (pad_x, pad_y, scale) per image fuses detector.py:67-69.  The result is written into fresh tensors the
         caller owns; ``reuse_outputs=True`` writes into the engine's own output buffers (no allocation, see ``Detections``)."""
         cur = torch.cuda.current_stream(self.device)
@@ -516,7 +531,7 @@ class VGHeadsEngine:
             with torch.cuda.stream(self.stream):
                 slot = self.new_output_slot(flame, B)
         # (r06) lazy FLAME gather: detect() queues the select right behind the candidates, so the survivors' vectors come straight from the prediction buffers
-        if use_graph and B <= self.arena_batch and fmt not in _lib.RAW_FORMATS:
+        if use_graph and B <= self.arena_batch and fmt not in _lib.DESCRIPTOR_FORMATS:
             self.forward_candidates(images, True, lazy_flame=True)
         else:
             self._set_lazy_flame(True)

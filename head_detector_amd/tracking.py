@@ -190,7 +190,7 @@ class HeadTracker:
         return self.update_batch([frame], rgb=rgb)[0]
 
     def update_batch(self, frames: Sequence, *, rgb: str = "host") -> List[TrackedPredictionResult]:
-        """``frames``: RGB images as ``HeadDetector.detect_batch`` takes them, or ``video.YUV420Frame`` s (all of them; converted inside the device letterbox).  For
+        """``frames``: RGB images as ``HeadDetector.detect_batch`` takes them, or ``video.YUV420Frame`` s / ``video.YUV420Frame16`` s (one kind, all of them; converted inside the device letterbox).  For
         those, each result's ``original_image`` is the frame's ``to_rgb()``: a NumPy array, or with ``rgb="device"`` a GPU tensor, or with ``rgb="none"`` None (no RGB
         copy is made), and its ``source_frame`` is the frame, which ``anonymize_frame`` works on."""
         import torch
@@ -202,9 +202,9 @@ class HeadTracker:
         det = self.detector
         if len(frames) > det._max_batch:
             raise ValueError(f"update_batch: {len(frames)} frames exceed max_batch={det._max_batch} (pass max_batch= to HeadDetector)")
-        from .video import YUV420Frame, frame_rgb
+        from .video import FRAME_TYPES, frame_rgb
 
-        yuv = any(isinstance(im, YUV420Frame) for im in frames)  # (a list mixing them with RGB images is refused by the engine)
+        yuv = any(isinstance(im, FRAME_TYPES) for im in frames)  # (a list mixing them with RGB images is refused by the engine)
         if rgb != "host" and not yuv:
             raise ValueError(f"rgb={rgb!r} applies to YUV420Frame inputs only")
         originals = list(frames) if yuv else [det._convert_image(im) for im in frames]

@@ -12,6 +12,13 @@ integer rule stated in include/vgh.h (vgh_yuv420_image) -- nearest chroma sample
 ``YUV420Frame.to_rgb()`` is that rule in torch integer ops (CPU or GPU tensors); the detector's result is defined as "``to_rgb()``, then what an RGB image gets".
 PARITY UNPINNED against cv2.cvtColor (cv2 rounds its coefficients to another fixed-point precision): ``tools/first_contact.py --cv2`` reports the difference.
 
+10- and 12-bit frames (HEVC Main10, AV1 10-bit: P010 / P012 / P016 surfaces, yuv420p10le planes) go in the same way as a ``YUV420Frame16``:
+
+    frame = YUV420Frame16.from_p010(surface, height, width, pitch=surface_pitch, uv_offset=aligned_height * surface_pitch)   # or from_i010; views, no copy
+    predictions = detector(frame)                 # VGH_IMG_YUV420P16_RAW: sample = (word >> shift) & (2^D - 1), the same rule with 2^(D+8) coefficients, RGB BYTES out
+
+Everything behind the fetch is the 8-bit path; ``to_8bit()`` narrows a deep frame for ``anonymize_frame``, the overlay and the head tensors, which work in 8-bit planes.
+
 Out again, to an encoder (include/vgh_video.h, libvghvideo.so; restated in tests/yuv_anonymize_ref.py and equal to it bit for bit):
 
     anonymize_frame(frame, heads, out=frame)      # every head hidden in the frame's own luma and chroma planes, in place: no RGB image is made
@@ -38,7 +45,7 @@ import torch
 MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722), "bt2020": (0.2627, 0.0593)}
 
 
-def yuv_coefficients(matrix: str = "bt709", full_range: bool = False) -> Tuple[int, int, int, int, int, int]:
+def yuv_coefficients(matrix: str = "bt709", full_range: bool = False, bit_depth: int = 8) -> Tuple[int, int, int, int, int, int]:
     """-> (y_offset, cy, crv, cgu, cgv, cbu): the fixed-point coefficients (* 2^16) of vgh_yuv420_image, rounded (``round``: half to even; no value is a tie) from
     the float64 (Kr, Kb) definition of ``matrix``, Kg = 1 - Kr - Kb:
 
@@ -47,14 +54,26 @@ def yuv_coefficients(matrix: str = "bt709", full_range: bool = False) -> Tuple[i
         crv = round(65536 * sc * 2 (1 - Kr))                  R = sy (Y - y_offset) + sc 2 (1 - Kr) (V - 128)
         cbu = round(65536 * sc * 2 (1 - Kb))                  B = sy (Y - y_offset) + sc 2 (1 - Kb) (U - 128)
         cgu = round(65536 * sc * -2 Kb (1 - Kb) / Kg)         G = (Y - Kr R - Kb B) / Kg
-        cgv = round(65536 * sc * -2 Kr (1 - Kr) / Kg)"""
+        cgv = round(65536 * sc * -2 Kr (1 - Kr) / Kg)
+
+    ``bit_depth`` D = 10 or 12: the coefficients (* 2^(D+8)) of vgh_yuv420p16_image, which take D-bit samples to 8-bit RGB -- the same expressions with
+    65536 -> 2^(D+8), 128 -> 2^(D-1) and, with k = 2^(D-8):
+
+        limited range: y_offset = 16 k, sy = 255 / (219 k), sc = 255 / (224 k)        full range: y_offset = 0, sy = sc = 255 / (2^D - 1)
+
+    (a power of two scales a float64 exactly, so the limited-range integers are those of 8 bits; the full-range ones are not: 255 / 1023 is not 1 / 4)."""
     if matrix not in MATRICES:
         raise ValueError(f"yuv_coefficients: matrix {matrix!r} is not one of {sorted(MATRICES)}")
+    if bit_depth not in (8, 10, 12):
+        raise ValueError(f"yuv_coefficients: bit_depth {bit_depth!r} is not 8, 10 or 12")
     kr, kb = MATRICES[matrix]
     kg = 1.0 - kr - kb
-    sy, sc = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
-    q = lambda v: int(round(65536.0 * v))  # noqa: E731
-    return (0 if full_range else 16, q(sy), q(sc * 2.0 * (1.0 - kr)), q(sc * -2.0 * kb * (1.0 - kb) / kg), q(sc * -2.0 * kr * (1.0 - kr) / kg), q(sc * 2.0 * (1.0 - kb)))
+    k = float(1 << (bit_depth - 8))
+    sy, sc = (255.0 / ((1 << bit_depth) - 1),) * 2 if full_range else (255.0 / (219.0 * k), 255.0 / (224.0 * k))  # (8 bits, full range: 255 / 255 = 1.0)
+    one = float(1 << (bit_depth + 8))
+    q = lambda v: int(round(one * v))  # noqa: E731
+    return (0 if full_range else 16 << (bit_depth - 8), q(sy), q(sc * 2.0 * (1.0 - kr)), q(sc * -2.0 * kb * (1.0 - kb) / kg), q(sc * -2.0 * kr * (1.0 - kr) / kg),
+            q(sc * 2.0 * (1.0 - kb)))
 
 
 def rgb_to_yuv_coefficients(matrix: str = "bt709", full_range: bool = False) -> Tuple[int, ...]:
@@ -327,7 +346,240 @@ class YUV420Frame:
         return f"YUV420Frame({h} x {w}, chroma_step={self.chroma_step}, {self.matrix}, {'full' if self.full_range else 'limited'} range, {self.device})"
 
 
-def frame_rgb(frame: YUV420Frame, rgb: str = "host") -> Union[np.ndarray, torch.Tensor, None]:
+_WORDS = tuple(getattr(torch, n) for n in ("int16", "uint16") if hasattr(torch, n))
+
+
+def _as_words(a, what: str, surface: bool = False) -> torch.Tensor:
+    """A tensor of 16-bit words as it is (CPU or GPU, int16 or uint16); a NumPy array of them uploaded once to the current GPU.  ``surface``: bytes will do as well."""
+    ok = "uint8, int16 or uint16" if surface else "int16 or uint16"
+    if isinstance(a, np.ndarray):
+        if a.dtype not in ((np.int16, np.uint16, np.uint8) if surface else (np.int16, np.uint16)):
+            raise ValueError(f"{what}: expected {ok}; got {a.dtype}")
+        a = np.ascontiguousarray(a)
+        return torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).to(torch.device("cuda", torch.cuda.current_device()))
+    if not isinstance(a, torch.Tensor) or a.dtype not in (_WORDS + ((torch.uint8,) if surface else ())):
+        raise ValueError(f"{what}: expected a tensor or array of {ok}; got {getattr(a, 'dtype', type(a))}")
+    return a
+
+
+class YUV420Frame16:
+    """One 10- or 12-bit YUV 4:2:0 frame in 16-bit words, as HEVC Main10 / AV1 10-bit decoders deliver it (P010 / P012 / P016 surfaces, I010 = yuv420p10le planes):
+    ``y`` [h, w] (rows may be pitched: strides (pitch, 1)), ``u`` and ``v`` [(h+1)//2, (w+1)//2] with strides (uv_pitch, chroma_step), all counted in ELEMENTS
+    (16-bit words) -- chroma_step 1 for planar planes, 2 for the two interleaved views of a P010 chroma plane.  The planes are ``torch.int16`` or ``torch.uint16``
+    tensors, kept as given (views are not copied) and read as unsigned little-endian words either way; all three on one device.  NumPy ``uint16`` planes are
+    uploaded once to the current GPU (planar only, see ``from_p010``).  A sample is ``(word >> shift) & (2^bit_depth - 1)``: ``shift = 16 - bit_depth`` for the
+    MSB-aligned words of a hardware decoder, 0 for LSB-aligned ones; whatever lies in a word's other bits is never looked at.  ``matrix`` / ``full_range`` choose
+    the coefficients (``yuv_coefficients(matrix, full_range, bit_depth)``).
+
+    The detector takes it wherever it takes a ``YUV420Frame`` (VGH_IMG_YUV420P16_RAW: every tap converted to RGB BYTES inside the device letterbox by the rule of
+    include/vgh.h, vgh_yuv420p16_image; ``to_rgb()`` is that rule in torch integer ops).  It is deliberately not a ``YUV420Frame``: ``anonymize_frame``, the overlay
+    and the head tensors work in 8-bit planes, and ``to_8bit()`` is the bridge to them.  Writing into deep planes, crops from them, 4:2:2 / 4:4:4, big-endian words,
+    16 significant bits, chroma interpolation and HDR tone mapping are not built: a PQ / HLG frame is converted by its matrix only."""
+
+    def __init__(self, y, u, v, *, chroma_step: int, bit_depth: int = 10, shift: int = 0, matrix: str = "bt709", full_range: bool = False):
+        who = "YUV420Frame16"
+        if chroma_step not in (1, 2):
+            raise ValueError(f"{who}: chroma_step {chroma_step} (in 16-bit elements: 1 = planar, 2 = interleaved)")
+        if bit_depth not in (10, 12):
+            raise ValueError(f"{who}: bit_depth {bit_depth!r} (10 or 12)")
+        if not isinstance(shift, (int, np.integer)) or isinstance(shift, bool) or not 0 <= shift <= 16 - bit_depth:
+            raise ValueError(f"{who}: shift {shift!r} outside 0 .. 16 - bit_depth = {16 - bit_depth}")
+        if chroma_step == 2 and any(isinstance(p, np.ndarray) for p in (u, v)):
+            raise ValueError(f"{who}: interleaved NumPy chroma views would be uploaded as two buffers; use from_p010 with the whole surface")
+        y, u, v = _as_words(y, f"{who}: y"), _as_words(u, f"{who}: u"), _as_words(v, f"{who}: v")
+        if y.dim() != 2 or y.shape[0] < 1 or y.shape[1] < 1:
+            raise ValueError(f"{who}: y must be [h, w] with h, w >= 1; got {tuple(y.shape)}")
+        h, w = int(y.shape[0]), int(y.shape[1])
+        ch, cw = (h + 1) // 2, (w + 1) // 2
+        if tuple(u.shape) != (ch, cw) or tuple(v.shape) != (ch, cw):
+            raise ValueError(f"{who}: a {h} x {w} frame has chroma planes [{ch}, {cw}]; got u {tuple(u.shape)}, v {tuple(v.shape)}")
+        if not (y.device == u.device == v.device):
+            raise ValueError(f"{who}: planes on different devices: {y.device}, {u.device}, {v.device}")
+        if w > 1 and y.stride(1) != 1:
+            raise ValueError(f"{who}: the luma samples of a row must be dense (strides (pitch, 1)); got {y.stride()}")
+        y_pitch = _pitch(y, 0, w)
+        if y_pitch < w:
+            raise ValueError(f"{who}: luma pitch {y_pitch} < width {w}")
+        for name, p in (("u", u), ("v", v)):
+            if cw > 1 and p.stride(1) != chroma_step:
+                raise ValueError(f"{who}: {name} has samples {p.stride(1)} elements apart, chroma_step says {chroma_step}")
+        uv_pitch, v_pitch = _pitch(u, 0, chroma_step * cw), _pitch(v, 0, chroma_step * cw)
+        if ch > 1 and uv_pitch != v_pitch:
+            raise ValueError(f"{who}: u and v rows are {uv_pitch} and {v_pitch} elements apart; the two chroma planes share one pitch")
+        if uv_pitch < chroma_step * cw:
+            raise ValueError(f"{who}: chroma pitch {uv_pitch} < chroma_step * ((w + 1) // 2) = {chroma_step * cw}")
+        coef = yuv_coefficients(matrix, full_range, bit_depth)
+        self.y, self.u, self.v = y, u, v
+        self._words = tuple(p if p.dtype == torch.int16 else p.view(torch.int16) for p in (y, u, v))  # torch has no shift for uint16: the same memory as int16
+        self.chroma_step, self.bit_depth, self.shift = int(chroma_step), int(bit_depth), int(shift)
+        self.matrix, self.full_range = matrix, bool(full_range)
+        self.y_pitch, self.uv_pitch = y_pitch, uv_pitch  # in elements, like the strides
+        self.coefficients = coef
+
+    # ---- views of decoder output ----------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _surface(buffer, who: str) -> torch.Tensor:
+        """The surface as one flat int16 view of the buffer (uint8 buffers: an even number of bytes from an even address)."""
+        t = _as_words(buffer, who, surface=True)
+        if not t.is_contiguous():
+            raise ValueError(f"{who}: the surface must be one contiguous buffer; got strides {t.stride()}")
+        t = t.reshape(-1)
+        if t.dtype == torch.uint8:
+            if t.storage_offset() % 2 or (t.device.type != "meta" and t.numel() and t.data_ptr() % 2):
+                raise ValueError(f"{who}: the surface starts at an odd byte; 16-bit words need an even address")
+            t = t[:t.numel() & ~1]
+        return t if t.dtype == torch.int16 else t.view(torch.int16)
+
+    @staticmethod
+    def _view(flat: torch.Tensor, who: str, shape, strides, offset: int) -> torch.Tensor:
+        last = offset + sum((n - 1) * s for n, s in zip(shape, strides))
+        if offset < 0 or last >= flat.numel():
+            raise ValueError(f"{who}: bytes [{2 * offset}, {2 * last + 1}] lie outside the surface of {2 * flat.numel()} bytes")
+        return torch.as_strided(flat, shape, strides, flat.storage_offset() + offset)
+
+    @staticmethod
+    def _geometry(who: str, height, width, pitch, uv_offset, unit: int):
+        """-> (h, w, ch, cw, pitch, uv_offset), the last two in BYTES and checked: ``pitch`` a multiple of ``unit``, the chroma behind the luma plane."""
+        h, w = int(height), int(width)
+        if h < 1 or w < 1:
+            raise ValueError(f"{who}: frame of {h} x {w}")
+        ch, cw = (h + 1) // 2, (w + 1) // 2
+        pitch = int(pitch) if pitch is not None else 4 * cw  # (an odd width needs w + 1 words per chroma row)
+        if pitch % unit or pitch < 2 * w or pitch < 4 * cw:
+            raise ValueError(f"{who}: pitch {pitch} bytes must be a multiple of {unit} and hold rows of {2 * w} luma / {4 * cw} chroma bytes")
+        uv_offset = int(uv_offset) if uv_offset is not None else pitch * h
+        if uv_offset % 2 or uv_offset < pitch * (h - 1) + 2 * w:
+            raise ValueError(f"{who}: uv_offset {uv_offset} is odd or lies inside the luma plane ({h} rows, {pitch} bytes apart)")
+        return h, w, ch, cw, pitch, uv_offset
+
+    @classmethod
+    def from_p010(cls, buffer_or_planes, height: int, width: int, pitch: Optional[int] = None, uv_offset: Optional[int] = None, bit_depth: int = 10, **kw) -> "YUV420Frame16":
+        """P010: a luma plane and ONE chroma plane of interleaved (U, V) pairs of 16-bit words with the sample in the TOP bits (``shift = 16 - bit_depth``), as
+        hardware decoders deliver HEVC Main10 / AV1 10-bit; ``bit_depth=12`` reads a P012 / P016 surface at its top 12 bits.  ``buffer_or_planes``: the whole surface
+        as one contiguous buffer (uint8, int16 or uint16) -- rows ``pitch`` BYTES apart (default: 4 * ((width + 1) // 2)), the chroma plane at BYTE ``uv_offset``
+        (default ``pitch * height``) -- or a pair (y [h, w], uv [ch, cw, 2]) of 16-bit planes.  Views, no copy (NumPy: one upload).  ``**kw``: matrix, full_range."""
+        who = "from_p010"
+        if bit_depth not in (10, 12):
+            raise ValueError(f"{who}: bit_depth {bit_depth!r} (10 or 12)")
+        kw = dict(kw, bit_depth=bit_depth, shift=16 - bit_depth)
+        if isinstance(buffer_or_planes, (tuple, list)):
+            h, w = int(height), int(width)
+            if h < 1 or w < 1:
+                raise ValueError(f"{who}: frame of {h} x {w}")
+            ch, cw = (h + 1) // 2, (w + 1) // 2
+            if len(buffer_or_planes) != 2:
+                raise ValueError(f"{who}: planes are (y, uv)")
+            y, uv = _as_words(buffer_or_planes[0], f"{who}: y"), _as_words(buffer_or_planes[1], f"{who}: uv")
+            if uv.dim() == 2 and uv.shape[1] == 2 * cw and uv.stride(1) == 1:
+                uv = uv.unflatten(1, (cw, 2))
+            if uv.dim() != 3 or tuple(uv.shape) != (ch, cw, 2):
+                raise ValueError(f"{who}: the chroma plane of a {h} x {w} frame is [{ch}, {cw}, 2] (or [{ch}, {2 * cw}]); got {tuple(uv.shape)}")
+            if tuple(y.shape) != (h, w):
+                raise ValueError(f"{who}: y is {tuple(y.shape)}, not [{h}, {w}]")
+            return cls(y, uv[..., 0], uv[..., 1], chroma_step=2, **kw)
+        h, w, ch, cw, pitch, uv_offset = cls._geometry(who, height, width, pitch, uv_offset, 2)
+        flat = cls._surface(buffer_or_planes, who)
+        y = cls._view(flat, who, (h, w), (pitch // 2, 1), 0)
+        u = cls._view(flat, who, (ch, cw), (pitch // 2, 2), uv_offset // 2)
+        v = cls._view(flat, who, (ch, cw), (pitch // 2, 2), uv_offset // 2 + 1)
+        return cls(y, u, v, chroma_step=2, **kw)
+
+    @classmethod
+    def from_i010(cls, buffer_or_planes, height: int, width: int, pitch: Optional[int] = None, uv_offset: Optional[int] = None, bit_depth: int = 10, **kw) -> "YUV420Frame16":
+        """Planar I010 (``yuv420p10le``; ``bit_depth=12``: ``yuv420p12le``): luma, then the U plane, then the V plane, 16-bit words with the sample in the LOW bits
+        (``shift = 0``), as software decoders deliver it.  ``buffer_or_planes``: one contiguous buffer (uint8, int16 or uint16) -- luma rows ``pitch`` BYTES apart (a
+        multiple of 4; default 4 * ((width + 1) // 2)), chroma rows ``pitch // 2``, the U plane at BYTE ``uv_offset`` (default ``pitch * height``) and the V plane
+        right behind its ``(height + 1) // 2`` rows -- or a triple (y, u, v) of 16-bit planes.  Views, no copy."""
+        who = "from_i010"
+        if bit_depth not in (10, 12):
+            raise ValueError(f"{who}: bit_depth {bit_depth!r} (10 or 12)")
+        kw = dict(kw, bit_depth=bit_depth, shift=0)
+        if isinstance(buffer_or_planes, (tuple, list)):
+            if len(buffer_or_planes) != 3:
+                raise ValueError(f"{who}: planes are (y, u, v)")
+            y, u, v = buffer_or_planes
+            if tuple(getattr(y, "shape", ())) != (int(height), int(width)):
+                raise ValueError(f"{who}: y is {tuple(getattr(y, 'shape', ()))}, not [{int(height)}, {int(width)}]")
+            return cls(y, u, v, chroma_step=1, **kw)
+        h, w, ch, cw, pitch, uv_offset = cls._geometry(who, height, width, pitch, uv_offset, 4)
+        flat = cls._surface(buffer_or_planes, who)
+        cp = pitch // 4  # chroma rows in words
+        y = cls._view(flat, who, (h, w), (pitch // 2, 1), 0)
+        u = cls._view(flat, who, (ch, cw), (cp, 1), uv_offset // 2)
+        v = cls._view(flat, who, (ch, cw), (cp, 1), uv_offset // 2 + cp * ch)
+        return cls(y, u, v, chroma_step=1, **kw)
+
+    # ---------------------------------------------------------------------------------------------------------------------------------------
+    @property
+    def shape(self) -> Tuple[int, int, int]:
+        """(h, w, 3): the shape of the RGB image this frame stands for."""
+        return (int(self.y.shape[0]), int(self.y.shape[1]), 3)
+
+    @property
+    def device(self) -> torch.device:
+        return self.y.device
+
+    @property
+    def planes(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        return self.y, self.u, self.v
+
+    def _samples(self):
+        """The three planes as int32 samples: (word >> shift) & (2^bit_depth - 1), the words read as unsigned."""
+        mask = (1 << self.bit_depth) - 1
+        return tuple(torch.bitwise_right_shift(p.to(torch.int32) & 0xFFFF, self.shift) & mask for p in self._words)
+
+    def to_rgb(self) -> torch.Tensor:
+        """uint8 [h, w, 3] on the frame's device: every pixel by the rule of include/vgh.h (vgh_yuv420p16_image), in int32 torch ops (exactly what the library's
+        letterbox fetches)."""
+        h, w, _ = self.shape
+        D = self.bit_depth
+        y_offset, cy, crv, cgu, cgv, cbu = self.coefficients
+        ys, us, vs = self._samples()
+        up = lambda p: (p - (1 << (D - 1))).repeat_interleave(2, dim=0)[:h].repeat_interleave(2, dim=1)[:, :w]  # noqa: E731  (y >> 1, x >> 1)
+        d, e = up(us), up(vs)
+        luma = cy * (ys - y_offset) + (1 << (D + 7))
+        rgb = torch.stack([luma + crv * e, luma + cgu * d + cgv * e, luma + cbu * d], dim=-1)
+        return torch.bitwise_right_shift(rgb, D + 8).clamp_(0, 255).to(torch.uint8)
+
+    def to_8bit(self, layout: Optional[str] = None, out: Optional[YUV420Frame] = None) -> YUV420Frame:
+        """The frame narrowed to 8 bits per sample, a ``YUV420Frame`` with this frame's matrix and range: every sample s becomes
+        ``min(255, (s + 2^(D-9)) >> (D-8))``.  The bridge to ``anonymize_frame``, ``draw_overlay`` and ``get_head_tensors``, which work in 8-bit planes.  A new dense
+        ``layout`` frame ("nv12" for interleaved chroma, "i420" for planar, unless given), or ``out``: a ``YUV420Frame`` of the same size on the same device (its own
+        layout is kept, its matrix and range must be this frame's).  Several torch passes over the frame, not a tuned kernel.  In limited range the code values
+        scale by 2^(D-8) exactly, so this is the matching 8-bit frame up to rounding; in FULL range (white = 2^D - 1, not 255 * 2^(D-8)) it is a rounded shift, not a
+        range-exact rescale.  The detector's result on the 8-bit frame is not that on the deep frame."""
+        h, w, _ = self.shape
+        if out is None:
+            layout = layout if layout is not None else "nv12" if self.chroma_step == 2 else "i420"
+            if layout not in LAYOUTS:
+                raise ValueError(f"to_8bit: layout must be one of {LAYOUTS}, got {layout!r}")
+            out = YUV420Frame.empty(h, w, layout, self.device, matrix=self.matrix, full_range=self.full_range)
+        elif not (isinstance(out, YUV420Frame) and out.shape == self.shape and out.device == self.device):
+            raise ValueError(f"to_8bit: out must be a YUV420Frame of {h} x {w} on {self.device}; got {out!r}")
+        elif (out.matrix, out.full_range) != (self.matrix, self.full_range):
+            raise ValueError(f"to_8bit: out is {out!r}; the frame is {self.matrix}, {'full' if self.full_range else 'limited'} range")
+        D = self.bit_depth
+        for dst, s in zip(out.planes, self._samples()):
+            dst.copy_(torch.bitwise_right_shift(s + (1 << (D - 9)), D - 8).clamp_(max=255))
+        return out
+
+    def __repr__(self) -> str:
+        h, w, _ = self.shape
+        return (f"YUV420Frame16({h} x {w}, {self.bit_depth} bits >> {self.shift}, chroma_step={self.chroma_step}, {self.matrix}, "
+                f"{'full' if self.full_range else 'limited'} range, {self.device})")
+
+
+FRAME_TYPES = (YUV420Frame, YUV420Frame16)  # what the detector's and the tracker's entry points take as a video frame
+
+
+def require_8bit_frame(who: str, frame) -> None:
+    """The refusal of the consumers that work in 8-bit planes, for a result whose ``source_frame`` is a deep frame."""
+    if isinstance(frame, YUV420Frame16):
+        raise ValueError(f"{who}: the source_frame is a {frame.bit_depth}-bit YUV420Frame16 and {who} works in 8-bit planes; narrow it with source_frame.to_8bit() and pass "
+                         "that frame (video.anonymize_frame, overlay.draw_heads, head_tensors.head_tensors)")
+
+
+def frame_rgb(frame: Union[YUV420Frame, YUV420Frame16], rgb: str = "host") -> Union[np.ndarray, torch.Tensor, None]:
     """The ``original_image`` of a result whose input was a frame: ``to_rgb()`` on the host (NumPy, the default, like any other call) or kept on the device; with
     ``rgb="none"`` no RGB copy is made at all (None): the result keeps its ``source_frame``, which ``anonymize_frame`` works on."""
     if rgb not in ("host", "device", "none"):

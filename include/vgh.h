@@ -69,6 +69,41 @@ typedef struct vgh_yuv420_image {
     int32_t cy, crv, cgu, cgv, cbu;       /* fixed-point coefficients * 2^16, each |c| <= 2^20 (1048576) */
 } vgh_yuv420_image;
 
+#define VGH_IMG_YUV420P16_RAW 4 /* 10- and 12-bit YUV 4:2:0 video frames in 16-bit words (P010 / P012 / P016 surfaces, I010 / yuv420p10le / yuv420p12le planes), converted to */
+                                /*   RGB bytes and letterboxed on the device in one pass: `images_dev` is a HOST array of B vgh_yuv420p16_image.  Accepted and rejected */
+                                /*   exactly where VGH_IMG_YUV420_RAW is. */
+
+/* One frame of a VGH_IMG_YUV420P16_RAW batch (read on the host during the call; the planes are read by work queued on the call's stream, as for vgh_raw_image).
+ *
+ * THE CONVERSION RULE FOR DEEP FRAMES (the single statement of it; head_detector_amd/video.py and tests/yuv16_ref.py restate it).  D = bit_depth, M = 2^D - 1; every
+ * sample is a little-endian 16-bit word.  For the luma pixel (x, y), 0 <= x < w, 0 <= y < h, with byte offsets:
+ *     Y = (word(y_dev + y * y_pitch_bytes + 2 * x) >> shift) & M
+ *     U = (word(u_dev + (y >> 1) * uv_pitch_bytes + (x >> 1) * chroma_step) >> shift) & M          V likewise from v_dev
+ *     c = Y - y_offset,  d = U - 2^(D-1),  e = V - 2^(D-1)
+ *     R = clamp8((cy * c           + crv * e + 2^(D+7)) >> (D + 8))
+ *     G = clamp8((cy * c + cgu * d + cgv * e + 2^(D+7)) >> (D + 8))
+ *     B = clamp8((cy * c + cbu * d           + 2^(D+7)) >> (D + 8))
+ * in int32 arithmetic; >> is the arithmetic (flooring) shift; clamp8(v) = min(max(v, 0), 255).  Nearest chroma sample: no chroma interpolation.  At D = 8 this is the
+ * rule of vgh_yuv420_image.  The mask makes the rule total: ANY 16-bit word gives a defined byte, and whatever a decoder leaves in the unused bits of a P010 word
+ * never reaches the arithmetic.
+ * Nothing overflows: |c| <= 4095 and cy <= 2^17, so |cy * c| < 2^29; |d|, |e| <= 2^11 and every |chroma coefficient| <= 2^18, so each chroma product is <= 2^29;
+ * the largest sum (G) is below 3 * 2^29 + 2^19 < 2^31 (D = 12; D = 10 is smaller still).
+ * The frame then is the RGB image [h, w, 3] of these BYTES, and the call does with it exactly what VGH_IMG_U8_RAW does with that image (same letterbox geometry,
+ * LANCZOS4 tables, border colour and un-pad table): every source pixel is converted AND clamped to bytes first, then resampled.  Transfer functions are not
+ * touched: a PQ / HLG frame is converted by its matrix only.
+ * Coefficients (* 2^(D+8)): head_detector_amd/video.py::yuv_coefficients(matrix, full_range, bit_depth).  PARITY UNPINNED against cv2.cvtColor. */
+typedef struct vgh_yuv420p16_image {
+    const uint16_t *y_dev, *u_dev, *v_dev; /* little-endian 16-bit words; luma [h, w], chroma [(h+1)/2, (w+1)/2] each; every pointer and both pitches even (validated) */
+    int32_t h, w;                          /* luma size, >= 1 */
+    int64_t y_pitch_bytes;                 /* >= 2 * w */
+    int64_t uv_pitch_bytes;                /* >= chroma_step * ((w+1)/2); one pitch for both chroma planes */
+    int32_t chroma_step;                   /* BYTES between chroma samples of a row: 2 = planar (I010, yuv420p10le); 4 = interleaved (P010: v_dev = u_dev + 1 word) */
+    int32_t bit_depth;                     /* D: 10 or 12 */
+    int32_t shift;                         /* 0 .. 16 - D: sample = (word >> shift) & (2^D - 1).  P010 / P016 read at 10 bits: 6; P012: 4; LSB-aligned (I010): 0 */
+    int32_t y_offset;                      /* 0 .. 2^D - 1: 16 * 2^(D-8) = limited ("video") range, 0 = full range */
+    int32_t cy, crv, cgu, cgv, cbu;        /* fixed-point coefficients * 2^(D+8): 0 <= cy <= 2^17 (131072), every |chroma coefficient| <= 2^18 (262144) */
+} vgh_yuv420p16_image;
+
 #define VGH_NUM_FLAME_PARAMS 413 /* FLAME_CONSTS, head_detector/head_info.py:12-21 */
 
 const char* vgh_version(void);
@@ -79,7 +114,8 @@ const char* vgh_last_error(void);
  * vgh_flame_set_matrix_path; r05 -> 6: VGH_FMT_FP8, vgh_buf_desc.scale, vgh_conv_call.out_fp8 / gscale_dev, vgh_pack_conv_weights_fp8;
  * -> 7: VGH_FMT_I8, vgh_conv_call.out_fp8 = 2 / diag_dev, vgh_pack_conv_weights_i8, vgh_net_set_i8_diag; -> 8: VGH_IMG_U8_RAW / vgh_raw_image, the
  * detector's VGH_SCRATCH_UNPAD / VGH_SCRATCH_CANVAS; VGH_IMG_YUV420_RAW / vgh_yuv420_image were added within 8: a new format value and a new struct, no
- * symbol added, no existing struct or meaning changed -- an older library answers "unknown image format 3").  A client built against another revision passes structs of another size: compare before the
+ * symbol added, no existing struct or meaning changed -- an older library answers "unknown image format 3"; VGH_IMG_YUV420P16_RAW / vgh_yuv420p16_image
+ * were added within 8 in the same way -- an older library answers "unknown image format 4").  A client built against another revision passes structs of another size: compare before the
  * first call that takes one (head_detector_amd/_lib.py and tests/c_abi_smoke.c do). */
 #define VGH_ABI_VERSION 8
 int vgh_abi_version(void);
@@ -142,7 +178,7 @@ typedef struct vgh_net vgh_net;
 int vgh_net_create(int device, int image_size, int max_batch, const vgh_buf_desc* bufs, int n_bufs, const vgh_op_desc* ops, int n_ops,
                    const float* weights_host, int64_t n_weights, const float* biases_host, int64_t n_biases, vgh_net** out);
 void vgh_net_destroy(vgh_net* net);
-/* image_dev: [B,3,S,S] f32 (VGH_IMG_F32_NCHW) or [B,S,S,3] u8 (VGH_IMG_U8_NHWC). Runs every op.  (VGH_IMG_U8_RAW and VGH_IMG_YUV420_RAW are rejected here and by
+/* image_dev: [B,3,S,S] f32 (VGH_IMG_F32_NCHW) or [B,S,S,3] u8 (VGH_IMG_U8_NHWC). Runs every op.  (VGH_IMG_U8_RAW, VGH_IMG_YUV420_RAW and VGH_IMG_YUV420P16_RAW are rejected here and by
  * vgh_net_profile / vgh_net_capture: a network needs a canvas.) */
 int vgh_net_forward(vgh_net* net, const void* image_dev, int image_fmt, int B, void* stream);
 /* As vgh_net_forward but host-synchronous, bracketing every op with HIP events on `stream`;
@@ -378,10 +414,10 @@ int vgh_flame_set_matrix_path(int mode);
  *       caller's fixed-capacity slabs + the image-major head list + reproject_spatial_vertices / un-pad / calculate_rpy of
  *       every survivor (detector.py:66-69,87)
  *   vgh_detect              = both.
- * Nothing is allocated after vgh_detector_create -- except, once, by the first VGH_IMG_U8_RAW or VGH_IMG_YUV420_RAW call (whichever comes first; they share it): the u8 canvas [arena_batch,S,S,3] and two
+ * Nothing is allocated after vgh_detector_create -- except, once, by the first VGH_IMG_U8_RAW, VGH_IMG_YUV420_RAW or VGH_IMG_YUV420P16_RAW call (whichever comes first; they share it): the u8 canvas [arena_batch,S,S,3] and two
  * pinned + device staging slots of letterbox tables -- all outputs are caller-owned device memory; every call is asynchronous on `stream`; a
  * detector (like the net and FLAME handles it borrows) serves one stream at a time.
- * VGH_IMG_U8_RAW (images of any size) and VGH_IMG_YUV420_RAW (video frames, converted to RGB inside that same launch): per arena chunk ONE async upload of the chunk's LANCZOS4 tables + descriptors, ONE batched letterbox
+ * VGH_IMG_U8_RAW (images of any size) and VGH_IMG_YUV420_RAW / VGH_IMG_YUV420P16_RAW (8-bit / 10- and 12-bit video frames, converted to RGB inside that same launch): per arena chunk ONE async upload of the chunk's LANCZOS4 tables + descriptors, ONE batched letterbox
  * launch into the detector's canvas (the vgh_letterbox arithmetic, bit-identical to it), then the network on the canvas as VGH_IMG_U8_NHWC.
  * The detections stay in the padded S-space (boxes_dev); with out->unpad_dev == NULL the FLAME outputs are un-padded with the detector's
  * table of this call (VGH_SCRATCH_UNPAD); a non-NULL unpad_dev wins.  Invalid descriptors (NULL data, channels < 3, pitch < w * channels, an
@@ -428,7 +464,7 @@ int vgh_detector_candidate_buffers(vgh_detector* d, float** boxes_dev, float** s
 int vgh_detector_set_flame(vgh_detector* d, vgh_flame* flame);
 /* detector-owned intermediates (parity tests / debugging): dense boxes [max_batch,A,4], dense scores [max_batch,A],
  * top-k anchor indices [max_batch,pre_k] i32, NMS keep positions [max_batch,keep_k] i32, head rows [max_batch*keep_k] i32;
- * of the last VGH_IMG_U8_RAW / VGH_IMG_YUV420_RAW call (NULL before the first one): the un-pad table [max_batch,3] f32 (pad_x, pad_y, scale) per image
+ * of the last VGH_IMG_U8_RAW / VGH_IMG_YUV420_RAW / VGH_IMG_YUV420P16_RAW call (NULL before the first one): the un-pad table [max_batch,3] f32 (pad_x, pad_y, scale) per image
  * (detector.py:67-69; what un-pads boxes_dev: (x - pad_x) / scale), and the u8 canvas [arena_batch,S,S,3] holding its last arena chunk */
 #define VGH_SCRATCH_BOXES_ALL 0
 #define VGH_SCRATCH_SCORES_ALL 1

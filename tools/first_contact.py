@@ -163,6 +163,21 @@ def main():
                 d = np.abs(got.astype(np.int32) - cv2.cvtColor(surf, cv2.COLOR_YUV2RGB_NV12).astype(np.int32))
                 yworst, ybad, ytotal = max(yworst, int(d.max())), ybad + int((d > 0).sum()), ytotal + d.size
             print(f"[REPORT] YUV420Frame.to_rgb (bt601, limited) vs cv2 COLOR_YUV2RGB_NV12 (parity unpinned): max |diff| {yworst}, {ybad} of {ytotal} bytes differ", flush=True)
+            # video.YUV420Frame16.to_rgb (the deep rule of include/vgh.h, 10-bit P010, bt601 limited range): cv2.cvtColor converts 8-bit 4:2:0 only, so the
+            # comparison is against cv2 on the frame's to_8bit() NV12 narrowing -- REPORTED, unpinned like the 8-bit rule; the two low sample bits that the
+            # narrowing rounds away add up to one more least significant bit
+            from head_detector_amd.video import YUV420Frame16
+
+            dworst, dbad, dtotal = 0, 0, 0
+            for h, w in ((480, 640), (1080, 1920), (2, 2)):
+                words = rng.integers(0, 65536, (h * 3 // 2, w), dtype=np.uint16)  # 10 sample bits on top of 6 bits a decoder promises nothing about
+                deep = YUV420Frame16.from_p010(torch.from_numpy(words.view(np.int16)), h, w, matrix="bt601")
+                narrow = deep.to_8bit()
+                surf = np.concatenate([narrow.y.numpy(), np.stack([narrow.u.numpy(), narrow.v.numpy()], axis=-1).reshape(h // 2, w)])
+                d = np.abs(deep.to_rgb().numpy().astype(np.int32) - cv2.cvtColor(surf, cv2.COLOR_YUV2RGB_NV12).astype(np.int32))
+                dworst, dbad, dtotal = max(dworst, int(d.max())), dbad + int((d > 0).sum()), dtotal + d.size
+            print(f"[REPORT] YUV420Frame16.to_rgb (P010, 10 bits, bt601, limited) vs cv2 COLOR_YUV2RGB_NV12 on its to_8bit() frame (parity unpinned): max |diff| {dworst}, "
+                  f"{dbad} of {dtotal} bytes differ", flush=True)
             # YUV420Frame.from_rgb (the packer of include/vgh_video.h, bt601 limited range) against cv2.cvtColor(COLOR_RGB2YUV_I420): REPORTED as well -- cv2 has
             # its own fixed-point coefficients and takes a block's chroma its own way
             pworst, pbad, ptotal = 0, 0, 0
